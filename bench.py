@@ -17,6 +17,12 @@ Multi-GPU: messages are independent, so each rank owns its own batch (weak scali
 collective on the data path; the only collectives are the timing barriers and the gathers of
 the per-rank figures).
 
+A plain run (--gpus N --steps K --warmup W) generates the batch, runs W warm-up and K timed
+steps, checks the last step's round trip, writes --dump-outputs DIR if asked and prints one JSON
+line; ms_per_step is the wall time of one timed step.  Every side measurement (the compacted API
+leg, roofline.copy_ceiling, cpu_baseline, --host-inclusive, --latency) takes runs of its own and
+is made only under --full; a plain run reports null in their places.
+
 Measurement:
   * kernels_ms: HIP events on the launch stream around EACH codec kernel alone (the slot
     kernels are timed separately in slots_ms);
@@ -25,12 +31,12 @@ Measurement:
     is §8(d)'s 2(n+E) / (t_enc + t_dec);
   * roofline.traffic: HBM bytes per launch from rocprofv3 FETCH/WRITE passes, taken only from a
     profiles/*_traffic.json whose lib_sha256 matches the library being run (else null);
-  * cpu_baseline: the reference codec itself (oracle/_ref, compiled from the reference header
-    where it lies) on this host: 1 thread and all usable cores, sample_fraction 0.3 (the
+  * cpu_baseline (--full): the reference codec itself (oracle/_ref, compiled from the reference
+    header where it lies) on this host: 1 thread and all usable cores, sample_fraction 0.3 (the
     reference default) and 1.0 (parity mode); value = the default-config all-cores row.  A
     missing reference build is an error, not a silent fallback (--cpu-kind port times the C
     restatement instead, labelled as such);
-  * host_inclusive (--host-inclusive): pinned host buffers through tdt_encode_host /
+  * host_inclusive (--full --host-inclusive): pinned host buffers through tdt_encode_host /
     tdt_decode_host, every rank, next to the pinned hipMemcpyAsync H2D / D2H ceiling.
 """
 from __future__ import annotations
@@ -71,11 +77,20 @@ def parse():
     ap.add_argument("--compacted-steps", type=int, default=3,
                     help="timed steps of the compacted (look-back) API leg after the headline (0 = skip)")
     ap.add_argument("--seed", type=int, default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every side measurement: the compacted API leg, the HBM "
+                         "copy ceiling, the CPU baseline rows and, where asked for, --host-inclusive and --latency "
+                         "(a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step returned to DIR/<name>.npy "
+                         "(see dump_outputs)")
     ap.add_argument("--workload", choices=["c2", "c3", "c4", "c5"], default="c3",
                     help="c3 (default, the BASELINE metric): 262,144 x 64 KiB gradient; c2: 1 Mi x 1 KiB "
                          "uniform bytes; c4: 4 Mi Zipf(1.5)-sized (64 B - 1 MiB) gradient messages; c5: "
-                         "32 GiB of C3-style messages per GPU (256 GiB at 8 GPUs), host-inclusive leg on")
+                         "32 GiB of C3-style messages per GPU (256 GiB at 8 GPUs), host-inclusive leg on under --full")
     a = ap.parse_args()
+    if (a.host_inclusive or a.latency) and not a.full:
+        ap.error("--host-inclusive and --latency are side measurements: pass --full with them")
     if a.workload == "c2":
         a.msgs = a.msgs if a.msgs != 262144 else 1 << 20
         a.msg_bytes = 1024 if a.msg_bytes == 65536 else a.msg_bytes
@@ -572,6 +587,49 @@ def gather_obj(obj, world):
     return out
 
 
+DUMP_SEED = 0xD0D0
+DUMP_PER_MSG = 1 << 19  # per-message arrays: whole up to this many messages, else a sample
+DUMP_BYTES = 1 << 22    # sampled bytes of each of the two byte buffers
+
+
+def dump_outputs(torch, outdir, off, enc, eslot, elen, est, dec, dslot, dlen, dst):
+    """--dump-outputs: what the last timed step handed its caller, as <name>.npy (44 MB for the C3 batch, 55 MB at
+    the most):
+
+      elen, eslot, est     encode: blob lengths, slot offsets, statuses, one per message (eslot n+1)
+      dlen, dslot, dst     decode: message lengths, slot offsets, statuses
+      enc_bytes            DUMP_BYTES bytes of the blobs: message m (drawn uniformly) at byte
+                           floor(u * elen[m]) of its blob, u uniform in [0, 1) (only bytes inside a
+                           blob: the slack of a slot is never written)
+      dec_bytes            DUMP_BYTES bytes of the decoded payload at uniformly drawn offsets
+
+    Offsets and lengths are float64 (exact: far below 2^53), statuses and bytes float32.  The
+    per-message arrays are whole up to DUMP_PER_MSG messages, above that the same sorted sample of
+    messages for all six (eslot/dslot without their last entry then).  Every draw comes from
+    numpy's default_rng(DUMP_SEED) and depends on the batch's shape alone, so two builds run with
+    the same arguments write the same positions."""
+    import numpy as np
+    out = pathlib.Path(outdir)
+    out.mkdir(parents=True, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    n = int(elen.numel())
+    pick = None
+    if n > DUMP_PER_MSG:
+        pick = torch.from_numpy(np.sort(rng.choice(n, DUMP_PER_MSG, replace=False))).to(elen.device)
+    for name, t, kind in (("elen", elen, np.float64), ("eslot", eslot, np.float64), ("est", est, np.float32),
+                          ("dlen", dlen, np.float64), ("dslot", dslot, np.float64), ("dst", dst, np.float32)):
+        np.save(out / (name + ".npy"), (t if pick is None else t[pick]).cpu().numpy().astype(kind))
+    m = rng.integers(0, n, DUMP_BYTES)
+    u = rng.random(DUMP_BYTES)
+    ln = elen.cpu().numpy()[m]
+    pos = eslot.cpu().numpy()[m] + np.minimum((u * ln).astype(np.int64), np.maximum(ln - 1, 0))
+    got = enc[torch.from_numpy(pos).to(enc.device)].cpu().numpy().astype(np.float32)
+    np.save(out / "enc_bytes.npy", np.where(ln > 0, got, np.float32(0)))
+    total = int(off[-1].item() - off[0].item())
+    pos = torch.from_numpy(rng.integers(0, total, DUMP_BYTES)).to(dec.device)
+    np.save(out / "dec_bytes.npy", dec[pos].cpu().numpy().astype(np.float32))
+
+
 def main():
     a = parse()
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
@@ -694,6 +752,8 @@ def main():
     ok = bool(torch.equal(dec, data)) and int(est.abs().sum()) == 0 and int(dst.abs().sum()) == 0
     ok = ok and bool(torch.equal(dslot, off - off[0]))
     enc_bytes = int(elen.sum().item())
+    if a.dump_outputs and rank == 0:  # (rank 0's own batch; before any other leg reuses the buffers)
+        dump_outputs(torch, a.dump_outputs, off, enc, eslot, elen, est, dec, dslot, dlen, dst)
     avg = lambda i, j: sum(e[i].elapsed_time(e[j]) for e in evs) / a.steps  # ms
     t_enc, t_dec = avg(1, 2), avg(3, 4)
     t_eslot, t_dslot = avg(0, 1), avg(2, 3)
@@ -707,9 +767,10 @@ def main():
     # Compacted API leg (tdt_encode_batch / tdt_decode_batch: blobs and decoded messages packed
     # in message order, offsets by the kernels' decoupled look-back — the north_star's
     # variable-length output compaction), on the same batch after the timed loop; reported
-    # beside the headline, never as `value`.  Reuses the slotted buffers.
+    # beside the headline, never as `value`.  Reuses the slotted buffers.  (--full only, as every
+    # leg below that takes GPU or CPU runs of its own.)
     compacted = None
-    if a.compacted_steps > 0:
+    if a.full and a.compacted_steps > 0:
         coff = torch.empty(n + 1, dtype=torch.int64, device=dev)
         cdoff = torch.empty(n + 1, dtype=torch.int64, device=dev)
 
@@ -742,11 +803,11 @@ def main():
                      "roundtrip_ok": cok, "blob_bytes_equal_slotted": int(coff[-1].item()) == enc_bytes}
 
     host = None
-    if a.host_inclusive and a.workload != "c4":
+    if a.full and a.host_inclusive and a.workload != "c4":
         host = host_inclusive(torch, codec, data, off, n, mb)
         host["pcie_ceiling"] = pcie_ceiling(torch, dev)
     latency = (message_latency(torch, codec, data, sizes=[int(x) for x in a.latency_sizes.split(",")])
-               if a.latency and rank == 0 else None)
+               if a.full and a.latency and rank == 0 else None)
     per_rank = gather_obj({"rank": rank, "device": my_dev, "numa": numa, "msgs": n, "payload_bytes": payload,
                            "GiBps": round(my_rate, 3), "kernels_ms": [round(t_enc, 4), round(t_dec, 4)],
                            "host_inclusive": host}, world)
@@ -764,9 +825,9 @@ def main():
         src = recorded(pathlib.Path(os.environ.get("PSYNE_TDT_LIB") or _lib.LIB_PATH))
         tr = load_traffic(key, sha, src)
         traffic = tr["kernels"][dom].get("hbm_bytes_per_launch") if tr and dom in tr.get("kernels", {}) else None
-        ceil = copy_ceiling(torch, dev)  # (after the timed region; rank 0)
+        ceil = copy_ceiling(torch, dev) if a.full else None  # (after the timed region; rank 0)
         cpu = None
-        if a.cpu_seconds > 0 and a.workload == "c3" and world == 1:  # rank 0 at N=1 only
+        if a.full and a.cpu_seconds > 0 and a.workload == "c3" and world == 1:  # rank 0 at N=1 only
             if orig_affinity:
                 os.sched_setaffinity(0, orig_affinity)  # the whole host, not the GPU's NUMA node
             cpu = cpu_baseline(data, mb, a.cpu_seconds, a.cpu_threads, a.cpu_kind)
@@ -797,6 +858,7 @@ def main():
             "world_size_observed": observed_world,
             "steps": a.steps,
             "warmup": a.warmup,
+            "full": a.full,
             "ms_per_step": round(ms_per_step, 4),
             "higher_is_better": True,
             "scaling": "weak",
@@ -812,7 +874,7 @@ def main():
                          "traffic_source": tr["_file"] if traffic is not None else
                          "no PMC record for this library build (lib sha256 %s)" % sha[:16],
                          "algorithmic_bytes_per_launch": alg,
-                         "copy_ceiling": ceil, "frac_of_copy_ceiling": round(achieved / ceil["GBps"], 4),
+                         "copy_ceiling": ceil, "frac_of_copy_ceiling": round(achieved / ceil["GBps"], 4) if ceil else None,
                          "combined": {"achieved": round(combined, 2), "frac": round(combined / HBM_PEAK_GBS, 4),
                                       "def": "2(n+E) / (t_enc + t_dec), SURVEY.md 8(d)"}},
             "kernels_ms": {"encode": round(t_enc, 4), "decode": round(t_dec, 4)},

@@ -106,6 +106,22 @@ def test_bench_refuses_world_size_mismatch():
     assert p.returncode == 2 and "WORLD_SIZE=3" in p.stderr
 
 
+def test_bench_side_measurements_need_full(monkeypatch):
+    """--host-inclusive and --latency are made only under --full: alone they are an argument error,
+    never a flag that is quietly dropped; --full and --dump-outputs are off by default."""
+    import bench
+    for flag in ("--host-inclusive", "--latency"):
+        monkeypatch.setattr("sys.argv", ["bench.py", flag])
+        with pytest.raises(SystemExit) as e:
+            bench.parse()
+        assert e.value.code == 2
+        monkeypatch.setattr("sys.argv", ["bench.py", "--full", flag])
+        assert bench.parse().full is True
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+
+
 def test_bench_launcher_never_initialises_hip():
     """`bench.py --gpus N` (the driver's SCALE launch) starts its ranks from a parent that never
     touches HIP: it counts GPUs from the KFD topology, never imports torch, and refuses more GPUs

@@ -108,7 +108,9 @@ def test_bench_two_ranks_shared_device(launcher):
     explicit torch.distributed.run it must join the launched ranks."""
     env = dict(os.environ, PSYNE_BENCH_SHARED_DEVICE="1", OMP_NUM_THREADS="4")
     env.pop("WORLD_SIZE", None)
-    args = ["bench.py", "--gpus", "2", "--msgs", "4096", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0"]
+    # --full: the compacted API leg and the copy ceiling run on the two-rank path too
+    args = ["bench.py", "--gpus", "2", "--msgs", "4096", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0",
+            "--full"]
     if launcher == "plain":
         cmd = [sys.executable] + args
     else:
@@ -123,6 +125,7 @@ def test_bench_two_ranks_shared_device(launcher):
     assert [x["rank"] for x in r["per_rank"]] == [0, 1]
     assert all(x["device"]["local_rank"] == 0 for x in r["per_rank"])  # shared-device rehearsal
     assert r["value"] > 0 and r["cpu_baseline"] is None
+    assert r["compacted"]["roundtrip_ok"] is True and r["roofline"]["copy_ceiling"]["copy_ok"] is True
 
 
 @pytest.mark.timeout(300)
@@ -144,6 +147,36 @@ def test_bench_eight_ranks_shared_device():
     assert r["n_gpus"] == 8 and r["world_size_observed"] == 8 and r["roundtrip_ok"] is True
     assert [x["rank"] for x in r["per_rank"]] == list(range(8))
     assert r["scaling"] == "weak" and r["value"] > 0
+
+
+@pytest.mark.timeout(240)
+def test_bench_plain_run_dumps_outputs(tmp_path):
+    """A plain `bench.py --gpus 1` run makes none of the --full measurements, and --dump-outputs
+    writes the last timed step's outputs as float32 / float64 .npy files of at most 64 MB."""
+    env = dict(os.environ, OMP_NUM_THREADS="4")
+    env.pop("WORLD_SIZE", None)
+    env.pop("PSYNE_BENCH_SHARED_DEVICE", None)
+    n, mb = 4096, 65536
+    p = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--msgs", str(n), "--steps", "2", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path / "out")], cwd=ROOT, env=env, capture_output=True, text=True,
+                       timeout=220)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
+    r = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
+    assert r["steps"] == 2 and r["ms_per_step"] > 0 and r["roundtrip_ok"] is True and r["full"] is False
+    assert "compacted" not in r and r["cpu_baseline"] is None and r["roofline"]["copy_ceiling"] is None
+    got = {q.stem: np.load(q) for q in (tmp_path / "out").glob("*.npy")}
+    assert sorted(got) == ["dec_bytes", "dlen", "dslot", "dst", "elen", "enc_bytes", "eslot", "est"]
+    assert all(v.dtype in (np.float32, np.float64) for v in got.values())
+    assert sum(v.nbytes for v in got.values()) <= 64e6
+    assert got["elen"].shape == (n,) and got["eslot"].shape == (n + 1,) and got["dslot"].shape == (n + 1,)
+    assert not got["est"].any() and not got["dst"].any()
+    assert np.array_equal(got["dlen"], np.full(n, mb)) and np.array_equal(got["dslot"], np.arange(n + 1) * mb)
+    assert np.all(np.diff(got["eslot"]) >= got["elen"]) and np.all(got["elen"] > 0)
+    assert r["compression_ratio"] == round(n * mb / got["elen"].sum(), 4)
+    # 70 % of the payload's floats are exact zeros (four zero bytes each) and a byte of the others
+    # is zero about once in 256: 0.701 of the sampled bytes, +- 0.0002 (1 sigma) over 4 Mi draws
+    assert 0.69 < (got["dec_bytes"] == 0).mean() < 0.72
+    assert got["enc_bytes"].min() >= 0 and got["enc_bytes"].max() <= 255
 
 
 @pytest.mark.timeout(240)

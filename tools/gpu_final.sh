@@ -21,7 +21,7 @@ timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > "$OUT/
 rc=$?; tail -1 "$OUT/smoke.log"; [ $rc -eq 0 ] || exit $rc
 fi
 if on bench; then
-timeout -k 10 400 python -u bench.py > "$OUT/bench.log" 2>&1
+timeout -k 10 400 python -u bench.py --full > "$OUT/bench.log" 2>&1
 rc=$?; tail -1 "$OUT/bench.log" | cut -c1-400; [ $rc -eq 0 ] || exit $rc
 fi
 if on rocprof; then
@@ -39,7 +39,7 @@ PMC_KEY=c4_4194304x65536 bash tools/profile_pmc.sh "$OUT/pmc_c4" --workload c4 -
 fi
 if on c2_c4; then
 for wl in c2 c4; do
-  timeout -k 10 400 python -u bench.py --workload $wl --steps 5 --warmup 2 --cpu-seconds 0 > "$OUT/bench_$wl.log" 2>&1
+  timeout -k 10 400 python -u bench.py --full --workload $wl --steps 5 --warmup 2 --cpu-seconds 0 > "$OUT/bench_$wl.log" 2>&1
   rc=$?; tail -1 "$OUT/bench_$wl.log" | cut -c1-200; [ $rc -eq 0 ] || exit $rc
 done
 fi
