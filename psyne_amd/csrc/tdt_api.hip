@@ -483,8 +483,13 @@ template <int WS>
 int launch_slotted(tdt_ctx *c, PlanWS &pw, psy::EncodeArgs a, hipStream_t s) {
     using psy::MODE_ENCODE;
     const uint32_t n = a.n_msgs;
+    // the list-entry prefetch of the slotted kernels (EncodeArgs::list) reads entry
+    // min(i, n - 1) of a class list before its count: n >= 1, and every list holds n entries
+    // (ensure_plan: five lists of n entries behind the counters)
+    if (n == 0) return set_err(TDT_E_ARG, "slotted encode launch without messages");
     int st = ensure_plan(pw, n, s);
     if (st) return st;
+    if (pw.bytes < 256 + 20ull * n) return set_err(TDT_E_ARG, "plan buffer smaller than five lists of n entries");
     const bool capturing = ::capturing(s);
     CountHist &H = pw.eh;
     if (!capturing) H.refresh();  // (event queries are not capturable)

@@ -43,8 +43,16 @@ __device__ unsigned long long psy_prof[32];
 #endif
 #ifdef PSY_ASM_MARKS
 #define PSY_ASM_ROUND(p) asm volatile(";@@ROUND " #p ::)
+// (the encode's constant-layout arm marks its regions <p>c, so that tools/isa_spills.py counts
+// the two arms apart)
+#define PSY_ASM_ROUND_L(cl, p)             \
+    do {                                   \
+        if constexpr (cl) PSY_ASM_ROUND(p##c); \
+        else PSY_ASM_ROUND(p);             \
+    } while (0)
 #else
 #define PSY_ASM_ROUND(p) ((void)0)
+#define PSY_ASM_ROUND_L(cl, p) ((void)0)
 #endif
 
 template <int CTRL, int ROWMASK = 0xf, int BANKMASK = 0xf>

@@ -102,7 +102,10 @@ struct EncodeArgs {
     uint64_t *out_len;         // slotted outputs: blob lengths
     uint64_t min_tensor;
     int32_t policy_on;  // bandwidth < threshold && cpu <= threshold (host-evaluated atomics)
-    // slotted kernels: message ids from a class list (null: message id = blockIdx)
+    // slotted kernels: message ids from a class list (null: message id = blockIdx).
+    // Invariant (checked by the host's launch_slotted): every class list — list, list2 — holds at
+    // least n_msgs entries whatever its count says, and a slotted launch has n_msgs >= 1: the
+    // kernel reads entry min(i, n_msgs - 1) beside the count, before it knows whether i is listed.
     const uint32_t *list;
     const uint32_t *list_count;  // the list's length (device memory: the plan's counter)
     uint32_t list_base;  // first list / tile entry of this launch (grids of < 2^32 threads)
@@ -347,8 +350,7 @@ __device__ __forceinline__ uint32_t spread2(uint32_t e) {
 //         between messages.
 // Occupancy target (min waves per SIMD) of the 512-lane teams: 4 workgroups per CU = 8 waves per
 // SIMD (64 VGPRs; round 6: the C3 encode 7.44 -> 7.29 ms against 6 waves at 73 VGPRs, same box,
-// alternating runs; its 8-VGPR spill is stored in pass A1 and reloaded in pass B, 3 dwords per
-// lane).  The 256-lane teams stay at 6: their LDS (26 KB) allows no more.
+// alternating runs).  The 256-lane teams stay at 6: their LDS (26 KB) allows no more.
 #ifndef PSY_ENC_WPE
 #define PSY_ENC_WPE 8
 #endif
@@ -358,6 +360,12 @@ __device__ __forceinline__ uint32_t spread2(uint32_t e) {
 #endif
 #ifndef PSY_ENC_WPE_LB
 #define PSY_ENC_WPE_LB 6
+#endif
+// 1: the slotted main instance (word size 4, 512 lanes, resident) also holds the constant-layout arm
+// of the post-mapping passes (encode_one's CARM); 0: the runtime-layout body alone (no scratch at 64
+// VGPRs, but 1183 against 1207 GiB/s on C3: DESIGN.md §5)
+#ifndef PSY_ENC_DUAL
+#define PSY_ENC_DUAL 1
 #endif
 #define PSY_ENC_WAVES(TEAM, LB) ((TEAM) >= 512 ? ((LB) ? PSY_ENC_WPE_LB : PSY_ENC_WPE) : (TEAM) >= 256 ? 6 : 7)
 
@@ -370,7 +378,9 @@ __device__ __forceinline__ uint32_t spread2(uint32_t e) {
 // body's live state out of the resident body's register allocation.
 enum { PATH_BOTH = 0, PATH_RES = 1, PATH_STREAM = 2 };
 
-template <int WS, int TEAM, int G, int MODE, int LB, int TL, int PATH = PATH_BOTH>
+// CARM: the resident body also holds the post-mapping passes compiled for the speculated mapping's
+// slot layout as constants (the "constant arm"), taken when the message's mapping is that one.
+template <int WS, int TEAM, int G, int MODE, int LB, int TL, int PATH = PATH_BOTH, bool CARM = false>
 __device__ __forceinline__ void encode_one(const EncodeArgs &a, uint8_t *smem, uint32_t msg, uint32_t lj,
                                            uint32_t tile) {
     static_assert(TL == 0 || (TEAM * G == (int)kTileGroups && MODE == MODE_ENCODE && !LB), "tile shape");
@@ -527,7 +537,19 @@ __device__ __forceinline__ void encode_one(const EncodeArgs &a, uint8_t *smem, u
     // Resident rounds live in fully unrolled loops (compile-time indices only): indexing the
     // arrays with a run-time round number would push them to scratch.
     uint4 dres[GR];     // the round's 16 bytes per lane; after pass A1 its slot word T
-    uint32_t cres[GR];  // run-start masks (A1 → A2), then chunk-start masks (A2 → B)
+    // run-start masks (A1 → A2), then chunk-start masks (A2 → B): two rounds per register, round
+    // r in cres[r / 2] shifted by kCS·(r & 1) — a mask has 16 bits; in the byte-lane layout
+    // (sb_pos: the low nibble of each byte) the odd round takes the high nibbles
+    constexpr bool kBLR = RES && WS <= 4 && TL != 2;
+    constexpr uint32_t kCS = kBLR ? 4u : 16u, kCM = kBLR ? 0x0f0f0f0fu : 0xffffu;
+    uint32_t cres[(GR + 1) / 2];
+    auto cget = [&](uint32_t cm, uint32_t r) __attribute__((always_inline)) -> uint32_t {
+        return RES ? (cm >> (kCS * (r & 1u))) & kCM : cm;
+    };
+    auto cput = [&](uint32_t &cm, uint32_t r, uint32_t m) __attribute__((always_inline)) {
+        if constexpr (RES) cm = (cm & ~(kCM << (kCS * (r & 1u)))) | (m << (kCS * (r & 1u)));
+        else cm = m;
+    };
     // glibc log2 tables for the entropy pass, fetched BEFORE the message's rounds so that the
     // LDS copy below waits for these loads only (issued after the rounds, its wait would
     // cover every round's load and stall the team until the whole message had arrived)
@@ -540,6 +562,7 @@ __device__ __forceinline__ void encode_one(const EncodeArgs &a, uint8_t *smem, u
             l2v[k] = reinterpret_cast<const uint4 *>(i < 64 ? c_log2_tab : c_log2_tab2)[i & 63];
         }
     }
+    auto load_rounds = [&]() __attribute__((always_inline)) {
     if constexpr (RES) {
         // One unconditional dwordx4 per lane and round, all in flight before the first use (a
         // branchy load per round made the compiler wait for each before issuing the next).
@@ -557,15 +580,17 @@ __device__ __forceinline__ void encode_one(const EncodeArgs &a, uint8_t *smem, u
             typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
             const u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, vo, r * 1024, PSY_ENC_LDAUX);
             dres[r] = make_uint4(v.x, v.y, v.z, v.w);
-            cres[r] = 0;
+            cres[r >> 1] = 0;
         }
     }
+    };
+    load_rounds();
     // body(r, data&, cres&, res) for every round r < RW of this wave, in order.
     auto for_rounds = [&](auto &&body) __attribute__((always_inline)) {
         if constexpr (RES) {
 #pragma unroll
             for (int r = 0; r < G; ++r)
-                if ((uint32_t)r < RW) body((uint32_t)r, dres[r], cres[r], std::true_type{});
+                if ((uint32_t)r < RW) body((uint32_t)r, dres[r], cres[r >> 1], std::true_type{});
         } else {
             // rounds r < RW of the wave that hold a group of the message (uniform)
             auto live = [&](uint32_t r) __attribute__((always_inline)) {
@@ -1104,12 +1129,42 @@ __device__ __forceinline__ void encode_one(const EncodeArgs &a, uint8_t *smem, u
     }
 
     if constexpr (MODE != MODE_ANALYZE) {
+        // Everything after the mapping — slot layout, passes A1 / A2, the header, pass B — is one
+        // callable over a layout tag.  Runtime tag: the layout is loaded from the SlotTable entry of
+        // the message's mapping into SGPRs.  Constant tag (CL): every layout value is a compile-time
+        // constant of make_slot_layout<WS>(kSpec) — selectors, masks and the ·Ls multiplications
+        // fold into the instructions, ns2 and the stream switch in the sweeps resolve at compile
+        // time, and none of them occupies an SGPR across the passes.  The mapping is uniform over
+        // the workgroup, so the team branches once, below; both arms are terminal.
+        constexpr bool DUAL = CARM && RES && kSpec != 0xffffffffu;
+        auto post = [&](auto ltag) __attribute__((always_inline)) {
+        constexpr bool CL = decltype(ltag)::value;
+        // The resident body takes its lane and thread ids afresh here (two v_mbcnt) instead of
+        // keeping the kernel's alive through the histogram and entropy passes beside the
+        // message's 32 registers.  (Volatile: plain C++ would be merged with the earlier values.)
+        int lane_ = lane_id();
+        if constexpr (RES) asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane_));
+        const int lane = lane_;
+        const int tid = RES ? wv * 64 + lane_ : (int)threadIdx.x;
         // ------------------------------------------------ slot layout
         // separate_byte_streams :527-549: slot j < L0 is stream-0 byte j of the group
         // (word j / k0, position pos0[j % k0]); slot j >= L0 is stream-1 byte j - L0.
         uint32_t ns, L0, k0, k1, selA[4], selB[4], edA, edB;
-        const uint32_t mapbits = __builtin_amdgcn_readfirstlane(wm[M_MAPBITS]);
-        if constexpr (WS <= 8) {
+        const uint32_t mapbits = CL ? kSpec : __builtin_amdgcn_readfirstlane(wm[M_MAPBITS]);
+        if constexpr (CL) {
+            constexpr SlotLayout CS = make_slot_layout<WS>(kSpec);
+            ns = CS.ns;
+            L0 = CS.L0;
+            k0 = CS.k0;
+            k1 = CS.k1;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                selA[q] = CS.selA[q];
+                selB[q] = CS.selB[q];
+            }
+            edA = CS.edA;
+            edB = CS.edB;
+        } else if constexpr (WS <= 8) {
             // a constant table indexed by the mapping bits: scalar loads, no barrier
             const SlotLayout &SL = slot_layout<WS>(mapbits);
             ns = SL.ns;
@@ -1188,7 +1243,7 @@ __device__ __forceinline__ void encode_one(const EncodeArgs &a, uint8_t *smem, u
         // start masks of the resident word-size <= 4 bodies are kept in the byte-lane layout
         // (sb_pos); everything else (streaming bodies, tiles' count pass, A2's scans) in the
         // compact 16-bit one
-        constexpr bool BL = RES && WS <= 4 && TL != 2;
+        constexpr bool BL = kBLR;
         const uint32_t lowX = BL ? sb_spread(lowL0) : lowL0;   // stream-0 slots
         const uint32_t highX = BL ? sb_spread(~lowL0 & 0xffffu) : (~lowL0 & 0xffffu);  // stream-1 slots
         const uint32_t fullX = BL ? 0x0f0f0f0fu : 0xffffu;
@@ -1352,7 +1407,7 @@ __device__ __forceinline__ void encode_one(const EncodeArgs &a, uint8_t *smem, u
         if (!spec_hit) {
             uint32_t edc = edc0;
             for_rounds([&](uint32_t r, uint4 &d, uint32_t &cm, auto res) __attribute__((always_inline)) {
-                PSY_ASM_ROUND(A1);
+                PSY_ASM_ROUND_L(CL, A1);
                 const uint32_t g = gw0 + r * 64 + lane;
                 const uint32_t ed = edges(d);
                 uint32_t T[4];
@@ -1360,7 +1415,7 @@ __device__ __forceinline__ void encode_one(const EncodeArgs &a, uint8_t *smem, u
                 const uint32_t V = full_round(r) ? fullX : (BL ? sb_spread(vmask(vbytes(g))) : vmask(vbytes(g)));
                 const uint32_t m = run_mask(T, ed, edc, r == 0u && gw0 == 0u, V, std::integral_constant<bool, BL>{});
                 edc = rdlane(ed, 63);
-                cm = m;
+                cput(cm, r, m);
                 if constexpr (decltype(res)::value) d = make_uint4(T[0], T[1], T[2], T[3]);
                 constexpr bool SW = decltype(res)::value && TL != 2;  // scalar last-start tracking
                 const uint32_t m0 = m & lowX;
@@ -1410,7 +1465,7 @@ __device__ __forceinline__ void encode_one(const EncodeArgs &a, uint8_t *smem, u
                 uint32_t mv = 0;
 #pragma unroll
                 for (int r = 0; r < GR; ++r)
-                    if ((uint32_t)r == lr[c]) mv = rdlane(cres[r], (int)l);
+                    if ((uint32_t)r == lr[c]) mv = rdlane(cget(cres[r >> 1], (uint32_t)r), (int)l);
                 uint32_t hb;
                 if constexpr (BL) hb = sb_slot(hibit(c ? mv & highX : mv & lowX)) - (c ? L0 : 0u);
                 else hb = hibit(c ? mv >> L0 : mv & lowL0);
@@ -1469,12 +1524,12 @@ __device__ __forceinline__ void encode_one(const EncodeArgs &a, uint8_t *smem, u
             uint32_t rcarry[2] = {rin[0], rin[1]};
             uint32_t edc = edc0;
             for_rounds([&](uint32_t r, uint4 &d, uint32_t &cm, auto res) __attribute__((always_inline)) {
-                PSY_ASM_ROUND(A2);
+                PSY_ASM_ROUND_L(CL, A2);
                 const uint32_t g = gw0 + r * 64 + lane;
                 const uint32_t V = full_round(r) ? 0xffffu : vmask(vbytes(g));
                 uint32_t m;
                 if constexpr (decltype(res)::value) {
-                    m = BL ? sb_compact(cm) : cm;
+                    m = BL ? sb_compact(cget(cm, r)) : cget(cm, r);
                 } else {
                     uint32_t T[4];
                     tmat(d, T);
@@ -1483,7 +1538,7 @@ __device__ __forceinline__ void encode_one(const EncodeArgs &a, uint8_t *smem, u
                     edc = rdlane(ed, 63);
                 }
                 const uint32_t C = chunk_round(r, m, rcarry, g, V);
-                cm = BL ? sb_spread(C) : C;
+                cput(cm, r, BL ? sb_spread(C) : C);
                 pc0 += popc(C & lowL0);
                 pc1 += popc(C >> L0);
             });
@@ -1630,7 +1685,7 @@ __device__ __forceinline__ void encode_one(const EncodeArgs &a, uint8_t *smem, u
 #ifdef PSY_X_NOEMIT
             if (r < 100) return;
 #endif
-            PSY_ASM_ROUND(B);
+            PSY_ASM_ROUND_L(CL, B);
             const uint32_t T[4] = {Tw.x, Tw.y, Tw.z, Tw.w};
             const uint32_t gr = gw0 + r * 64;
             const uint32_t c0 = popc(C & lowL0);
@@ -1777,7 +1832,7 @@ __device__ __forceinline__ void encode_one(const EncodeArgs &a, uint8_t *smem, u
         };
         // C in the byte-lane layout for the resident body (BL), compact for the streaming one
         auto sweep6 = [&](const uint4 &Tw, uint32_t C, uint32_t pexc, uint32_t Stot) __attribute__((always_inline)) {
-            PSY_ASM_ROUND(B);
+            PSY_ASM_ROUND_L(CL, B);
             const uint32_t T[4] = {Tw.x, Tw.y, Tw.z, Tw.w};
             // entry 0 of a region holds the pending chunk (when there is one); the batch's own
             // entries follow it
@@ -1786,10 +1841,21 @@ __device__ __forceinline__ void encode_one(const EncodeArgs &a, uint8_t *smem, u
             uint32_t D = L0 == 0 ? D1 : D0;
             // entries of slots q + 4t, two per dword: E[q][0] = slots q, q+4; E[q][1] = q+8, q+12
             uint32_t E[4][2];
+            uint32_t pq[4] = {pos6[0], pos6[1], pos6[2], pos6[3]};
+            if constexpr (RES) {
+                // The resident body keeps pos6[0] alone across the rounds (three VGPRs less where the
+                // whole message is live) and rebuilds the others in every round: L0 is a multiple of
+                // 4, so byte t of every pos6[q] comes from the same stream, and both stream bases are
+                // multiples of 4, so adding q carries into no neighbouring byte.  (Volatile: as plain
+                // C++ the sums are common to all rounds and would be kept live instead.)
+                asm volatile("v_add_u32_e32 %0, 0x01010101, %1" : "=v"(pq[1]) : "v"(pos6[0]));
+                asm volatile("v_add_u32_e32 %0, 0x02020202, %1" : "=v"(pq[2]) : "v"(pos6[0]));
+                asm volatile("v_add_u32_e32 %0, 0x03030303, %1" : "=v"(pq[3]) : "v"(pos6[0]));
+            }
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                E[q][0] = perm(T[q], pos6[q], 0x05010400u);
-                E[q][1] = perm(T[q], pos6[q], 0x07030602u);
+                E[q][0] = perm(T[q], pq[q], 0x05010400u);
+                E[q][1] = perm(T[q], pq[q], 0x07030602u);
             }
 #pragma unroll
             for (int j = 0; j < 16; ++j) {
@@ -1968,7 +2034,8 @@ __device__ __forceinline__ void encode_one(const EncodeArgs &a, uint8_t *smem, u
             for (int r = 0; r < G; ++r) {
                 if ((uint32_t)r < RW) {
                     uint32_t pexc, Stot;
-                    scan6(cres[r], pexc, Stot);
+                    const uint32_t Cr = cget(cres[r >> 1], (uint32_t)r);
+                    scan6(Cr, pexc, Stot);
                     const uint32_t over = (u6[0] + (Stot & 0xffffu) > cap6[0] ? 1u : 0u) |
                                           (u6[1] + (Stot >> 16) > cap6[1] ? 1u : 0u);
                     if (over != 0u && !fresh) {
@@ -1980,19 +2047,20 @@ __device__ __forceinline__ void encode_one(const EncodeArgs &a, uint8_t *smem, u
                     }
                     fresh = false;
 #ifndef PSY_X_NOEMIT
-                    sweep6(dres[r], cres[r], pexc, Stot);
+                    sweep6(dres[r], Cr, pexc, Stot);
 #endif
-                    if ((uint32_t)(r + 1) == RW) {
-                        if (!flush_batch((uint32_t)r + 1u)) return;
-                    }
                 }
             }
+            // the wave's last batch (RW >= 1: a compressed message has at least 4 groups).  One
+            // flush site after the rounds instead of one in each of them: the flush is the largest
+            // piece of pass B, and the unrolled rounds each held two copies of it.
+            if (!flush_batch(RW)) return;
           } else
           {
 #pragma unroll
             for (int r = 0; r < G; ++r) {
                 if ((uint32_t)r < RW) {
-                    emit5((uint32_t)r, dres[r], cres[r]);
+                    emit5((uint32_t)r, dres[r], cget(cres[r >> 1], (uint32_t)r));
                 }
             }
           }
@@ -2061,6 +2129,15 @@ __device__ __forceinline__ void encode_one(const EncodeArgs &a, uint8_t *smem, u
             }
         }
         PSY_PROF_MARK(6);
+        };  // post
+        if constexpr (DUAL) {
+            // (float tensors take the speculated mapping: the register allocator weighs the arms by this)
+            if (__builtin_expect_with_probability(__builtin_amdgcn_readfirstlane(wm[M_MAPBITS]) == kSpec, 1, 0.999))
+                post(std::true_type{});
+            else post(std::false_type{});
+        } else {
+            post(std::false_type{});
+        }
     }
     };  // run
     if constexpr (PATH == PATH_RES) {
@@ -2140,8 +2217,11 @@ __global__ __launch_bounds__(TEAM, PSY_ENC_WAVES(TEAM, LB)) void tdt_encode_kern
             const uint32_t ic = i0 < a.n_msgs ? i0 : a.n_msgs - 1u;
             const uint32_t e2 = a.list2 ? a.list2[ic] : 0u, e1 = a.list[ic];
             if (i0 >= cnt) return;
-            encode_one<WS, TEAM, G, MODE, LB, 0, PATH>(a, smem, i0 < n2 ? e2 : (n2 == 0u ? e1 : a.list[i0 - n2]), 0,
-                                                       0);
+            // the slotted main instance of the medium list holds the constant arm (word size 4:
+            // float tensors; the other instances stay generic — code size and build time)
+            constexpr bool CARM = PSY_ENC_DUAL && WS == 4 && TEAM == 512 && PATH == PATH_RES && MODE == MODE_ENCODE;
+            encode_one<WS, TEAM, G, MODE, LB, 0, PATH, CARM>(a, smem, i0 < n2 ? e2 : (n2 == 0u ? e1 : a.list[i0 - n2]),
+                                                             0, 0);
         } else {
             if (i0 >= cnt) return;
             one(i0);

@@ -1,25 +1,65 @@
-"""Per-kernel resource usage of the library (one line per kernel: VGPRs, spills, occupancy,
-LDS), from hipcc's kernel-resource-usage remarks.  Usage: python tools/kres.py [-DPSY_FAST_BUILD]"""
+"""Per-kernel resource usage of the library (one line per kernel: VGPRs, spills, scratch, occupancy,
+LDS), from hipcc's kernel-resource-usage remarks over the translation units psyne_amd/build.py
+compiles: tdt_api.hip and tdt_enc_ws.hip once per word size (the encode kernels live there).
+Usage: python tools/kres.py [--ws 4[,8...]] [--grep SUBSTRING] [-DFLAG ...]   (device code only)"""
+import concurrent.futures
+import pathlib
 import re
 import subprocess
 import sys
+import tempfile
 
-cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-c", *sys.argv[1:],
-       "-I", "include", "psyne_amd/csrc/tdt_api.hip", "-o", "/tmp/kres.o", "-Rpass-analysis=kernel-resource-usage"]
-err = subprocess.run(cmd, capture_output=True, text=True).stderr
-cur, rows = None, []
-for line in err.splitlines():
-    m = re.search(r"remark:\s+(Function Name|VGPRs|AGPRs|SGPRs Spill|VGPRs Spill|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\S+)", line)
-    if not m:
-        continue
-    k, v = m.groups()
-    if k == "Function Name":
-        cur = {"name": v}
-        rows.append(cur)
-    elif cur is not None:
-        cur[k] = v
-for r in rows:
-    name = subprocess.run(["c++filt", r["name"]], capture_output=True, text=True).stdout.strip()
-    name = name.replace("psy::", "").replace("(psy::EncodeArgs)", "").replace("(psy::DecodeArgs)", "")
-    print("%-60s vgpr %3s vspill %3s sspill %3s occ %s lds %s" % (name[:60], r.get("VGPRs"), r.get("VGPRs Spill"),
-          r.get("SGPRs Spill"), r.get("Occupancy [waves/SIMD]"), r.get("LDS Size [bytes/block]")))
+ROOT = pathlib.Path(__file__).resolve().parent.parent
+KEYS = ("Function Name|VGPRs|AGPRs|ScratchSize \\[bytes/lane\\]|SGPRs Spill|VGPRs Spill|"
+        "Occupancy \\[waves/SIMD\\]|LDS Size \\[bytes/block\\]")
+
+
+def remarks(src, flags, out):
+    cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "--cuda-device-only", "-O3", "-std=c++17", "-c", *flags,
+           "-I", str(ROOT / "include"), str(src), "-o", out, "-Rpass-analysis=kernel-resource-usage"]
+    p = subprocess.run(cmd, capture_output=True, text=True)
+    if p.returncode:
+        sys.exit(p.stderr[-2000:])
+    cur, rows = None, []
+    for line in p.stderr.splitlines():
+        m = re.search(r"remark:\s+(" + KEYS + r"): (\S+)", line)
+        if not m:
+            continue
+        k, v = m.groups()
+        if k == "Function Name":
+            cur = {"name": v}
+            rows.append(cur)
+        elif cur is not None:
+            cur[k] = v
+    return rows
+
+
+def main(argv):
+    ws_list, grep, flags = [1, 2, 4, 8, 16], None, []
+    it = iter(argv)
+    for a in it:
+        if a == "--ws":
+            ws_list = [int(x) for x in next(it).split(",")]
+        elif a == "--grep":
+            grep = next(it)
+        else:
+            flags.append(a)
+    csrc = ROOT / "psyne_amd" / "csrc"
+    with tempfile.TemporaryDirectory() as tmp:
+        jobs = [(csrc / "tdt_api.hip", flags, tmp + "/api.o")]
+        jobs += [(csrc / "tdt_enc_ws.hip", flags + ["-DPSY_INST_WS=%d" % ws], tmp + "/ws%d.o" % ws) for ws in ws_list]
+        with concurrent.futures.ThreadPoolExecutor(len(jobs)) as ex:
+            rows = [r for rs in ex.map(lambda j: remarks(*j), jobs) for r in rs]
+    names = subprocess.run(["c++filt"], input="\n".join(r["name"] for r in rows), capture_output=True,
+                           text=True).stdout.splitlines()
+    for r, name in zip(rows, names):
+        name = name.replace("void ", "").replace("psy::", "").replace("(EncodeArgs)", "").replace("(DecodeArgs)", "")
+        if grep and grep not in name:
+            continue
+        print("%-64s vgpr %3s vspill %3s sspill %3s scratch %4s occ %s lds %s" % (
+            name[:64], r.get("VGPRs"), r.get("VGPRs Spill"), r.get("SGPRs Spill"),
+            r.get("ScratchSize [bytes/lane]"), r.get("Occupancy [waves/SIMD]"), r.get("LDS Size [bytes/block]")))
+
+
+if __name__ == "__main__":
+    main(sys.argv[1:])
