@@ -61,7 +61,9 @@ extern "C" {
 #define TDT_E_TRUNCATED 3     /* header or stream runs past the blob (reference: UB) */
 #define TDT_E_BAD_MAPPING 4   /* mapping shorter than word_size or value >= num_streams (reference: UB) */
 #define TDT_E_CAPACITY 5      /* output buffer too small for this message */
-#define TDT_E_UNSUPPORTED 6   /* word_size this build does not implement on the GPU */
+#define TDT_E_UNSUPPORTED 6   /* word_size above 64 (tdt_ctx_create, or a blob's header); a compacted
+                                 encode at a word size other than 1, 2, 4, 8, 16 under stream capture
+                                 or TDT_OPT_NO_TWO_PHASE (tdt_last_error has the text) */
 #define TDT_E_BAD_HEADER 7    /* word_size == 0 in a blob (reference: division by zero) */
 #define TDT_E_CONFIG 8        /* invalid tdt_config */
 #define TDT_E_HIP 10          /* HIP runtime error (tdt_last_error has the text) */
@@ -73,7 +75,9 @@ extern "C" {
  * (auto_detect_clusters, max_clusters, enable_simd) are omitted. */
 typedef struct tdt_config {
     float sample_fraction;           /* accepted; the GPU always uses the full sample (1.0) */
-    int32_t word_size;               /* 1, 2, 4, 8 or 16 */
+    int32_t word_size;               /* 1..64 (the record stride: 3 RGB8, 12 float3, ...); 1, 2, 4, 8
+                                        and 16 run the tuned kernels, every other width the generic
+                                        ones; <= 0: TDT_E_CONFIG, > 64: TDT_E_UNSUPPORTED */
     double bandwidth_threshold_mbps; /* default 100.0 */
     double cpu_usage_threshold;      /* default 0.8 */
     uint64_t min_tensor_size;        /* default 1024 */
@@ -114,7 +118,11 @@ uint64_t tdt_encode_bound(uint64_t n, int32_t word_size);
 
 /* Encode a batch.  out_cap: bytes available at d_out (use the sum of tdt_encode_bound).
  * Messages whose compressed blob would overflow out_cap get TDT_E_CAPACITY.
- * Returns TDT_OK or an argument/HIP error; per-message results go to d_status. */
+ * Returns TDT_OK or an argument/HIP error; per-message results go to d_status.
+ * At a word size other than 1, 2, 4, 8, 16 this call and tdt_encode_with_mapping_batch always
+ * encode into slots and gather (they read the batch's byte count back), so under stream capture
+ * or with TDT_OPT_NO_TWO_PHASE they return TDT_E_UNSUPPORTED: capture the slotted entry points
+ * (tdt_encode_slots + tdt_encode_batch_into), which read nothing back at any word size. */
 int tdt_encode_batch(tdt_ctx *ctx, const uint8_t *d_in, const uint64_t *d_in_off, uint32_t n_msgs,
                      uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_off, int32_t *d_status,
                      void *hip_stream);
@@ -126,7 +134,8 @@ int tdt_encode_with_mapping_batch(tdt_ctx *ctx, const uint8_t *d_in, const uint6
                                   uint64_t out_cap, uint64_t *d_out_off, int32_t *d_status,
                                   void *hip_stream);
 
-/* Decode a batch of blobs (any mix of UNCP and TDT).  Output compacted by decoded size. */
+/* Decode a batch of blobs (any mix of UNCP and TDT, of any word sizes up to 64 whatever the
+ * context's own; a blob with a larger one gets TDT_E_UNSUPPORTED).  Output compacted by decoded size. */
 int tdt_decode_batch(tdt_ctx *ctx, const uint8_t *d_in, const uint64_t *d_in_off, uint32_t n_msgs,
                      uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_off, int32_t *d_status,
                      void *hip_stream);

@@ -20,6 +20,8 @@ ARCH = os.environ.get("PSYNE_ARCH", "gfx950")
 SOURCES = [CSRC / "tdt_api.hip"]  # (diagnostic single-TU builds compile this file alone)
 ENC_WS_SRC = CSRC / "tdt_enc_ws.hip"  # the encode kernels of one word size
 WORD_SIZES = (1, 2, 4, 8, 16)
+ANYWS_SRC = CSRC / "tdt_anyws.hip"  # encode and decode of every other word size up to 64
+SOURCES.append(ANYWS_SRC)
 # every source and header under csrc/ (tdt_api.hip includes the headers, directly or not)
 DEPS = SOURCES + [ENC_WS_SRC] + sorted(CSRC.glob("*.h")) + [ROOT / "include" / "psyne_tdt.h"]
 OBJ_DIR = PKG / "build"
@@ -33,12 +35,13 @@ def needs_build() -> bool:
 
 
 def build(force: bool = False, verbose: bool = False) -> pathlib.Path:
-    """Compile tdt_api.hip and one tdt_enc_ws.hip object per word size in parallel (the encode
-    kernels dominate the compile time), then link libpsyne_tdt.so."""
+    """Compile tdt_api.hip, tdt_anyws.hip and one tdt_enc_ws.hip object per word size in parallel
+    (the encode kernels dominate the compile time), then link libpsyne_tdt.so."""
     if force or needs_build():
         OBJ_DIR.mkdir(exist_ok=True)
         base = [HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-I", str(ROOT / "include")]
-        jobs = [(base + ["-c", str(SOURCES[0]), "-o", str(OBJ_DIR / "tdt_api.o")], OBJ_DIR / "tdt_api.o")]
+        jobs = [(base + ["-c", str(src), "-o", str(OBJ_DIR / (src.stem + ".o"))], OBJ_DIR / (src.stem + ".o"))
+                for src in SOURCES]
         for ws in WORD_SIZES:
             o = OBJ_DIR / f"tdt_enc_ws{ws}.o"
             jobs.append((base + [f"-DPSY_INST_WS={ws}", "-c", str(ENC_WS_SRC), "-o", str(o)], o))

@@ -1,0 +1,497 @@
+// tdt_anyws.hip — the generic-word-size encode and decode kernels (tdt_anyws.h) and their
+// launchers.  A translation unit of its own, compiled beside tdt_api.hip and the per-word-size
+// encode objects (psyne_amd/build.py).
+//
+// Reference lines restated here (include/psyne/protocol/tdt_compression.hpp):
+//   should_transform :186-201, compress_tdt :363-399 (size guard :364-367), extract_features
+//   :434-468, calculate_entropy :470-480, perform_clustering :507-525, separate_byte_streams
+//   :527-549, simple_rle_compress :557-582, serialize :81-117;
+//   deserialize :119-170, simple_rle_decompress :596-612, recombine_byte_streams :614-637.
+// (the headers' non-template kernels are defined once, in tdt_api.hip)
+#define PSY_ENC_INST_TU 1
+#define PSY_DEC_INST_TU 1
+#include "tdt_anyws.h"
+
+#include "tdt_decode.h"
+#include "tdt_encode.h"
+
+// The mapping decision is bit-exact only if nothing below is contracted (tdt_log2.h).
+#pragma clang fp contract(off)
+
+namespace psy {
+namespace {
+
+constexpr int kAW = kAnyTeam / 64;  // waves per workgroup
+
+// 16 message bytes at p (any alignment), bytes at index >= valid read as 0 and are not touched;
+// nothing below `lo` or at / past `lim` is read.
+__device__ __forceinline__ uint4 ld16_msg(const uint8_t *p, int valid, const uint8_t *lo, const uint8_t *lim) {
+    typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
+    const uintptr_t a = (uintptr_t)p;
+    if (valid >= 16) {
+        if ((a & 15) == 0) {
+            const u32x4_t v = gload<u32x4_t>(p);
+            return make_uint4(v.x, v.y, v.z, v.w);
+        }
+        const uintptr_t a0 = a & ~(uintptr_t)3;
+        if (a0 >= (uintptr_t)lo && a0 + 20 <= (uintptr_t)lim) {
+            const uint32_t *q = reinterpret_cast<const uint32_t *>(a0);
+            const uint32_t sh = (uint32_t)(a & 3);
+            const uint32_t w0 = gload<uint32_t>(q), w1 = gload<uint32_t>(q + 1), w2 = gload<uint32_t>(q + 2),
+                           w3 = gload<uint32_t>(q + 3);
+            if (sh == 0) return make_uint4(w0, w1, w2, w3);
+            const uint32_t w4 = gload<uint32_t>(q + 4);
+            return make_uint4(__builtin_amdgcn_alignbyte(w1, w0, sh), __builtin_amdgcn_alignbyte(w2, w1, sh),
+                              __builtin_amdgcn_alignbyte(w3, w2, sh), __builtin_amdgcn_alignbyte(w4, w3, sh));
+        }
+    }
+    return ld16_any(p, valid);
+}
+
+__device__ __forceinline__ uint32_t byte_of(const uint32_t (&w)[4], int i) { return (w[i >> 2] >> (8 * (i & 3))) & 0xffu; }
+
+// ---------------------------------------------------------------------------------------
+// Encode.  HP: histogram positions held in LDS (>= ws; 1 for MODE_MAPPED, which has none).
+template <int MODE, int HP>
+__global__ __launch_bounds__(kAnyTeam) void tdt_encode_any_kernel(EncodeArgs a, uint32_t ws) {
+    __shared__ uint32_t s_hist[HP * 256];
+    __shared__ double s_ent[kAnyWsMax];
+    __shared__ uint32_t s_map[kAnyWsMax];           // mapping[b] in {0, 1}
+    __shared__ uint32_t s_before[2][kAnyWsMax + 1]; // positions < p mapped to stream s
+    __shared__ __attribute__((aligned(16))) uint8_t s_buf[16 + kAnyChunk + 16];  // [15]: the byte before the chunk
+    __shared__ uint32_t s_slots[2][kAW];
+    __shared__ uint32_t s_bad;
+
+    const uint32_t tid = threadIdx.x, lane = (uint32_t)lane_id(), wv = tid >> 6;
+    const uint32_t msg = blockIdx.x;
+    if (msg >= a.n_msgs) return;
+    const uint64_t off0 = a.in_off[msg];
+    const uint64_t n = a.in_off[msg + 1] - off0;
+    const uint8_t *base = a.in + off0;
+    const uint8_t *lim = base + n;
+
+    bool compress;
+    if constexpr (MODE == MODE_ANALYZE) {
+        compress = n > 0 && n % ws == 0 && n < (1ull << 32);
+        if (!compress) {
+            if (tid == 0 && a.status) a.status[msg] = ST_ARG;
+            return;
+        }
+    } else {
+        // should_transform :186-201, then compress_tdt's size guard :364-367 (→ the UNCP fallback)
+        compress = a.policy_on && n >= a.min_tensor && (n % 4 == 0) && n >= 64 && (n % ws == 0) && n > 0 &&
+                   n < (1ull << 32);
+    }
+    uint64_t slot_b = 0, cap = 0;
+    if constexpr (MODE != MODE_ANALYZE) {
+        slot_b = a.slot_off[msg];
+        cap = a.slot_off[msg + 1] - slot_b;
+        if (!compress) {
+            const uint64_t E = n + 4;
+            const bool fits = E <= cap;
+            if (tid == 0) {
+                if (a.status) a.status[msg] = fits ? ST_OK : ST_CAPACITY;
+                if (a.out_len) a.out_len[msg] = fits ? E : 0;
+            }
+            if (fits) {
+                uint8_t *dst = a.out + slot_b;
+                if (tid < 4) dst[tid] = (uint8_t)(kMagicUNCP >> (8 * tid));
+                team_copy_g2g<kAnyTeam>(dst + 4, base, n);
+            }
+            return;
+        }
+    }
+    const uint32_t n32 = (uint32_t)n, wc = n32 / ws;
+
+    if constexpr (MODE == MODE_MAPPED) {
+        if (tid == 0) s_bad = 0u;
+        __syncthreads();
+        if (tid < ws) {
+            const int32_t m = a.mapping_in[(uint64_t)msg * ws + tid];
+            if (m < 0 || m > 1) s_bad = 1u;
+            s_map[tid] = (uint32_t)(m & 1);
+        }
+        __syncthreads();
+        if (s_bad) {  // invalid caller mapping: an empty output for this message
+            if (tid == 0) {
+                if (a.out_len) a.out_len[msg] = 0;
+                if (a.status) a.status[msg] = ST_BAD_MAPPING;
+            }
+            return;
+        }
+    } else {
+        // ---- histograms (extract_features :441-446, every word): byte j counts at position j mod ws
+        for (uint32_t i = tid; i < ws * 256u; i += kAnyTeam) s_hist[i] = 0u;
+        __syncthreads();
+        {
+            const uint32_t step = kAnyChunk % ws;
+            uint32_t p0 = (16u * tid) % ws;
+            for (uint64_t j0 = 16ull * tid; j0 < n; j0 += kAnyChunk) {
+                const int valid = n - j0 >= 16 ? 16 : (int)(n - j0);
+                const uint4 v = ld16_msg(base + j0, valid, base, lim);
+                const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+                uint32_t p = p0;
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    if (i < valid) atomicAdd(&s_hist[p * 256u + byte_of(w, i)], 1u);
+                    p = p + 1u == ws ? 0u : p + 1u;
+                }
+                p0 += step;
+                if (p0 >= ws) p0 -= ws;
+            }
+        }
+        __syncthreads();
+        // ---- entropies (calculate_entropy :470-480): the exact chain only.  A wave takes one
+        // position at a time: lane l computes (-prob, log2 prob) of bins l, l + 64, l + 128,
+        // l + 192 (0, 0 for an empty bin: fma(0, 0, e) == e for the non-negative running sum),
+        // then every lane runs the chain over the bins in order 0..255.
+        const double total = (double)wc;
+        for (uint32_t b = wv; b < ws; b += kAW) {
+            double np[4], L[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const uint32_t c = s_hist[b * 256u + 64u * k + lane];
+                if constexpr (MODE == MODE_ANALYZE) {
+                    if (a.hist_out) a.hist_out[((uint64_t)msg * ws + b) * 256 + 64u * k + lane] = c;
+                }
+                np[k] = 0.0;
+                L[k] = 0.0;
+                if (c) {
+                    const double prob = (double)c / total;
+                    L[k] = psy_log2_glibc(prob, c_log2_tab, c_log2_tab2);
+                    np[k] = -prob;
+                }
+            }
+            double e = 0.0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                for (int l = 0; l < 64; ++l) e = __builtin_fma(readlane_f64(np[k], l), readlane_f64(L[k], l), e);
+            if (lane == 0) s_ent[b] = e;
+        }
+        __syncthreads();
+        // ---- mapping (perform_clustering :507-525): entropy > in-order sum / ws
+        if (tid == 0) {
+            double sum = 0.0;
+            for (uint32_t b = 0; b < ws; ++b) sum += s_ent[b];
+            const double thr = sum / (double)ws;
+            for (uint32_t b = 0; b < ws; ++b) s_map[b] = s_ent[b] > thr ? 1u : 0u;
+        }
+        __syncthreads();
+        if constexpr (MODE == MODE_ANALYZE) {
+            if (tid < ws) {
+                if (a.ent_out) a.ent_out[(uint64_t)msg * ws + tid] = s_ent[tid];
+                if (a.map_out) a.map_out[(uint64_t)msg * ws + tid] = (int32_t)s_map[tid];
+            }
+            if (tid == 0 && a.status) a.status[msg] = ST_OK;
+            return;
+        }
+    }
+
+    if constexpr (MODE != MODE_ANALYZE) {
+        // ---- stream layout: s_before[s][p] = positions below p mapped to stream s
+        if (tid == 0) {
+            uint32_t k[2] = {0u, 0u};
+            for (uint32_t p = 0; p < ws; ++p) {
+                s_before[0][p] = k[0];
+                s_before[1][p] = k[1];
+                k[s_map[p]]++;
+            }
+            s_before[0][ws] = k[0];
+            s_before[1][ws] = k[1];
+            s_buf[15] = 0;
+        }
+        __syncthreads();
+        const uint32_t ns = s_before[1][ws] ? 2u : 1u;  // separate_byte_streams :527-549: max(mapping) + 1
+        uint8_t *dst = a.out + slot_b;
+        // every store is bounded by the slot: a blob that does not fit is reported, not written past it
+        auto put8 = [&](uint64_t o, uint32_t v) __attribute__((always_inline)) {
+            if (o < cap) dst[o] = (uint8_t)v;
+        };
+        auto put32 = [&](uint64_t o, uint32_t v) __attribute__((always_inline)) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) put8(o + i, v >> (8 * i));
+        };
+        // ---- header (serialize :81-117): magic, original size, streams, word size, mapping
+        if (tid == 0) {
+            put32(0, kMagicTDT);
+            put32(4, n32);
+            put32(8, ns);
+            put32(12, ws);
+            put32(16, ws);
+        }
+        if (tid < ws) put32(20 + 4ull * tid, s_map[tid]);
+        uint64_t o = 20 + 4ull * ws;  // the next stream's length word
+
+        for (uint32_t s = 0; s < ns; ++s) {
+            const uint32_t ks = s_before[s][ws];
+            const uint64_t dpos = o + 4;  // the stream's pairs
+            // carries across chunks (uniform): last run start + 1 (0: none yet), pairs emitted
+            uint32_t cstart = 0u, cpairs = 0u, lastb = 0u;
+            if (ks) {
+                for (uint64_t cb64 = 0; cb64 < n; cb64 += kAnyChunk) {  // (n < 2^32; cb + 4096 may not be)
+                    // this lane's 16 message bytes, their word and position
+                    const uint32_t cb = (uint32_t)cb64;
+                    const uint32_t j0 = cb + 16u * tid;
+                    const int valid = cb64 + 16u * tid >= n ? 0 : (n32 - j0 >= 16u ? 16 : (int)(n32 - j0));
+                    // the chunk's stream bytes [B, B + Lc): stream index of message byte j =
+                    // (j / ws)·ks + s_before[s][j % ws]
+                    const uint32_t ce = n32 - cb < kAnyChunk ? n32 : cb + kAnyChunk;
+                    const uint32_t wcb = cb / ws, pcb = cb - wcb * ws;
+                    const uint32_t wce = ce / ws, pce = ce - wce * ws;
+                    const uint32_t B = wcb * ks + s_before[s][pcb];
+                    const uint32_t Lc = wce * ks + s_before[s][pce] - B;
+                    if (valid) {
+                        const uint4 v = ld16_msg(base + j0, valid, base, lim);
+                        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+                        uint32_t wj = j0 / ws, p = j0 - wj * ws;
+                        uint32_t rel = wj * ks - B;  // + s_before[s][p]: index in the chunk's stream bytes
+#pragma unroll
+                        for (int i = 0; i < 16; ++i) {
+                            if (i < valid && s_map[p] == s) s_buf[16u + rel + s_before[s][p]] = (uint8_t)byte_of(w, i);
+                            if (++p == ws) {
+                                p = 0u;
+                                rel += ks;
+                            }
+                        }
+                    }
+                    __syncthreads();
+                    // ---- RLE (simple_rle_compress :557-582) of the chunk's stream bytes, 16 per
+                    // lane.  A stream byte that differs from the one before it starts a run; every
+                    // run start closes the run before it, which began at the last run start so far
+                    // (a max-scan over the lanes, carried across chunks) and emits ceil(L / 255)
+                    // pairs: 255, ..., 255, remainder.  An add-scan of the pair counts places them.
+                    const uint32_t q0 = 16u * tid;
+                    const uint32_t m = q0 >= Lc ? 0u : (Lc - q0 >= 16u ? 16u : Lc - q0);
+                    const uint4 xv = *reinterpret_cast<const uint4 *>(s_buf + 16u + q0);
+                    const uint32_t x[4] = {xv.x, xv.y, xv.z, xv.w};
+                    const uint32_t prev = s_buf[15u + q0];
+                    if (Lc) lastb = s_buf[15u + Lc];
+                    uint32_t sm = neq_prev_mask4(x[0], prev << 24) | (neq_prev_mask4(x[1], x[0]) << 4) |
+                                  (neq_prev_mask4(x[2], x[1]) << 8) | (neq_prev_mask4(x[3], x[2]) << 12);
+                    if (B + q0 == 0u) sm |= 1u;  // the stream's first byte
+                    sm &= (1u << m) - 1u;
+                    uint32_t vmax[1] = {sm ? B + q0 + (31u - (uint32_t)__builtin_clz(sm)) + 1u : 0u}, tmax[1];
+                    team_excl_scan<kAW, 1, OpMax>(vmax, tmax, s_slots[0]);
+                    const uint32_t cur = vmax[0] > cstart ? vmax[0] : cstart;  // run start + 1 entering this lane
+                    // only a lane's first run start can close a run longer than its 16 bytes
+                    uint32_t first_full = 0u, first_rem = 0u, np = 0u;
+                    if (sm) {
+                        const uint32_t qf = B + q0 + (uint32_t)__builtin_ctz(sm);
+                        np = (uint32_t)__builtin_popcount(sm);
+                        if (qf == 0u) {
+                            --np;  // nothing before the stream's first byte
+                        } else {
+                            const uint32_t Lr = qf - (cur - 1u);
+                            first_full = (Lr - 1u) / 255u;
+                            first_rem = Lr - 255u * first_full;
+                            np += first_full;
+                        }
+                    }
+                    uint32_t vadd[1] = {np}, tadd[1];
+                    team_excl_scan<kAW, 1, OpAdd>(vadd, tadd, s_slots[1]);
+                    if (sm) {
+                        uint64_t po = dpos + 2ull * (cpairs + vadd[0]);
+                        uint32_t rs = cur;  // start + 1 of the run being closed
+                        bool first = true;
+#pragma unroll
+                        for (int i = 0; i < 16; ++i) {
+                            if (!((sm >> i) & 1u)) continue;
+                            const uint32_t q = B + q0 + (uint32_t)i;
+                            const uint32_t val = i ? byte_of(x, i - 1) : prev;
+                            if (q != 0u) {
+                                uint32_t cnt = q - (rs - 1u);
+                                if (first) {
+                                    for (uint32_t f = 0; f < first_full; ++f) {
+                                        put8(po, 255u);
+                                        put8(po + 1, val);
+                                        po += 2;
+                                    }
+                                    cnt = first_rem;
+                                }
+                                put8(po, cnt);
+                                put8(po + 1, val);
+                                po += 2;
+                            }
+                            first = false;
+                            rs = q + 1u;
+                        }
+                    }
+                    cstart = tmax[0] > cstart ? tmax[0] : cstart;
+                    cpairs += tadd[0];
+                    if (tid == 0 && Lc) s_buf[15] = (uint8_t)lastb;  // (only lane 0 reads it)
+                }
+                // the last run closes at the end of the stream
+                const uint32_t S = wc * ks;
+                const uint32_t Lr = S - (cstart - 1u);
+                const uint32_t full = (Lr - 1u) / 255u;
+                if (tid == 0) {
+                    uint64_t po = dpos + 2ull * cpairs;
+                    for (uint32_t f = 0; f < full; ++f) {
+                        put8(po, 255u);
+                        put8(po + 1, lastb);
+                        po += 2;
+                    }
+                    put8(po, Lr - 255u * full);
+                    put8(po + 1, lastb);
+                    s_buf[15] = 0;
+                }
+                cpairs += full + 1u;
+                __syncthreads();  // the next stream's chunks reuse s_buf
+            }
+            if (tid == 0) put32(o, 2u * cpairs);
+            o = dpos + 2ull * cpairs;
+        }
+        const bool fits = o <= cap;
+        if (tid == 0) {
+            if (a.status) a.status[msg] = fits ? ST_OK : ST_CAPACITY;
+            if (a.out_len) a.out_len[msg] = fits ? o : 0;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------
+// Decode of the deferred blobs.  blob_check (tdt_decode.h) has passed each of them: header,
+// mapping (>= ws entries, each < num_streams) and stream table lie inside the blob, 1 <= ws <= 64
+// and at least one whole word.  Every output byte is written exactly once: by the pair that
+// covers it, or as zero (a stream shorter than its share of the words, the bytes past the
+// last whole word: recombine_byte_streams :614-637 over its zero-initialised result).
+__global__ __launch_bounds__(kAnyTeam) void tdt_decode_any_kernel(DecodeArgs a) {
+    __shared__ uint32_t s_map[kAnyWsMax], s_soff[kAnyWsMax], s_slen[kAnyWsMax], s_ptab[kAnyWsMax];
+    __shared__ uint32_t s_slots[2][kAW];
+    const uint32_t tid = threadIdx.x, lane = (uint32_t)lane_id();
+    const uint32_t listed = __builtin_amdgcn_readfirstlane(*a.dcount);
+    const uint32_t cnt = listed < a.n_msgs ? listed : a.n_msgs;
+    for (uint32_t it = blockIdx.x; it < cnt; it += gridDim.x) {
+        if (it != blockIdx.x) __syncthreads();
+        const uint32_t msg = a.dlist[it];
+        const uint64_t boff = a.in_off[msg];
+        const uint64_t len = a.in_len ? a.in_len[msg] : a.in_off[msg + 1] - boff;
+        const uint8_t *blob = a.in + boff;
+        const uint8_t *blim = blob + len;
+        const uint32_t orig = ld_u32_bytes(blob + 4), ns = ld_u32_bytes(blob + 8), ws = ld_u32_bytes(blob + 12),
+                       msize = ld_u32_bytes(blob + 16);
+        uint64_t ob;
+        bool fits;
+        if (a.slot_off) {
+            ob = a.slot_off[msg];
+            fits = orig <= a.slot_off[msg + 1] - ob;
+        } else {
+            ob = a.out_off[msg];  // (the look-back kernel placed it)
+            fits = ob + orig <= a.out_cap;
+        }
+        if (tid == 0) {
+            if (a.status) a.status[msg] = fits ? ST_OK : ST_CAPACITY;
+            if (a.slot_off && a.out_len) a.out_len[msg] = fits ? orig : 0;
+        }
+        if (!fits || ws == 0u || ws > (uint32_t)kAnyWsMax) continue;  // (the width: blob_check's, restated)
+        uint8_t *dst = a.out + ob;
+        // mapping and stream table: lane b of wave 0 keeps position b's stream
+        if (tid < 64) {
+            const uint32_t mp = lane < ws ? ld_u32_bytes(blob + 20 + 4 * lane) : 0xffffffffu;
+            uint64_t off = 20 + 4ull * msize;
+            uint32_t my_off = 0, my_len = 0;
+            for (uint32_t s = 0; s < ns; ++s) {  // uniform
+                const uint32_t sl = ld_u32_bytes(blob + off);
+                off += 4;
+                if (mp == s) {
+                    my_off = (uint32_t)off;
+                    my_len = sl;
+                }
+                off += sl;
+            }
+            if (lane < ws) {
+                s_map[lane] = mp;
+                s_soff[lane] = my_off;
+                s_slen[lane] = my_len;
+            }
+        }
+        __syncthreads();
+        const uint32_t wc = orig / ws, wbytes = wc * ws;
+        for (uint32_t k = wbytes + tid; k < orig; k += kAnyTeam) dst[k] = 0;
+        uint32_t alt = 0u;
+        for (uint32_t b0 = 0; b0 < ws; ++b0) {  // every referenced stream once, at its first position
+            const uint32_t s = s_map[b0];
+            bool seen = false;
+            for (uint32_t bb = 0; bb < b0; ++bb) seen = seen || s_map[bb] == s;
+            if (seen) continue;  // uniform
+            // the stream's positions in word order: byte q of the decoded stream is byte
+            // s_ptab[q % k] of word q / k
+            uint32_t k = 0u, rank = 0u;
+            for (uint32_t bb = 0; bb < ws; ++bb) {
+                const bool same = s_map[bb] == s;
+                k += same ? 1u : 0u;
+                rank += same && bb < tid ? 1u : 0u;
+            }
+            if (tid < ws && s_map[tid] == s) s_ptab[rank] = tid;
+            __syncthreads();
+            const uint32_t soff = s_soff[b0], np = s_slen[b0] / 2u;  // (an odd trailing byte is ignored :600)
+            const uint32_t S = wc * k;                                 // the stream's share of the output
+            uint64_t sbase = 0;                                        // decoded bytes before this chunk
+            for (uint32_t pc = 0; pc < np && sbase < S; pc += kAnyDecPairs) {
+                const uint32_t p0 = pc + 8u * tid;
+                const uint32_t nv = p0 < np ? (np - p0 < 8u ? np - p0 : 8u) : 0u;
+                const uint4 pv = nv ? ld16_span(blob + soff + 2ull * p0, (int)(2 * nv), blim) : make_uint4(0, 0, 0, 0);
+                const uint32_t pw[4] = {pv.x, pv.y, pv.z, pv.w};
+                const uint32_t s2 = (pw[0] & 0x00ff00ffu) + (pw[1] & 0x00ff00ffu) + (pw[2] & 0x00ff00ffu) +
+                                    (pw[3] & 0x00ff00ffu);
+                uint32_t v[1] = {(s2 & 0xffffu) + (s2 >> 16)}, tot[1];
+                const uint32_t mine = v[0];
+                team_excl_scan<kAW, 1, OpAdd>(v, tot, s_slots[alt]);
+                alt ^= 1u;
+                uint64_t q64 = sbase + v[0];
+                if (mine && q64 < S) {
+                    uint32_t q = (uint32_t)q64;
+                    uint32_t w = q / k, t = q - w * k;
+                    uint8_t *row = dst + (uint64_t)w * ws;
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) {
+                        const uint32_t pr = pw[i >> 1] >> (16 * (i & 1));
+                        const uint32_t c = pr & 0xffu;  // (count 0 emits nothing :602)
+                        const uint8_t val = (uint8_t)(pr >> 8);
+                        for (uint32_t r = 0; r < c && q < S; ++r, ++q) {
+                            row[s_ptab[t]] = val;
+                            if (++t == k) {
+                                t = 0u;
+                                row += ws;
+                            }
+                        }
+                    }
+                }
+                sbase += tot[0];
+            }
+            // a stream shorter than its share leaves zeros (recombine :626-631)
+            for (uint64_t q = sbase + tid; q < S; q += kAnyTeam) {
+                const uint32_t w = (uint32_t)q / k, t = (uint32_t)q - w * k;
+                dst[(uint64_t)w * ws + s_ptab[t]] = 0;
+            }
+            __syncthreads();  // s_ptab is rebuilt for the next stream
+        }
+    }
+}
+
+}  // namespace
+
+int launch_encode_any(const EncodeArgs &a, int ws, int mode, hipStream_t s) {
+    if (a.n_msgs == 0) return 0;
+    const dim3 g(a.n_msgs), t(kAnyTeam);
+    const uint32_t w = (uint32_t)ws;
+#define PSY_ANY_HP(MODE_)                                                                              \
+    do {                                                                                               \
+        if (ws <= 8) hipLaunchKernelGGL((tdt_encode_any_kernel<MODE_, 8>), g, t, 0, s, a, w);          \
+        else if (ws <= 16) hipLaunchKernelGGL((tdt_encode_any_kernel<MODE_, 16>), g, t, 0, s, a, w);   \
+        else if (ws <= 32) hipLaunchKernelGGL((tdt_encode_any_kernel<MODE_, 32>), g, t, 0, s, a, w);   \
+        else hipLaunchKernelGGL((tdt_encode_any_kernel<MODE_, 64>), g, t, 0, s, a, w);                 \
+    } while (0)
+    if (mode == MODE_ENCODE) PSY_ANY_HP(MODE_ENCODE);
+    else if (mode == MODE_ANALYZE) PSY_ANY_HP(MODE_ANALYZE);
+    else hipLaunchKernelGGL((tdt_encode_any_kernel<MODE_MAPPED, 1>), g, t, 0, s, a, w);
+#undef PSY_ANY_HP
+    return (int)hipGetLastError();
+}
+
+int launch_decode_any(const DecodeArgs &a, uint32_t grid, hipStream_t s) {
+    hipLaunchKernelGGL(tdt_decode_any_kernel, dim3(grid ? grid : 1u), dim3(kAnyTeam), 0, s, a);
+    return (int)hipGetLastError();
+}
+
+}  // namespace psy

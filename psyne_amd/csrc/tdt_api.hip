@@ -19,6 +19,7 @@
 #include <string>
 #include <vector>
 
+#include "tdt_anyws.h"
 #include "tdt_copypool.h"
 #include "tdt_decode.h"
 #include "tdt_encode.h"
@@ -37,6 +38,14 @@ PSY_ENC_EXT_WS(2)
 PSY_ENC_EXT_WS(4)
 PSY_ENC_EXT_WS(8)
 PSY_ENC_EXT_WS(16)
+#endif
+
+// The generic-word-size kernels live in tdt_anyws.hip; the diagnostic single-file builds leave
+// them out (word sizes other than 1, 2, 4, 8, 16 are then unsupported, as blobs carrying one).
+#if !defined(PSY_FAST_BUILD) && !(defined(PSY_PROF) && PSY_PROF) && !defined(PSY_SINGLE_TU)
+#define PSY_HAVE_ANYWS 1
+#else
+#define PSY_HAVE_ANYWS 0
 #endif
 
 namespace {
@@ -232,8 +241,10 @@ namespace {
 
 constexpr size_t kCounterBytes = 64;
 
+// workspace: counters | one look-back word per message (+ 1) | the deferred-blob list of the
+// compacted decode (one u32 per message, tdt_anyws.h)
 int ensure_ws(tdt_ctx *c, uint32_t n_msgs, hipStream_t s) {
-    const size_t need = kCounterBytes + 8ull * (n_msgs + 1);
+    const size_t need = kCounterBytes + 8ull * (n_msgs + 1) + 4ull * n_msgs;
     if (need > c->ws_bytes) {
         if (int st = no_growth_in_capture(s)) return st;
         if (c->ws) c->retired.push_back(c->ws);  // (a graph captured earlier may use it)
@@ -245,7 +256,32 @@ int ensure_ws(tdt_ctx *c, uint32_t n_msgs, hipStream_t s) {
     return TDT_OK;
 }
 
-bool ws_supported(int ws) { return ws == 1 || ws == 2 || ws == 4 || ws == 8 || ws == 16; }
+bool ws_supported(int ws) { return psy::anyws_tuned(ws) || (PSY_HAVE_ANYWS && psy::anyws_generic(ws)); }
+
+// the generic encode kernel (any word size in 1..64 the tuned kernels do not cover)
+int launch_any_encode(const psy::EncodeArgs &a, int ws, int mode, hipStream_t s) {
+#if PSY_HAVE_ANYWS
+    if (psy::anyws_generic(ws)) {
+        const int e = psy::launch_encode_any(a, ws, mode, s);
+        if (e) return set_err(TDT_E_HIP, std::string("generic encode launch: ") + hipGetErrorString((hipError_t)e));
+        return TDT_OK;
+    }
+#endif
+    (void)a, (void)mode, (void)s, (void)ws;
+    return set_err(TDT_E_UNSUPPORTED, "word_size not supported on the GPU path");
+}
+// the follow-up launch of a decode call: the blobs of a generic word size its kernels deferred
+// (grid: workgroups striding over the device-side list; any grid decodes every listed blob)
+int launch_any_decode(const psy::DecodeArgs &a, uint32_t grid, hipStream_t s) {
+#if PSY_HAVE_ANYWS
+    if (!a.dlist) return TDT_OK;
+    const int e = psy::launch_decode_any(a, std::max(1u, std::min(a.n_msgs, grid)), s);
+    if (e) return set_err(TDT_E_HIP, std::string("generic decode launch: ") + hipGetErrorString((hipError_t)e));
+#else
+    (void)a, (void)grid, (void)s;
+#endif
+    return TDT_OK;
+}
 
 bool policy_on(const tdt_ctx *c) {
     // should_transform :192-200 (the size / tensor-shape terms are evaluated per message on
@@ -677,8 +713,10 @@ int launch_slotted_any(tdt_ctx *c, PlanWS &pw, psy::EncodeArgs a, hipStream_t s)
         case 8: return launch_slotted<8>(c, pw, a, s);
         case 16: return launch_slotted<16>(c, pw, a, s);
 #endif
+        default: break;
     }
-    return set_err(TDT_E_UNSUPPORTED, "word_size not supported on the GPU path");
+    // generic widths: one workgroup per message, message id = block index, no plan
+    return launch_any_encode(a, c->cfg.word_size, psy::MODE_ENCODE, s);
 }
 
 // messages > 4 KiB: TEAM threads per message, G resident rounds per wave (64 KiB resident)
@@ -725,8 +763,13 @@ int launch_encode(tdt_ctx *c, psy::EncodeArgs a, hipStream_t s, int small_teams)
         case 8: return launch_encode_ws<8, MODE, LB>(a, small, res, s);
         case 16: return launch_encode_ws<16, MODE, LB>(a, small, res, s);
 #endif
+        default: break;
     }
-    return set_err(TDT_E_UNSUPPORTED, "word_size not supported on the GPU path");
+    // generic widths: analysis, or a blob into its slot (the compacted entry points take the
+    // two-phase route, encode_two_phase_any)
+    if (MODE != psy::MODE_ANALYZE && !a.slot_off && psy::anyws_generic(c->cfg.word_size))
+        return set_err(TDT_E_UNSUPPORTED, "compacted one-pass encode needs word_size 1, 2, 4, 8 or 16");
+    return launch_any_encode(a, c->cfg.word_size, MODE, s);
 }
 
 // Zero the counters + look-back words of a batch; `wsp` = an explicit workspace (host
@@ -849,6 +892,11 @@ int launch_decode_slotted(tdt_ctx *c, PlanWS &pw, psy::DecodeArgs a, hipStream_t
     auto *cnt32 = reinterpret_cast<uint32_t *>(pw.buf);
     auto *list = reinterpret_cast<uint32_t *>(pw.buf + 256);
     uint32_t *slist = list + n, *blist = slist + n, *clist = blist + n;
+#if PSY_HAVE_ANYWS
+    // the deferred-blob list (generic word sizes): the plan buffer's fifth list and last counter
+    a.dlist = clist + n;
+    a.dcount = cnt32 + 30;
+#endif
     const uint32_t lcap = large_on ? pw.d_lcap : 0u, bcap = large_on ? pw.d_bcap : 0u,
                    tcap = large_on ? pw.d_tcap : 0u;
     auto *dmeta = reinterpret_cast<psy::DMeta *>(pw.dlarge);
@@ -929,8 +977,11 @@ int launch_decode_slotted(tdt_ctx *c, PlanWS &pw, psy::DecodeArgs a, hipStream_t
         lists(guess(H, 8, n, n), forked && !c->small_main ? pw.side : s, psy::tdt_decode_kernel<0, 1, 0>,
               psy::tdt_decode_kernel<0, 1, 1>);
     }
-    if (forked) return join_side(pw, s);
-    return TDT_OK;
+    if (forked && (st = join_side(pw, s))) return st;
+    // the deferred blobs (generic word sizes): near-empty when no kernel above listed one.  (A
+    // fixed grid: the plan's count snapshot is taken before the class kernels append to the list,
+    // so the history cannot size it — 64 workgroups for 4,096 listed blobs ran at a twelfth of the rate.)
+    return launch_any_decode(a, (uint32_t)c->cus * 4u, s);
 }
 
 int decode_common(tdt_ctx *c, bool sizes_only, const uint8_t *d_in, const uint64_t *d_in_off, uint32_t n_msgs,
@@ -969,9 +1020,15 @@ int decode_common(tdt_ctx *c, bool sizes_only, const uint8_t *d_in, const uint64
         st = launch_decode_slotted(c, pws ? *pws : c->pw, a, s);
         if (st) return st;
     } else {
+#if PSY_HAVE_ANYWS
+        a.dlist = reinterpret_cast<uint32_t *>(wsp + kCounterBytes + 8ull * (n_msgs + 1));
+        a.dcount = reinterpret_cast<uint32_t *>(wsp) + 2;  // (zeroed with the counters by prep)
+#endif
         launch_list(n_msgs, 64, [&](uint32_t, uint32_t g) {  // ids from the ticket
             hipLaunchKernelGGL((psy::tdt_decode_kernel<1>), dim3(g), dim3(64), 0, s, a);
         });
+        st = launch_any_decode(a, (uint32_t)c->cus * 4u, s);
+        if (st) return st;
     }
     HIPCHK(hipGetLastError());
     return TDT_OK;
@@ -1610,9 +1667,16 @@ int host_one(tdt_ctx *c, bool encode, const uint8_t *h_in, const uint64_t *h_in_
     const uint8_t *src = h_in + h_in_off[0];
     uint64_t osize;
     if (encode) {
-        if (len > kOneMax) return -1;
+        if (len > kOneMax || !psy::anyws_tuned(c->cfg.word_size)) return -1;  // (generic widths: the pipeline)
         osize = tdt_encode_bound(len, c->cfg.word_size);
     } else {
+        // a TDT blob of a generic word size is decoded by the pipeline's follow-up launch
+        if (len >= 16) {
+            uint32_t magic, bws;
+            std::memcpy(&magic, src, 4);
+            std::memcpy(&bws, src + 12, 4);
+            if (magic == psy::kMagicTDT && !psy::anyws_tuned((int)bws)) return -1;
+        }
         osize = host_decoded_size(src, len);
         if (osize > kOneMax || len > 2 * kOneMax + 1024) return -1;
         if (osize > out_cap) return set_err(TDT_E_CAPACITY, "host output capacity exceeded");
@@ -1661,7 +1725,7 @@ int host_one(tdt_ctx *c, bool encode, const uint8_t *h_in, const uint64_t *h_in_
             case 8: launch_one_encode<8>(a, len, s); break;
             case 16: launch_one_encode<16>(a, len, s); break;
 #endif
-            default: return set_err(TDT_E_UNSUPPORTED, "word_size not supported on the GPU path");
+            default: return -1;  // (generic widths took the pipeline above)
         }
     } else {
         psy::DecodeArgs a{};
@@ -1859,7 +1923,7 @@ int tdt_ctx_create(int device, const tdt_config *cfg, tdt_ctx **out) {
     if (cfg) c = *cfg;
     else tdt_default_config(&c);
     if (c.word_size <= 0) return set_err(TDT_E_CONFIG, "word_size must be positive");
-    if (!ws_supported(c.word_size)) return set_err(TDT_E_UNSUPPORTED, "GPU encoder supports word_size 1,2,4,8,16");
+    if (!ws_supported(c.word_size)) return set_err(TDT_E_UNSUPPORTED, "GPU codec supports word_size 1..64");
     int ndev = 0;
     HIPCHK(hipGetDeviceCount(&ndev));
     if (device < 0 || device >= ndev) return set_err(TDT_E_ARG, "bad device");
@@ -1989,8 +2053,63 @@ uint64_t tdt_encode_bound(uint64_t n, int32_t word_size) {
 // successors waiting in the look-back would stall every CU (head-of-line blocking); batches of
 // small messages: the per-message ticket / look-back chain bounds the rate.  Both are encoded
 // slotted (the message-class kernels), then the lengths are scanned and the blobs gathered.
+// Compacted encode at a generic word size (tdt_anyws.h): always the two phases — slots, the
+// generic kernel into cp_buf, a scan of the lengths, the gather.  The scan's input needs the
+// batch's byte count on the host, so not under stream capture (nor with the no-two-phase knob).
+static int encode_two_phase_any(tdt_ctx *ctx, int mode, const uint8_t *d_in, const uint64_t *d_in_off, uint32_t n_msgs,
+                                const int32_t *d_mapping, uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_off,
+                                int32_t *d_status, void *stream) {
+    if (!d_in_off || !d_out || !d_out_off) return set_err(TDT_E_ARG, "null argument");
+    if (mode == psy::MODE_MAPPED && !d_mapping) return set_err(TDT_E_ARG, "null mapping");
+    if (!two_phase_ok(ctx, stream))
+        return set_err(TDT_E_UNSUPPORTED, "compacted encode at a word size other than 1, 2, 4, 8, 16 reads the batch "
+                                          "size back: not under stream capture or TDT_OPT_NO_TWO_PHASE (use the "
+                                          "slotted entry points there)");
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(hipSetDevice(ctx->device));
+    uint64_t h2[2];
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        const size_t need = 2ull * n_msgs + 2;
+        if (need > ctx->cp_idx_n) {
+            if (ctx->cp_idx) HIPCHK(hipFree(ctx->cp_idx));
+            ctx->cp_idx = nullptr;
+            HIPCHK(hipMalloc(&ctx->cp_idx, 8 * need));
+            ctx->cp_idx_n = need;
+        }
+        HIPCHK(hipMemcpyAsync(&h2[0], d_in_off, 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(&h2[1], d_in_off + n_msgs, 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        // Σ encode bounds = 2·(input bytes) + n·(28 + 4·ws)
+        const uint64_t bound = 2 * (h2[1] - h2[0]) + (uint64_t)n_msgs * (28 + 4ull * (uint64_t)ctx->cfg.word_size + 4);
+        if (bound > ctx->cp_bytes) {
+            if (ctx->cp_buf) HIPCHK(hipFree(ctx->cp_buf));
+            ctx->cp_buf = nullptr;
+            HIPCHK(hipMalloc(&ctx->cp_buf, bound));
+            ctx->cp_bytes = bound;
+        }
+    }
+    uint64_t *slot = ctx->cp_idx, *len = ctx->cp_idx + n_msgs + 1;
+    int st = tdt_encode_slots(ctx, d_in_off, n_msgs, slot, stream);
+    if (st) return st;
+    st = encode_common(ctx, mode, d_in, d_in_off, n_msgs, d_mapping, ctx->cp_buf, 0, nullptr, d_status, nullptr, nullptr,
+                       nullptr, stream, slot, len);
+    if (st) return st;
+    hipLaunchKernelGGL(cp_len_kernel, dim3((n_msgs + 255) / 256), dim3(256), 0, s, len, d_out_off, n_msgs);
+    HIPCHK(hipGetLastError());
+    st = scan_sizes(ctx, d_out_off, n_msgs, s);  // exclusive, total at [n]
+    if (st) return st;
+    hipLaunchKernelGGL(cp_gather_kernel, dim3((n_msgs + 3) / 4), dim3(256), 0, s, ctx->cp_buf, slot, len, d_out,
+                       d_out_off, out_cap, d_status, n_msgs);
+    HIPCHK(hipGetLastError());
+    return TDT_OK;
+}
+
 int tdt_encode_batch(tdt_ctx *ctx, const uint8_t *d_in, const uint64_t *d_in_off, uint32_t n_msgs, uint8_t *d_out,
                      uint64_t out_cap, uint64_t *d_out_off, int32_t *d_status, void *stream) {
+    if (ctx && n_msgs && psy::anyws_generic(ctx->cfg.word_size))
+        return encode_two_phase_any(ctx, psy::MODE_ENCODE, d_in, d_in_off, n_msgs, nullptr, d_out, out_cap, d_out_off,
+                                    d_status, stream);
     if (!ctx || n_msgs == 0 || !d_in_off || !d_out || !d_out_off || !two_phase_ok(ctx, stream))
         return encode_common(ctx, psy::MODE_ENCODE, d_in, d_in_off, n_msgs, nullptr, d_out, out_cap, d_out_off,
                              d_status, nullptr, nullptr, nullptr, stream);
@@ -2052,6 +2171,9 @@ int tdt_encode_batch(tdt_ctx *ctx, const uint8_t *d_in, const uint64_t *d_in_off
 int tdt_encode_with_mapping_batch(tdt_ctx *ctx, const uint8_t *d_in, const uint64_t *d_in_off, uint32_t n_msgs,
                                   const int32_t *d_mapping, uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_off,
                                   int32_t *d_status, void *stream) {
+    if (ctx && n_msgs && psy::anyws_generic(ctx->cfg.word_size))
+        return encode_two_phase_any(ctx, psy::MODE_MAPPED, d_in, d_in_off, n_msgs, d_mapping, d_out, out_cap, d_out_off,
+                                    d_status, stream);
     return encode_common(ctx, psy::MODE_MAPPED, d_in, d_in_off, n_msgs, d_mapping, d_out, out_cap, d_out_off,
                          d_status, nullptr, nullptr, nullptr, stream);
 }
@@ -2263,7 +2385,7 @@ const char *tdt_status_string(int status) {
         case TDT_E_TRUNCATED: return "TDT: truncated blob";
         case TDT_E_BAD_MAPPING: return "TDT: invalid cluster mapping";
         case TDT_E_CAPACITY: return "TDT: output capacity exceeded";
-        case TDT_E_UNSUPPORTED: return "TDT: word size not supported on the GPU path";
+        case TDT_E_UNSUPPORTED: return "TDT: word size not supported on the GPU path";  // (> 64)
         case TDT_E_BAD_HEADER: return "TDT: word size 0";
         case TDT_E_CONFIG: return "TDT: invalid configuration";
         case TDT_E_HIP: return "TDT: HIP runtime error";

@@ -62,7 +62,15 @@ struct DecodeArgs {
     uint32_t *bsum;        // per 512-pair block: count sum, then (scan) start position
     const uint32_t *tent;  // tile entries (large-blob index)
     uint32_t *tblk;        // per tile and referenced stream: the block holding its position - 1
+    // blobs of a generic word size (tdt_anyws.h): the kernels here place them and append their
+    // ids to dlist (length *dcount, one atomic each); a follow-up launch decodes the listed blobs
+    uint32_t *dlist;
+    uint32_t *dcount;
 };
+
+// blob_check's internal status of a valid blob whose word size (<= 64, not 1/2/4/8/16) the
+// kernels of this file do not decode: deferred to tdt_anyws.hip.  Never reported to the caller.
+constexpr uint32_t ST_DEFER = 0x100;
 
 constexpr int kMaxRef = 16;  // referenced streams <= word_size <= 16
 constexpr uint32_t kDecTileGroups = 2048;  // large blobs: 32 KiB of output per tile
@@ -146,7 +154,9 @@ __device__ __forceinline__ uint4 ld16_span(const uint8_t *p, int valid, const ui
 // checks there) and recombine_byte_streams :614-637's preconditions (word_size > 0, every
 // mapping entry < num_streams whenever a word exists).  rd32(off) reads the u32 at blob
 // offset off (only called for offsets proven inside the blob).  osize = the decoded size
-// (original_size, or len - 4 for UNCP), 0 on error.
+// (original_size, or len - 4 for UNCP), 0 on error.  A blob that passes every check but has a
+// word size the kernels here do not take returns, last, ST_DEFER (word size <= 64: osize =
+// original_size, the generic kernel decodes it) or ST_UNSUPPORTED (word size > 64).
 // (Written as one status chain without early returns: the hipcc 7.2 structurizer dropped the
 // success value of osize when the checks returned from inside the loops.)
 template <class RD>
@@ -189,14 +199,15 @@ __device__ __forceinline__ uint32_t blob_check(RD &&rd32, uint64_t len, uint32_t
                     const int32_t m = (int32_t)rd32(20 + 4 * b);
                     if (m < 0 || (uint32_t)m >= ns) st = ST_BAD_MAPPING;
                 }
-                if (st == ST_OK && (ws > 16 || (16 % ws) != 0)) st = ST_UNSUPPORTED;
+                if (st == ST_OK && (ws > 16 || (16 % ws) != 0)) st = ws <= 64 ? ST_DEFER : ST_UNSUPPORTED;
             }
         }
     }
-    osize = st != ST_OK ? 0ull : uncp ? len - 4 : (uint64_t)orig;
+    osize = (st != ST_OK && st != ST_DEFER) ? 0ull : uncp ? len - 4 : (uint64_t)orig;
     return st;
 }
 
+#ifndef PSY_DEC_INST_TU  // (the non-template kernels are defined once, in tdt_api.hip)
 // Decoded sizes (and statuses) only: one lane per blob, no LDS — the header words sit in the
 // first cache lines of each blob.
 __global__ __launch_bounds__(256) void tdt_decode_sizes_kernel(DecodeArgs a) {
@@ -236,8 +247,9 @@ __global__ __launch_bounds__(256) void tdt_decode_sizes_kernel(DecodeArgs a) {
     uint64_t osize;
     const uint32_t st = blob_check(rd32, len, uncp, osize);
     a.sizes_out[msg] = osize;
-    if (a.status) a.status[msg] = (int32_t)st;
+    if (a.status) a.status[msg] = (int32_t)(st == ST_DEFER ? (uint32_t)ST_OK : st);  // (a generic width decodes)
 }
+#endif  // PSY_DEC_INST_TU
 
 // ---------------------------------------------------------------------------------------
 // Fast path: at most two referenced streams whose per-group segments seg_r = WPG·k_r are
@@ -1126,6 +1138,23 @@ __device__ __forceinline__ void decode_one(const DecodeArgs &a, uint8_t *smem, u
         ob = slot_b;
         fits = osize <= slot_e - ob;
     }
+    if (st == ST_DEFER) {
+        // a generic word size: placed here (the look-back has published its size), decoded —
+        // status, length and bytes — by the follow-up launch over dlist (tdt_anyws.hip)
+        if (lane == 0) {
+            if constexpr (LB) {
+                a.out_off[msg] = ob;
+                if (msg == a.n_msgs - 1) a.out_off[a.n_msgs] = ob + osize;
+            }
+            if (a.dlist) {
+                a.dlist[atomicAdd(a.dcount, 1u)] = msg;
+            } else {  // (a launch without the follow-up: the one-message host call, which the host keeps such blobs from)
+                if (!LB && a.out_len) a.out_len[msg] = 0;
+                if (a.status) a.status[msg] = ST_UNSUPPORTED;
+            }
+        }
+        return;
+    }
     if (st == ST_OK && !fits) st = ST_CAPACITY;
     if (lane == 0) {
         if constexpr (LB) {
@@ -1405,6 +1434,7 @@ struct DPlanArgs {
     uint32_t copy_on;   // 0: UNCP blobs join the one-wave lists
 };
 
+#ifndef PSY_DEC_INST_TU
 __global__ __launch_bounds__(1024) void tdt_decode_plan_kernel(DPlanArgs p) {
     __shared__ uint64_t lds[6 * (4 * 16 + 1)];
     // one wave per blob keeps the chip busy while a blob is at most ~1/4096 of the batch's
@@ -1632,6 +1662,7 @@ __global__ __launch_bounds__(64) void tdt_decode_lscan_kernel(DecodeArgs a) {
     if (lane == 0) m->slen[r] = (uint32_t)run;
     }
 }
+#endif  // PSY_DEC_INST_TU
 
 // Tile pass: one wave per 32 KiB output tile (main launch: tiles [list_base, list_base + grid);
 // overflow launch, PS = 1: the tiles past it, grid-stride).

@@ -38,7 +38,8 @@ class TDTConfig:
     """TDTConfig (tdt_compression.hpp:31-43).  auto_detect_clusters / max_clusters /
     enable_simd are declared by the reference but never read; kept for API parity.
     sample_fraction is accepted, but the GPU always analyses every word (the reference's
-    sample_fraction = 1.0 behaviour, which is the only deterministic one)."""
+    sample_fraction = 1.0 behaviour, which is the only deterministic one).  word_size: any record
+    stride in 1..64 (1, 2, 4, 8, 16 on the tuned kernels, the others on the generic ones)."""
     sample_fraction: float = 0.3
     word_size: int = 4
     auto_detect_clusters: bool = True
