@@ -17,12 +17,14 @@
 #include <mutex>
 #include <sched.h>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "tdt_anyws.h"
 #include "tdt_copypool.h"
 #include "tdt_decode.h"
 #include "tdt_encode.h"
+#include "tdt_plan.h"
 #include "tdt_slots.h"
 
 // The encode kernels live in tdt_enc_ws.hip (one translation unit per word size); diagnostic
@@ -81,13 +83,15 @@ int no_growth_in_capture(hipStream_t s) {
 
 // Counts of an earlier plan (the slotted calls size their main grids from them; no call ever
 // waits for them).  Each call's plan counters are copied into pinned memory behind the plan
-// kernel; a later call takes them once that copy has completed.
+// kernel; a later call takes them once that copy has completed.  K: the direction's counter names.
+template <class K>
 struct CountHist {
-    uint32_t *pin = nullptr;  // pinned: the plan's 8 u64 counters
+    uint32_t *pin = nullptr;  // pinned: the snapshotted part of the plan's counter block
     hipEvent_t ev = nullptr;
     bool pending = false, valid = false;
-    uint32_t v[32] = {};
+    uint32_t v[psy::kPlanSnapBytes / 4] = {};
     uint32_t n = 0, n_pending = 0;  // messages in the snapshot's batch
+    uint32_t operator[](K k) const { return v[psy::lo32(k)]; }
     // fold the newest completed snapshot in (never waits)
     void refresh() {
         if (pending && hipEventQuery(ev) == hipSuccess) {
@@ -117,7 +121,8 @@ struct PlanWS {
     uint32_t e_lcap = 0, e_tcap = 0;
     uint8_t *dlarge = nullptr;  // decode: DMeta | block entries | block sums | tile entries | tile blocks
     uint32_t d_lcap = 0, d_bcap = 0, d_tcap = 0;
-    CountHist eh, dh;  // encode / decode plan counts
+    CountHist<psy::EncCount> eh;  // encode / decode plan counts
+    CountHist<psy::DecCount> dh;
     // buffers replaced by a larger one: a graph captured on the context before the growth may
     // still point at them, so they are freed only with the workspace
     std::vector<void *> retired;
@@ -394,11 +399,14 @@ constexpr uint32_t kLmax = 1u << 16;   // large messages per batch (full budget)
 uint32_t tile_cap_of(int ws) { return (262144u / (uint32_t)ws) * psy::kSpanTiles; }
 // the budget a context starts with (512 MiB of large messages); plans that claim more grow it
 constexpr uint32_t kL0 = 1024, kT0 = 8192;
-size_t elarge_bytes(uint32_t lcap, uint32_t tcap, int ws) {
-    const size_t sc = tcap / psy::kSpanTiles;
-    // LMeta | tile entries | tile records | span entries | span bins | count-pass tile list
-    return (size_t)lcap * sizeof(psy::LMeta) + (size_t)tcap * (8 + sizeof(psy::TileRec)) + sc * 8 + sc * ws * 1024 +
-           (size_t)tcap * 8;
+// the large-message records (PlanWS::elarge): LMeta | tile entries | tile records | span entries |
+// span bins | count-pass tile list, as byte offsets
+struct ELargeLayout { size_t tiles, trec, spans, shist, rtiles, bytes; };  // (LMeta at 0)
+ELargeLayout elarge_layout(uint32_t lcap, uint32_t tcap, int ws) {
+    const size_t sc = tcap / psy::kSpanTiles, tiles = (size_t)lcap * sizeof(psy::LMeta), trec = tiles + 8ull * tcap,
+                 spans = trec + sizeof(psy::TileRec) * (size_t)tcap, shist = spans + 8 * sc,
+                 rtiles = shist + sc * ws * 1024;  // (WS x 256 u32 bins per span)
+    return {tiles, trec, spans, shist, rtiles, rtiles + 8ull * tcap};
 }
 uint32_t pow2_at_least(uint64_t x, uint32_t lo, uint32_t hi) {
     uint64_t p = lo;
@@ -407,7 +415,7 @@ uint32_t pow2_at_least(uint64_t x, uint32_t lo, uint32_t hi) {
 }
 
 int ensure_plan(PlanWS &w, uint32_t n, hipStream_t s) {
-    const size_t need = 256 + 20ull * n;  // counters | small | medium | mid-sized | big | copy lists
+    const size_t need = psy::plan_layout(n).bytes;
     if (need > w.bytes) {
         if (int st = no_growth_in_capture(s)) return st;
         if (w.buf) w.retired.push_back(w.buf);  // (a graph captured earlier may use it)
@@ -443,12 +451,13 @@ int small_copies(hipStream_t s, const void *s0, void *d0, size_t b0, const void 
 }
 
 // The plan counters of this call → pinned snapshot (not under stream capture).
-int record_counts(CountHist &h, const void *dcnt, uint32_t n_msgs, hipStream_t s) {
+template <class K>
+int record_counts(CountHist<K> &h, const void *dcnt, uint32_t n_msgs, hipStream_t s) {
     if (!h.pin) {
-        HIPCHK(hipHostMalloc(&h.pin, 128, hipHostMallocDefault));
+        HIPCHK(hipHostMalloc(&h.pin, psy::kPlanSnapBytes, hipHostMallocDefault));
         HIPCHK(hipEventCreateWithFlags(&h.ev, hipEventDisableTiming));
     }
-    if (int st = small_copies(s, dcnt, h.pin, 128)) return st;
+    if (int st = small_copies(s, dcnt, h.pin, psy::kPlanSnapBytes)) return st;
     HIPCHK(hipEventRecord(h.ev, s));
     h.n_pending = n_msgs;
     h.pending = true;
@@ -456,9 +465,10 @@ int record_counts(CountHist &h, const void *dcnt, uint32_t n_msgs, hipStream_t s
 }
 
 // Main-launch grid of a class: the earlier count plus slack (capped), or `dflt` before any.
-uint32_t guess(const CountHist &h, int idx, uint32_t bound, uint32_t dflt) {
+template <class K>
+uint32_t guess(const CountHist<K> &h, K k, uint32_t bound, uint32_t dflt) {
     if (!h.valid) return std::min(dflt, bound);
-    const uint64_t x = h.v[idx];
+    const uint64_t x = h[k];
     return (uint32_t)std::min<uint64_t>(x + x / 8 + 64, bound);
 }
 
@@ -487,9 +497,9 @@ int join_side(PlanWS &w, hipStream_t s) {
 int ensure_elarge(PlanWS &w, int ws, hipStream_t s) {
     uint32_t lc = w.e_lcap ? w.e_lcap : kL0, tc = w.e_tcap ? w.e_tcap : kT0;
     if (w.eh.valid) {
-        lc = std::max(lc, pow2_at_least(w.eh.v[4], kL0, kLmax));
-        tc = std::max(tc, pow2_at_least(std::max<uint64_t>(w.eh.v[6], (uint64_t)w.eh.v[8] * psy::kSpanTiles), kT0,
-                                        tile_cap_of(ws)));
+        lc = std::max(lc, pow2_at_least(w.eh[psy::EC_LARGE], kL0, kLmax));
+        const uint64_t t = std::max<uint64_t>(w.eh[psy::EC_TILES], (uint64_t)w.eh[psy::EC_SPANS] * psy::kSpanTiles);
+        tc = std::max(tc, pow2_at_least(t, kT0, tile_cap_of(ws)));
     }
     if (w.elarge && lc == w.e_lcap && tc == w.e_tcap) return TDT_OK;
     if (w.elarge) {
@@ -499,7 +509,7 @@ int ensure_elarge(PlanWS &w, int ws, hipStream_t s) {
         w.elarge = nullptr;
         w.e_lcap = w.e_tcap = 0;
     }
-    const size_t b = elarge_bytes(lc, tc, ws);
+    const size_t b = elarge_layout(lc, tc, ws).bytes;
     HIPCHK(hipMalloc(&w.elarge, b));
     HIPCHK(hipMemsetAsync(w.elarge, 0, b, s));
     w.e_lcap = lc;
@@ -515,9 +525,53 @@ void launch_list(uint32_t count, uint32_t team, F &&launch) {
     for (uint32_t b = 0; b < count; b += mx) launch(b, std::min(mx, count - b));
 }
 
+// One class of a slotted call: the main launch, one workgroup per entry over [0, g) (g from an
+// earlier plan's count, guess(); launches of < 2^32 threads each), then the overflow launch of at
+// most `ovf` workgroups striding over [g, bound).  `list` and its length, counter `k`, go into the
+// kernels' arguments (null for the tile passes: their entries are the large-message records).
+template <class Args>
+struct ClassLaunch {
+    Args &a;
+    const uint32_t *cnt;  // u32 view of the plan's counter block
+    template <class K, class KM, class KO>
+    void operator()(const uint32_t *list, K k, uint32_t g, uint32_t bound, uint32_t team, uint32_t ovf, hipStream_t s,
+                    KM main_k, KO over_k) const {
+        if (list) {
+            a.list = list;
+            a.list_count = cnt + psy::lo32(k);
+        }
+        launch_list(g, team, [&](uint32_t b, uint32_t grid) {
+            a.list_base = b;
+            hipLaunchKernelGGL(main_k, dim3(grid), dim3(team), 0, s, a);
+        });
+        if (g < bound) {
+            a.list_base = g;
+            hipLaunchKernelGGL(over_k, dim3(std::min(ovf, bound - g)), dim3(team), 0, s, a);
+        }
+    }
+};
+
+// cfg.word_size as a compile-time WS: f(Int<WS>), W() in f, for the tuned word sizes (diagnostic
+// builds: 4 only); false for every other one (the callers' generic-width routes)
+template <int V>
+using Int = std::integral_constant<int, V>;
+template <class F>
+bool with_word_size(int ws, F &&f) {
+    switch (ws) {
+#ifndef PSY_FAST_BUILD
+        case 1: f(Int<1>{}); return true;
+        case 2: f(Int<2>{}); return true;
+        case 8: f(Int<8>{}); return true;
+        case 16: f(Int<16>{}); return true;
+#endif
+        case 4: f(Int<4>{}); return true;
+        default: return false;
+    }
+}
+
 template <int WS>
 int launch_slotted(tdt_ctx *c, PlanWS &pw, psy::EncodeArgs a, hipStream_t s) {
-    using psy::MODE_ENCODE;
+    using namespace psy;  // (counter, list and kernel names)
     const uint32_t n = a.n_msgs;
     // the list-entry prefetch of the slotted kernels (EncodeArgs::list) reads entry
     // min(i, n - 1) of a class list before its count: n >= 1, and every list holds n entries
@@ -525,57 +579,50 @@ int launch_slotted(tdt_ctx *c, PlanWS &pw, psy::EncodeArgs a, hipStream_t s) {
     if (n == 0) return set_err(TDT_E_ARG, "slotted encode launch without messages");
     int st = ensure_plan(pw, n, s);
     if (st) return st;
-    if (pw.bytes < 256 + 20ull * n) return set_err(TDT_E_ARG, "plan buffer smaller than five lists of n entries");
+    const PlanLayout PL = plan_layout(n);
+    if (pw.bytes < PL.bytes) return set_err(TDT_E_ARG, "plan buffer smaller than five lists of n entries");
     const bool capturing = ::capturing(s);
-    CountHist &H = pw.eh;
+    auto &H = pw.eh;
     if (!capturing) H.refresh();  // (event queries are not capturable)
     // classes an earlier plan found empty are off (their messages, if any, go medium)
-    const bool small_on = !H.valid || H.v[10] > 0;  // (counter 5: small messages, listed or not)
-    const bool mid_on = !H.valid || H.v[14] > 0;    // (counter 7: mid-sized messages, listed or not)
-    const bool copy_on = !H.valid || H.v[18] > 0;   // (counter 9: UNCP messages)
-    bool tiles_on = !H.valid || H.v[4] > 0;
+    const bool small_on = !H.valid || H[EC_SMALL_ALL] > 0;
+    const bool mid_on = !H.valid || H[EC_MID_ALL] > 0;
+    const bool copy_on = !H.valid || H[EC_UNCP_ALL] > 0;
+    bool tiles_on = !H.valid || H[EC_LARGE] > 0;
     if (tiles_on && !capturing) {
         st = ensure_elarge(pw, WS, s);
         if (st) return st;
     }
     tiles_on = tiles_on && pw.elarge;
     auto *cnt64 = reinterpret_cast<unsigned long long *>(pw.buf);
-    auto *cnt = reinterpret_cast<uint32_t *>(pw.buf);  // cnt[2k]: the low word of counter k
-    uint32_t *slist = reinterpret_cast<uint32_t *>(pw.buf + 256), *mlist = slist + n, *qlist = mlist + n,
-             *blist = qlist + n, *clist = blist + n;
+    auto *cnt = reinterpret_cast<uint32_t *>(pw.buf);  // cnt[lo32(k)]: the low word of counter k
+    auto list = [&](EncList l) { return reinterpret_cast<uint32_t *>(pw.buf + PL.list[l]); };
     const uint32_t lcap = tiles_on ? pw.e_lcap : 0u;
-    const uint32_t tcap = tiles_on ? std::min(pw.e_tcap, std::max(c->tile_cap, psy::kSpanTiles)) : 0u;
-    const uint32_t scap = tcap / psy::kSpanTiles;
-    auto *lmeta = reinterpret_cast<psy::LMeta *>(pw.elarge);
-    auto *tiles = reinterpret_cast<uint64_t *>(pw.elarge + (size_t)pw.e_lcap * sizeof(psy::LMeta));
-    auto *trec = reinterpret_cast<psy::TileRec *>(reinterpret_cast<uint8_t *>(tiles) + 8ull * pw.e_tcap);
-    auto *spans =
-        reinterpret_cast<uint64_t *>(reinterpret_cast<uint8_t *>(trec) + sizeof(psy::TileRec) * pw.e_tcap);
-    auto *shist = reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(spans) + 8ull * (pw.e_tcap / psy::kSpanTiles));
-    auto *rtiles = reinterpret_cast<uint64_t *>(shist + (size_t)(pw.e_tcap / psy::kSpanTiles) * WS * 256);
-    HIPCHK(hipMemsetAsync(cnt, 0, 128, s));
-    psy::PlanArgs p{a.in,      a.in_off,  n,       cnt64,   slist,          mlist,              qlist,
-                    blist,     clist,   tiles,   spans,          lmeta,              lcap,
-                    tcap,      kSmallMax, kMidMax, kBigMin,      c->large_min,       small_on ? 1u : 0u,
-                    mid_on ? 1u : 0u, a.min_tensor, (uint32_t)a.policy_on, (uint32_t)WS, copy_on ? 1u : 0u};
-    const uint32_t per = psy::kPlanThreads * psy::kPlanPer;
-    hipLaunchKernelGGL(psy::tdt_encode_plan_kernel, dim3((uint32_t)(((uint64_t)n + per - 1) / per)),
-                       dim3(psy::kPlanThreads), 0, s, p);
+    const uint32_t tcap = tiles_on ? std::min(pw.e_tcap, std::max(c->tile_cap, kSpanTiles)) : 0u;
+    const uint32_t scap = tcap / kSpanTiles;
+    // (the records lie where the allocated budgets put them, whatever this call's tcap)
+    const ELargeLayout EL = elarge_layout(pw.e_lcap, pw.e_tcap, WS);
+    auto *lmeta = reinterpret_cast<LMeta *>(pw.elarge);
+    auto *tiles = reinterpret_cast<uint64_t *>(pw.elarge + EL.tiles);
+    auto *spans = reinterpret_cast<uint64_t *>(pw.elarge + EL.spans);
+    HIPCHK(hipMemsetAsync(cnt, 0, kPlanSnapBytes, s));
+    PlanArgs p{a.in, a.in_off, n, cnt64, list(EL_SMALL), list(EL_MEDIUM), list(EL_MID), list(EL_BIG), list(EL_COPY),
+               tiles, spans, lmeta, lcap, tcap, kSmallMax, kMidMax, kBigMin, c->large_min, small_on ? 1u : 0u,
+               mid_on ? 1u : 0u, a.min_tensor, (uint32_t)a.policy_on, (uint32_t)WS, copy_on ? 1u : 0u};
+    const uint32_t per = kPlanThreads * kPlanPer;
+    hipLaunchKernelGGL(tdt_encode_plan_kernel, dim3((uint32_t)(((uint64_t)n + per - 1) / per)), dim3(kPlanThreads), 0, s,
+                       p);
     HIPCHK(hipGetLastError());
     // (with tiles, the snapshot follows the map pass instead: it also holds the count pass's list length)
     if (!capturing && !tiles_on && (st = record_counts(H, cnt, n, s))) return st;
     a.pcnt = cnt;
     const uint32_t ovf512 = (uint32_t)c->cus * 3, ovf256 = (uint32_t)c->cus * 6, ovf64 = (uint32_t)c->cus * 24;
-    // main launch over [0, g) + overflow launch over [g, count) of one class
-    auto both = [&](uint32_t g, uint32_t bound, uint32_t ovf, auto &&main, auto &&over) {
-        if (g) main(0u, g);
-        if (g < bound) over(g, std::min(ovf, bound - g));
-    };
+    const ClassLaunch<EncodeArgs> cls{a, cnt};
     bool forked = false;
     hipStream_t ts = s;  // the tile pipeline's (and the small / mid-sized lists') stream
     // the side stream carries the tile pipeline and the small / mid-sized lists beside the medium
     // list (queued behind it on one stream they would run alone in its tail)
-    const bool medium_on = !H.valid || H.v[2] + H.v[16] > 0;  // (counters 1 and 8)
+    const bool medium_on = !H.valid || H[EC_MEDIUM] + H[EC_BIG] > 0;
     if (tiles_on || ((small_on || mid_on || copy_on) && medium_on && !c->small_main)) {
         const int fr = c->no_side || pw.no_side ? -1 : fork_side(pw, s);
         if (fr > 0) return fr;
@@ -586,135 +633,59 @@ int launch_slotted(tdt_ctx *c, PlanWS &pw, psy::EncodeArgs a, hipStream_t s) {
         a.tiles = tiles;
         a.spans = spans;
         a.lmeta = lmeta;
-        a.trec = trec;
-        a.shist = shist;
-        a.rtiles = rtiles;
-        a.rcount = cnt64 + 11;
+        a.trec = reinterpret_cast<TileRec *>(pw.elarge + EL.trec);
+        a.shist = reinterpret_cast<uint32_t *>(pw.elarge + EL.shist);
+        a.rtiles = reinterpret_cast<uint64_t *>(pw.elarge + EL.rtiles);
+        a.rcount = cnt64 + EC_RECOUNT;
         a.lcap = lcap;
         a.tcap = tcap;
-#define PSY_TILE_STEP(TL, IDX, BOUND)                                                                           \
-        both(guess(H, IDX, BOUND, 0), BOUND, ovf512,                                                            \
-             [&](uint32_t b, uint32_t g) {                                                                      \
-                 a.list_base = b;                                                                               \
-                 hipLaunchKernelGGL((psy::tdt_encode_kernel<WS, 512, 8, MODE_ENCODE, 0, TL, 0>), dim3(g), dim3(512), \
-                                    0, ts, a);                                                                  \
-             },                                                                                                 \
-             [&](uint32_t b, uint32_t g) {                                                                      \
-                 a.list_base = b;                                                                               \
-                 hipLaunchKernelGGL((psy::tdt_encode_kernel<WS, 512, 8, MODE_ENCODE, 0, TL, 1>), dim3(g), dim3(512), \
-                                    0, ts, a);                                                                  \
-             })
-        PSY_TILE_STEP(1, 8, scap);  // span histograms (and counts under the speculated mapping)
-        PSY_TILE_STEP(4, 4, lcap);  // mapping per large message; lists the tiles to count again
+        auto tile_pass = [&](auto TL, EncCount k, uint32_t bound) {  // (no main launch before any count is known)
+            cls(nullptr, k, guess(H, k, bound, 0), bound, 512, ovf512, ts,
+                tdt_encode_kernel<WS, 512, 8, MODE_ENCODE, 0, TL(), 0>,
+                tdt_encode_kernel<WS, 512, 8, MODE_ENCODE, 0, TL(), 1>);
+        };
+        tile_pass(Int<1>{}, EC_SPANS, scap);  // span histograms (and counts under the speculated mapping)
+        tile_pass(Int<4>{}, EC_LARGE, lcap);  // mapping per large message; lists the tiles to count again
         if (!capturing && (st = record_counts(H, cnt, n, ts))) return st;
-        PSY_TILE_STEP(2, 22, tcap);  // per-tile counts of the listed tiles
-        hipLaunchKernelGGL((psy::tdt_encode_lscan_kernel<WS>), dim3(std::max(1u, std::min(lcap, 1024u))), dim3(64), 0,
-                           ts, a, cnt + 4, lcap);
-        PSY_TILE_STEP(3, 6, tcap);  // emit
-#undef PSY_TILE_STEP
+        tile_pass(Int<2>{}, EC_RECOUNT, tcap);  // per-tile counts of the listed tiles
+        hipLaunchKernelGGL((tdt_encode_lscan_kernel<WS>), dim3(std::max(1u, std::min(lcap, 1024u))), dim3(64), 0, ts, a,
+                           cnt + lo32(EC_LARGE), lcap);
+        tile_pass(Int<3>{}, EC_TILES, tcap);  // emit
     }
     // medium messages: one workgroup per list entry — the big list first (longer or unaligned
     // messages: the streaming-only kernel; a long team started last would run alone in the
-    // kernel's tail), then the medium list (resident-only kernel)
+    // kernel's tail), then the medium list (resident-only kernel).  Both are always launched
+    // (messages of a class switched off join them; the overflow launch ends at once when the list
+    // is empty); the big list has no main launch when the history says it is empty
     a.list2 = nullptr;
-    {
-        // (always launched: messages of a class switched off join it; the overflow launch ends at
-        // once when the list is empty)
-        a.list = blist;
-        a.list_count = cnt + 16;
-        both(H.valid ? (H.v[16] ? guess(H, 16, n, n) : 0u) : n, n, ovf512,
-             [&](uint32_t b, uint32_t g) {
-                 launch_list(g, 512, [&](uint32_t b2, uint32_t g2) {
-                     a.list_base = b + b2;
-                     hipLaunchKernelGGL((psy::tdt_encode_kernel<WS, 512, 8, MODE_ENCODE, 0, 0, 0, psy::PATH_STREAM>),
-                                        dim3(g2), dim3(512), 0, s, a);
-                 });
-             },
-             [&](uint32_t b, uint32_t g) {
-                 a.list_base = b;
-                 hipLaunchKernelGGL((psy::tdt_encode_kernel<WS, 512, 8, MODE_ENCODE, 0, 0, 1, psy::PATH_STREAM>), dim3(g),
-                                    dim3(512), 0, s, a);
-             });
-    }
-    a.list = mlist;
-    a.list_count = cnt + 2;
-    const uint32_t gmed = H.valid ? guess(H, 2, n, n) : n;
-    both(gmed, n, ovf512,
-         [&](uint32_t b, uint32_t g) {
-             launch_list(g, 512, [&](uint32_t b2, uint32_t g2) {
-                 a.list_base = b + b2;
-                 hipLaunchKernelGGL((psy::tdt_encode_kernel<WS, 512, 8, MODE_ENCODE, 0, 0, 0, psy::PATH_RES>), dim3(g2),
-                                    dim3(512), 0, s, a);
-             });
-         },
-         [&](uint32_t b, uint32_t g) {
-             a.list_base = b;
-             hipLaunchKernelGGL((psy::tdt_encode_kernel<WS, 512, 8, MODE_ENCODE, 0, 0, 1, psy::PATH_RES>), dim3(g),
-                                dim3(512), 0, s, a);
-         });
-    // small messages behind the tile pipeline on the side stream (the two streams' loads balance
-    // better: C4's tile pipeline is shorter than its medium list)
-    if (small_on) {
-        const hipStream_t ss = forked && !c->small_main ? pw.side : s;
-        a.list = slist;
-        a.list_count = cnt;
-        both(guess(H, 0, n, n), n, ovf64,
-             [&](uint32_t b, uint32_t g) {
-                 launch_list(g, 64, [&](uint32_t b2, uint32_t g2) {
-                     a.list_base = b + b2;
-                     hipLaunchKernelGGL((psy::tdt_encode_kernel<WS, 64, 4, MODE_ENCODE, 0, 0, 0>), dim3(g2), dim3(64),
-                                        0, ss, a);
-                 });
-             },
-             [&](uint32_t b, uint32_t g) {
-                 a.list_base = b;
-                 hipLaunchKernelGGL((psy::tdt_encode_kernel<WS, 64, 4, MODE_ENCODE, 0, 0, 1>), dim3(g), dim3(64), 0,
-                                    ss, a);
-             });
-    }
-    // passthrough copies on the small list's stream
-    if (copy_on) {
-        a.list = clist;
-        a.list_count = cnt + 20;
+    cls(list(EL_BIG), EC_BIG, H.valid && !H[EC_BIG] ? 0u : guess(H, EC_BIG, n, n), n, 512, ovf512, s,
+        tdt_encode_kernel<WS, 512, 8, MODE_ENCODE, 0, 0, 0, PATH_STREAM>,
+        tdt_encode_kernel<WS, 512, 8, MODE_ENCODE, 0, 0, 1, PATH_STREAM>);
+    cls(list(EL_MEDIUM), EC_MEDIUM, guess(H, EC_MEDIUM, n, n), n, 512, ovf512, s,
+        tdt_encode_kernel<WS, 512, 8, MODE_ENCODE, 0, 0, 0, PATH_RES>,
+        tdt_encode_kernel<WS, 512, 8, MODE_ENCODE, 0, 0, 1, PATH_RES>);
+    // the small, copy and mid-sized lists behind the tile pipeline on the side stream (the two
+    // streams' loads balance better: C4's tile pipeline is shorter than its medium list)
+    const hipStream_t ss = forked && !c->small_main ? pw.side : s;
+    if (small_on)  // one-wave teams
+        cls(list(EL_SMALL), EC_SMALL, guess(H, EC_SMALL, n, n), n, 64, ovf64, ss,
+            tdt_encode_kernel<WS, 64, 4, MODE_ENCODE, 0, 0, 0>, tdt_encode_kernel<WS, 64, 4, MODE_ENCODE, 0, 0, 1>);
+    if (copy_on) {  // passthrough copies
+        a.list = list(EL_COPY);
+        a.list_count = cnt + lo32(EC_UNCP);
         hipLaunchKernelGGL(tdt_encode_copy_kernel, dim3(std::max(1u, std::min((uint32_t)c->cus * c->copy_wgs, (n + 15) / 16))),
-                           dim3(256), 0, forked && !c->small_main ? pw.side : s, a);
+                           dim3(256), 0, ss, a);
     }
-    // mid-sized messages (256-lane teams) on the small list's stream
-    if (mid_on) {
-        const hipStream_t qs = forked && !c->small_main ? pw.side : s;
-        a.list = qlist;
-        a.list_count = cnt + 12;
-        both(guess(H, 12, n, n), n, ovf256,
-             [&](uint32_t b, uint32_t g) {
-                 launch_list(g, 256, [&](uint32_t b2, uint32_t g2) {
-                     a.list_base = b + b2;
-                     hipLaunchKernelGGL((psy::tdt_encode_kernel<WS, 256, 8, MODE_ENCODE, 0, 0, 0>), dim3(g2),
-                                        dim3(256), 0, qs, a);
-                 });
-             },
-             [&](uint32_t b, uint32_t g) {
-                 a.list_base = b;
-                 hipLaunchKernelGGL((psy::tdt_encode_kernel<WS, 256, 8, MODE_ENCODE, 0, 0, 1>), dim3(g), dim3(256), 0,
-                                    qs, a);
-             });
-    }
+    if (mid_on)  // 256-lane teams
+        cls(list(EL_MID), EC_MID, guess(H, EC_MID, n, n), n, 256, ovf256, ss,
+            tdt_encode_kernel<WS, 256, 8, MODE_ENCODE, 0, 0, 0>, tdt_encode_kernel<WS, 256, 8, MODE_ENCODE, 0, 0, 1>);
     if (forked) return join_side(pw, s);
     return TDT_OK;
 }
 
 int launch_slotted_any(tdt_ctx *c, PlanWS &pw, psy::EncodeArgs a, hipStream_t s) {
-    switch (c->cfg.word_size) {
-#ifdef PSY_FAST_BUILD
-        case 4: return launch_slotted<4>(c, pw, a, s);
-#else
-        case 1: return launch_slotted<1>(c, pw, a, s);
-        case 2: return launch_slotted<2>(c, pw, a, s);
-        case 4: return launch_slotted<4>(c, pw, a, s);
-        case 8: return launch_slotted<8>(c, pw, a, s);
-        case 16: return launch_slotted<16>(c, pw, a, s);
-#endif
-        default: break;
-    }
+    int st = TDT_OK;
+    if (with_word_size(c->cfg.word_size, [&](auto W) { st = launch_slotted<W()>(c, pw, a, s); })) return st;
     // generic widths: one workgroup per message, message id = block index, no plan
     return launch_any_encode(a, c->cfg.word_size, psy::MODE_ENCODE, s);
 }
@@ -741,9 +712,9 @@ int launch_encode_ws(psy::EncodeArgs a, bool small, bool res, hipStream_t s) {
 // one-wave teams when most messages of this context's latest slotted plan were small (<= 4 KiB),
 // the size hint only before any plan has been observed.
 bool lb_small_teams(tdt_ctx *c, hipStream_t s) {
-    CountHist &H = c->pw.eh;
+    auto &H = c->pw.eh;
     if (!capturing(s)) H.refresh();
-    if (H.valid && H.n) return 2ull * ((uint64_t)H.v[10] + H.v[18]) > H.n;  // (counters 5, 9: small, UNCP)
+    if (H.valid && H.n) return 2ull * ((uint64_t)H[psy::EC_SMALL_ALL] + H[psy::EC_UNCP_ALL]) > H.n;
     return c->size_hint.load() <= kSmallMax;
 }
 
@@ -753,18 +724,9 @@ template <int MODE, int LB>
 int launch_encode(tdt_ctx *c, psy::EncodeArgs a, hipStream_t s, int small_teams) {
     const bool small = small_teams < 0 ? lb_small_teams(c, s) : small_teams == 1;
     const bool res = small_teams == 2;
-    switch (c->cfg.word_size) {
-#ifdef PSY_FAST_BUILD  // diagnostic builds: word_size 4 only
-        case 4: return launch_encode_ws<4, MODE, LB>(a, small, res, s);
-#else
-        case 1: return launch_encode_ws<1, MODE, LB>(a, small, res, s);
-        case 2: return launch_encode_ws<2, MODE, LB>(a, small, res, s);
-        case 4: return launch_encode_ws<4, MODE, LB>(a, small, res, s);
-        case 8: return launch_encode_ws<8, MODE, LB>(a, small, res, s);
-        case 16: return launch_encode_ws<16, MODE, LB>(a, small, res, s);
-#endif
-        default: break;
-    }
+    int st = TDT_OK;
+    if (with_word_size(c->cfg.word_size, [&](auto W) { st = launch_encode_ws<W(), MODE, LB>(a, small, res, s); }))
+        return st;
     // generic widths: analysis, or a blob into its slot (the compacted entry points take the
     // two-phase route, encode_two_phase_any)
     if (MODE != psy::MODE_ANALYZE && !a.slot_off && psy::anyws_generic(c->cfg.word_size))
@@ -849,16 +811,21 @@ int encode_common(tdt_ctx *c, int mode, const uint8_t *d_in, const uint64_t *d_i
 // the device: main grids from an earlier call's counts, overflow launches past them.
 constexpr uint32_t kDLmax = 1u << 16, kDBcap = 1u << 23, kDTcap = 1u << 20;  // full budgets
 constexpr uint32_t kDL0 = 1024, kDB0 = 1u << 16, kDT0 = 8192;                 // starting budgets
-size_t dlarge_bytes(uint32_t lcap, uint32_t bcap, uint32_t tcap) {
-    return (size_t)lcap * sizeof(psy::DMeta) + 8ull * bcap + 4ull * tcap + 8ull * tcap;
+// the large-blob records (PlanWS::dlarge): DMeta | block entries | block sums | tile entries | tile
+// blocks (two per tile), as byte offsets
+struct DLargeLayout { size_t bent, bsum, tent, tblk, bytes; };  // (DMeta at 0)
+DLargeLayout dlarge_layout(uint32_t lcap, uint32_t bcap, uint32_t tcap) {
+    const size_t bent = (size_t)lcap * sizeof(psy::DMeta), bsum = bent + 4ull * bcap, tent = bsum + 4ull * bcap,
+                 tblk = tent + 4ull * tcap;
+    return {bent, bsum, tent, tblk, tblk + 8ull * tcap};
 }
 
 int ensure_dlarge(PlanWS &w) {
     uint32_t lc = w.d_lcap ? w.d_lcap : kDL0, bc = w.d_bcap ? w.d_bcap : kDB0, tc = w.d_tcap ? w.d_tcap : kDT0;
     if (w.dh.valid) {
-        lc = std::max(lc, pow2_at_least(w.dh.v[2], kDL0, kDLmax));
-        tc = std::max(tc, pow2_at_least(w.dh.v[4], kDT0, kDTcap));
-        bc = std::max(bc, pow2_at_least(w.dh.v[6], kDB0, kDBcap));
+        lc = std::max(lc, pow2_at_least(w.dh[psy::DC_LARGE], kDL0, kDLmax));
+        tc = std::max(tc, pow2_at_least(w.dh[psy::DC_TILES], kDT0, kDTcap));
+        bc = std::max(bc, pow2_at_least(w.dh[psy::DC_BLOCKS], kDB0, kDBcap));
     }
     if (w.dlarge && lc == w.d_lcap && bc == w.d_bcap && tc == w.d_tcap) return TDT_OK;
     if (w.dlarge) {
@@ -866,7 +833,7 @@ int ensure_dlarge(PlanWS &w) {
         w.dlarge = nullptr;
         w.d_lcap = w.d_bcap = w.d_tcap = 0;
     }
-    HIPCHK(hipMalloc(&w.dlarge, dlarge_bytes(lc, bc, tc)));
+    HIPCHK(hipMalloc(&w.dlarge, dlarge_layout(lc, bc, tc).bytes));
     w.d_lcap = lc;
     w.d_bcap = bc;
     w.d_tcap = tc;
@@ -874,15 +841,16 @@ int ensure_dlarge(PlanWS &w) {
 }
 
 int launch_decode_slotted(tdt_ctx *c, PlanWS &pw, psy::DecodeArgs a, hipStream_t s) {
+    using namespace psy;  // (counter, list and kernel names)
     const uint32_t n = a.n_msgs;
     int st = ensure_plan(pw, n, s);
     if (st) return st;
     const bool capturing = ::capturing(s);
-    CountHist &H = pw.dh;
+    auto &H = pw.dh;
     if (!capturing) H.refresh();
-    const bool small_on = !H.valid || H.v[10] > 0;  // counter 5: small blobs, listed or not
-    const bool copy_on = !H.valid || H.v[14] > 0;   // counter 7: UNCP blobs
-    bool large_on = !H.valid || H.v[2] > 0;
+    const bool small_on = !H.valid || H[DC_SMALL_ALL] > 0;
+    const bool copy_on = !H.valid || H[DC_UNCP_ALL] > 0;
+    bool large_on = !H.valid || H[DC_LARGE] > 0;
     if (large_on && !capturing) {
         st = ensure_dlarge(pw);
         if (st) return st;
@@ -890,50 +858,40 @@ int launch_decode_slotted(tdt_ctx *c, PlanWS &pw, psy::DecodeArgs a, hipStream_t
     large_on = large_on && pw.dlarge;
     auto *cnt = reinterpret_cast<unsigned long long *>(pw.buf);
     auto *cnt32 = reinterpret_cast<uint32_t *>(pw.buf);
-    auto *list = reinterpret_cast<uint32_t *>(pw.buf + 256);
-    uint32_t *slist = list + n, *blist = slist + n, *clist = blist + n;
+    const PlanLayout PL = plan_layout(n);
+    auto list = [&](DecList l) { return reinterpret_cast<uint32_t *>(pw.buf + PL.list[l]); };
 #if PSY_HAVE_ANYWS
     // the deferred-blob list (generic word sizes): the plan buffer's fifth list and last counter
-    a.dlist = clist + n;
-    a.dcount = cnt32 + 30;
+    a.dlist = list(DL_DEFERRED);
+    a.dcount = cnt32 + lo32(DC_DEFERRED);
 #endif
     const uint32_t lcap = large_on ? pw.d_lcap : 0u, bcap = large_on ? pw.d_bcap : 0u,
                    tcap = large_on ? pw.d_tcap : 0u;
-    auto *dmeta = reinterpret_cast<psy::DMeta *>(pw.dlarge);
-    auto *bent = reinterpret_cast<uint32_t *>(pw.dlarge + (size_t)pw.d_lcap * sizeof(psy::DMeta));
-    uint32_t *bsum = bent + pw.d_bcap, *tent = bsum + pw.d_bcap, *tblk = tent + pw.d_tcap;
-    HIPCHK(hipMemsetAsync(cnt, 0, 128, s));
-    psy::DPlanArgs p{a.in, a.in_off, a.in_len, n, cnt, list, slist, c->dsmall_max, blist, c->dbig_min, clist, dmeta,
-                     bent, tent, lcap, bcap, tcap, c->large_min, small_on ? 1u : 0u, copy_on ? 1u : 0u};
-    hipLaunchKernelGGL(psy::tdt_decode_plan_kernel, dim3((uint32_t)(((uint64_t)n + 4095) / 4096)), dim3(1024), 0, s, p);
+    const DLargeLayout DL = dlarge_layout(pw.d_lcap, pw.d_bcap, pw.d_tcap);
+    a.dmeta = reinterpret_cast<DMeta *>(pw.dlarge);
+    auto *bent = reinterpret_cast<uint32_t *>(pw.dlarge + DL.bent);
+    auto *tent = reinterpret_cast<uint32_t *>(pw.dlarge + DL.tent);
+    HIPCHK(hipMemsetAsync(cnt, 0, kPlanSnapBytes, s));
+    DPlanArgs p{a.in, a.in_off, a.in_len, n, cnt, list(DL_MAIN), list(DL_SMALL), c->dsmall_max, list(DL_BIG), c->dbig_min,
+                list(DL_COPY), a.dmeta, bent, tent, lcap, bcap, tcap, c->large_min, small_on ? 1u : 0u, copy_on ? 1u : 0u};
+    hipLaunchKernelGGL(tdt_decode_plan_kernel, dim3((uint32_t)(((uint64_t)n + 4095) / 4096)), dim3(1024), 0, s, p);
     HIPCHK(hipGetLastError());
     if (!capturing && (st = record_counts(H, cnt, n, s))) return st;
-    a.dmeta = dmeta;
     a.bent = bent;
-    a.bsum = bsum;
+    a.bsum = reinterpret_cast<uint32_t *>(pw.dlarge + DL.bsum);
     a.tent = tent;
-    a.tblk = tblk;
+    a.tblk = reinterpret_cast<uint32_t *>(pw.dlarge + DL.tblk);
     a.pcnt = cnt32;
     a.lcap = lcap;
     a.bcap = bcap;
     a.tcap = tcap;
     const uint32_t ovf = (uint32_t)c->cus * 32;
-    // one-wave list kernels: main launch over [0, g), overflow launch over [g, count)
-    auto lists = [&](uint32_t g, hipStream_t ls, auto main_k, auto over_k) {
-        if (g) launch_list(g, 64, [&](uint32_t b, uint32_t k) {
-            a.list_base = b;
-            hipLaunchKernelGGL(main_k, dim3(k), dim3(64), 0, ls, a);
-        });
-        if (g < n) {
-            a.list_base = g;
-            hipLaunchKernelGGL(over_k, dim3(std::min(ovf, n - g)), dim3(64), 0, ls, a);
-        }
-    };
+    const ClassLaunch<DecodeArgs> cls{a, cnt32};
     bool forked = false;
     hipStream_t ts = s;
     // the side stream carries the large-blob pipeline and the small-blob list beside the main
     // list (the small list queued behind the main list ran alone in its tail: C4 1.6 ms)
-    const bool main_on = !H.valid || H.v[0] + H.v[12] > 0;  // (counters 0 and 6)
+    const bool main_on = !H.valid || H[DC_MAIN] + H[DC_BIG] > 0;
     if (large_on || ((small_on || copy_on) && main_on && !c->small_main)) {
         const int fr = c->no_side || pw.no_side ? -1 : fork_side(pw, s);
         if (fr > 0) return fr;
@@ -942,41 +900,32 @@ int launch_decode_slotted(tdt_ctx *c, PlanWS &pw, psy::DecodeArgs a, hipStream_t
     }
     if (large_on) {
         const uint32_t gl = std::max(1u, std::min(lcap, 1024u));
-        hipLaunchKernelGGL(psy::tdt_decode_lprep_kernel, dim3(gl), dim3(256), 0, ts, a);
-        hipLaunchKernelGGL(psy::tdt_decode_lblock_kernel, dim3(std::max(1u, std::min((bcap + 3) / 4, ovf / 4))),
-                           dim3(256), 0, ts, a);
-        hipLaunchKernelGGL(psy::tdt_decode_lscan_kernel, dim3(gl, 2), dim3(64), 0, ts, a);
-        const uint32_t gt = guess(H, 4, tcap, 0);
-        if (gt) {
-            a.list_base = 0;
-            hipLaunchKernelGGL(psy::tdt_decode_ltile_kernel<0>, dim3(gt), dim3(64), 0, ts, a);
-        }
-        if (gt < tcap) {
-            a.list_base = gt;
-            hipLaunchKernelGGL(psy::tdt_decode_ltile_kernel<1>, dim3(std::min(ovf, tcap - gt)), dim3(64), 0, ts, a);
-        }
+        hipLaunchKernelGGL(tdt_decode_lprep_kernel, dim3(gl), dim3(256), 0, ts, a);
+        hipLaunchKernelGGL(tdt_decode_lblock_kernel, dim3(std::max(1u, std::min((bcap + 3) / 4, ovf / 4))), dim3(256), 0,
+                           ts, a);
+        hipLaunchKernelGGL(tdt_decode_lscan_kernel, dim3(gl, 2), dim3(64), 0, ts, a);
+        // (the tile entries are large-blob records, not a list; no main launch before any count is known)
+        cls(nullptr, DC_TILES, guess(H, DC_TILES, tcap, 0), tcap, 64, ovf, ts, tdt_decode_ltile_kernel<0>,
+            tdt_decode_ltile_kernel<1>);
     }
-    a.list = list;
-    a.list_count = cnt32;
-    a.blist = blist;
-    a.blist_count = cnt32 + 12;
-    const uint32_t gmain = H.valid ? std::min<uint32_t>(n, guess(H, 0, n, n) + guess(H, 12, n, n)) : n;
-    lists(gmain, s, psy::tdt_decode_kernel<0, psy::kDecWR, 0>, psy::tdt_decode_kernel<0, psy::kDecWR, 1>);
+    // the main list (one wave per blob), its kernels taking the big list's blobs first
+    a.blist = list(DL_BIG);
+    a.blist_count = cnt32 + lo32(DC_BIG);
+    cls(list(DL_MAIN), DC_MAIN, (uint32_t)std::min<uint64_t>(n, (uint64_t)guess(H, DC_MAIN, n, n) + guess(H, DC_BIG, n, n)),
+        n, 64, ovf, s, tdt_decode_kernel<0, kDecWR, 0>, tdt_decode_kernel<0, kDecWR, 1>);
     a.blist = nullptr;
+    const hipStream_t ss = forked && !c->small_main ? pw.side : s;
     // passthrough copies beside the main list
     if (copy_on) {
-        a.list = clist;
-        a.list_count = cnt32 + 16;
+        a.list = list(DL_COPY);
+        a.list_count = cnt32 + lo32(DC_UNCP);
         hipLaunchKernelGGL(tdt_decode_copy_kernel, dim3(std::max(1u, std::min((uint32_t)c->cus * c->copy_wgs, (n + 15) / 16))),
-                           dim3(256), 0, forked && !c->small_main ? pw.side : s, a);
+                           dim3(256), 0, ss, a);
     }
     // small blobs: one-round windows (a third less LDS per wave: more blobs in flight per CU)
-    if (small_on) {
-        a.list = slist;
-        a.list_count = cnt32 + 8;
-        lists(guess(H, 8, n, n), forked && !c->small_main ? pw.side : s, psy::tdt_decode_kernel<0, 1, 0>,
-              psy::tdt_decode_kernel<0, 1, 1>);
-    }
+    if (small_on)
+        cls(list(DL_SMALL), DC_SMALL, guess(H, DC_SMALL, n, n), n, 64, ovf, ss, tdt_decode_kernel<0, 1, 0>,
+            tdt_decode_kernel<0, 1, 1>);
     if (forked && (st = join_side(pw, s))) return st;
     // the deferred blobs (generic word sizes): near-empty when no kernel above listed one.  (A
     // fixed grid: the plan's count snapshot is taken before the class kernels append to the list,
@@ -1715,18 +1664,8 @@ int host_one(tdt_ctx *c, bool encode, const uint8_t *h_in, const uint64_t *h_in_
         a.policy_on = policy_on(c) ? 1 : 0;
         a.list = &dA->list;
         a.list_count = &dA->cnt;
-        switch (c->cfg.word_size) {
-#ifdef PSY_FAST_BUILD
-            case 4: launch_one_encode<4>(a, len, s); break;
-#else
-            case 1: launch_one_encode<1>(a, len, s); break;
-            case 2: launch_one_encode<2>(a, len, s); break;
-            case 4: launch_one_encode<4>(a, len, s); break;
-            case 8: launch_one_encode<8>(a, len, s); break;
-            case 16: launch_one_encode<16>(a, len, s); break;
-#endif
-            default: return -1;  // (generic widths took the pipeline above)
-        }
+        if (!with_word_size(c->cfg.word_size, [&](auto W) { launch_one_encode<W()>(a, len, s); }))
+            return -1;  // (generic widths took the pipeline above)
     } else {
         psy::DecodeArgs a{};
         a.in = db + kOneIn;

@@ -24,6 +24,7 @@
 #pragma once
 #include "tdt_device.h"
 #include "tdt_encode.h"
+#include "tdt_plan.h"
 
 namespace psy {
 
@@ -52,7 +53,7 @@ struct DecodeArgs {
     // one-wave blob of up to 1 MiB started late would run alone in the kernel's tail
     const uint32_t *blist;
     const uint32_t *blist_count;
-    // the plan's counters (u32 view: [2] large blobs, [4] tiles, [6] blocks claimed) and the
+    // the plan's counters (u32 view, lo32(): DC_LARGE, DC_TILES, DC_BLOCKS claimed) and the
     // budgets it ran with
     const uint32_t *pcnt;
     uint32_t lcap, tcap, bcap;
@@ -1415,10 +1416,7 @@ struct DPlanArgs {
     const uint64_t *in_off;
     const uint64_t *in_len;
     uint32_t n_msgs;
-    // [0] one-wave blobs, [1] large blobs, [2] tiles, [3] block slots, [4] small blobs (listed),
-    // [5] small blobs (listed or not: the host's count history switches the small list back on),
-    // [6] big one-wave blobs (their own list, dispatched first), [7] UNCP blobs (listed or not),
-    // [8] UNCP blobs listed (the copy list)
+    // the counter block (DecCount, tdt_plan.h)
     unsigned long long *cnt;
     uint32_t *list;
     uint32_t *slist;          // blobs decoding to <= small_max bytes (one-round windows: less LDS per wave)
@@ -1493,7 +1491,7 @@ __global__ __launch_bounds__(1024) void tdt_decode_plan_kernel(DPlanArgs p) {
         }
     }
     {
-        constexpr int ia[3] = {1, 2, 3};
+        constexpr int ia[3] = {DC_LARGE, DC_TILES, DC_BLOCKS};
         wg_claim_n<3, 4>(A, SA, p.cnt, ia, lds);
     }
 #pragma unroll
@@ -1529,7 +1527,7 @@ __global__ __launch_bounds__(1024) void tdt_decode_plan_kernel(DPlanArgs p) {
         one[k] = (any && !sm[k] && !big) ? 1u : 0u;
     }
     {
-        constexpr int ib[6] = {0, 4, 5, 6, 7, 8};
+        constexpr int ib[6] = {DC_MAIN, DC_SMALL, DC_SMALL_ALL, DC_BIG, DC_UNCP_ALL, DC_UNCP};
         wg_claim_n<6, 4>(B, SB, p.cnt, ib, lds);
     }
 #pragma unroll
@@ -1546,7 +1544,7 @@ __global__ __launch_bounds__(1024) void tdt_decode_plan_kernel(DPlanArgs p) {
 __global__ __launch_bounds__(256) void tdt_decode_lprep_kernel(DecodeArgs a) {
     __shared__ __attribute__((aligned(16))) uint8_t smem[DecLayout::BYTES];
     __shared__ uint32_t s_tiled, s_fast;
-    const uint32_t nl = __builtin_amdgcn_readfirstlane(umin(a.pcnt[2], a.lcap));
+    const uint32_t nl = __builtin_amdgcn_readfirstlane(umin(a.pcnt[lo32(DC_LARGE)], a.lcap));
     for (uint32_t j = blockIdx.x; j < nl; j += gridDim.x) {  // grid-stride over the large blobs
     if (j != blockIdx.x) __syncthreads();
     DMeta *m = a.dmeta + j;
@@ -1610,7 +1608,7 @@ __global__ __launch_bounds__(256) void tdt_decode_lprep_kernel(DecodeArgs a) {
 
 // Block pass: one wave per 512-pair block (8 pairs per lane): the block's count sum.
 __global__ __launch_bounds__(256) void tdt_decode_lblock_kernel(DecodeArgs a) {
-    const uint32_t nslots = __builtin_amdgcn_readfirstlane(umin(a.pcnt[6], a.bcap));
+    const uint32_t nslots = __builtin_amdgcn_readfirstlane(umin(a.pcnt[lo32(DC_BLOCKS)], a.bcap));
     for (uint32_t slot = blockIdx.x * 4u + (threadIdx.x >> 6); slot < nslots; slot += gridDim.x * 4u) {
     const uint32_t j = a.bent[slot];
     if (j == kNone) continue;
@@ -1636,7 +1634,7 @@ __global__ __launch_bounds__(256) void tdt_decode_lblock_kernel(DecodeArgs a) {
 // Scan: one wave per large blob and referenced stream: block sums → block start positions
 // (in place), the stream's decoded length, and each tile's carry block.
 __global__ __launch_bounds__(64) void tdt_decode_lscan_kernel(DecodeArgs a) {
-    const uint32_t nl = __builtin_amdgcn_readfirstlane(umin(a.pcnt[2], a.lcap));
+    const uint32_t nl = __builtin_amdgcn_readfirstlane(umin(a.pcnt[lo32(DC_LARGE)], a.lcap));
     const uint32_t r = blockIdx.y;
     for (uint32_t j = blockIdx.x; j < nl; j += gridDim.x) {  // grid-stride over the large blobs
     DMeta *m = a.dmeta + j;
@@ -1711,7 +1709,7 @@ __device__ __forceinline__ void decode_ltile(const DecodeArgs &a, uint8_t *smem,
 template <int PS = 0>
 __global__ __launch_bounds__(64) void tdt_decode_ltile_kernel(DecodeArgs a) {
     __shared__ __attribute__((aligned(16))) uint8_t smem[DecLayout::BYTES];
-    const uint32_t nt = __builtin_amdgcn_readfirstlane(umin(a.pcnt[4], a.tcap));
+    const uint32_t nt = __builtin_amdgcn_readfirstlane(umin(a.pcnt[lo32(DC_TILES)], a.tcap));
     const uint32_t i0 = a.list_base + blockIdx.x;
     if constexpr (PS) {
         for (uint32_t i = i0; i < nt; i += gridDim.x) {

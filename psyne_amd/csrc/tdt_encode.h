@@ -40,6 +40,7 @@
 #pragma once
 #include "tdt_device.h"
 #include "tdt_log2.h"
+#include "tdt_plan.h"
 
 #include <type_traits>
 
@@ -114,7 +115,7 @@ struct EncodeArgs {
     const uint32_t *list2;
     const uint32_t *list2_count;
     // tiled large messages: tile / span entries (L index | tile << 32); the plan's counters
-    // (u32 view: [4] large messages, [6] tiles, [8] spans claimed) and the budgets it ran with
+    // (u32 view, lo32(): EC_LARGE, EC_TILES, EC_SPANS claimed) and the budgets it ran with
     const uint64_t *tiles;
     const uint32_t *pcnt;
     uint32_t lcap, tcap;  // large-message entries, tiles (spans: tcap / kSpanTiles)
@@ -124,7 +125,7 @@ struct EncodeArgs {
     uint32_t *shist;  // per span: WS x 256 bin counts
     // the count pass's work list, appended by the map pass: every tile of a message whose mapping
     // is not the speculated one, and the tiles whose fused count could not rule the 255-cap out
-    // (entries as `tiles`; its length is plan counter 11, u32 view pcnt[22])
+    // (entries as `tiles`; its length is plan counter EC_RECOUNT)
     uint64_t *rtiles;
     unsigned long long *rcount;
 };
@@ -2170,10 +2171,10 @@ template <int TL>
 __device__ __forceinline__ uint32_t entry_count(const EncodeArgs &a) {
     uint32_t c;
     if constexpr (TL == 0) c = *a.list_count + (a.list2 ? *a.list2_count : 0u);
-    else if constexpr (TL == 4) c = umin(a.pcnt[4], a.lcap);
-    else if constexpr (TL == 1) c = umin(a.pcnt[8], a.tcap / kSpanTiles);
-    else if constexpr (TL == 2) c = umin(a.pcnt[22], a.tcap);
-    else c = umin(a.pcnt[6], a.tcap);
+    else if constexpr (TL == 4) c = umin(a.pcnt[lo32(EC_LARGE)], a.lcap);
+    else if constexpr (TL == 1) c = umin(a.pcnt[lo32(EC_SPANS)], a.tcap / kSpanTiles);
+    else if constexpr (TL == 2) c = umin(a.pcnt[lo32(EC_RECOUNT)], a.tcap);
+    else c = umin(a.pcnt[lo32(EC_TILES)], a.tcap);
     return __builtin_amdgcn_readfirstlane(c);
 }
 
@@ -2240,11 +2241,7 @@ struct PlanArgs {
     const uint8_t *in;  // (alignment of each message: the medium list is resident-only)
     const uint64_t *in_off;
     uint32_t n_msgs;
-    // [0] small (listed), [1] medium, [2] large entries, [3] tiles, [4] spans claimed, [5] small
-    // messages (listed or not: the host's count history switches the small class back on), [6]
-    // mid-sized (listed), [7] mid-sized messages (listed or not), [8] medium messages over big_min
-    // (their own list, dispatched first), [9] passthrough (UNCP) messages up to large_min (listed or
-    // not), [10] UNCP messages listed
+    // the counter block (EncCount, tdt_plan.h)
     unsigned long long *cnt;
     uint32_t *slist, *mlist, *qlist, *blist, *clist;
     uint64_t *tiles, *spans;
@@ -2290,7 +2287,7 @@ __global__ __launch_bounds__(kPlanThreads) void tdt_encode_plan_kernel(PlanArgs 
         S[k] = (T[k] + kSpanTiles - 1) / kSpanTiles;
     }
     {
-        constexpr int ia[3] = {2, 3, 4};
+        constexpr int ia[3] = {EC_LARGE, EC_TILES, EC_SPANS};
         wg_claim_n<3, kPlanPer>(A, SA, p.cnt, ia, lds);
     }
     auto &sm = B[0], &md = B[1], &sc = B[2], &qm = B[3], &qc = B[4], &bm = B[5], &cc = B[6], &cp = B[7];
@@ -2339,7 +2336,7 @@ __global__ __launch_bounds__(kPlanThreads) void tdt_encode_plan_kernel(PlanArgs 
         md[k] = medium && !bm[k] ? 1u : 0u;
     }
     {
-        constexpr int ib[8] = {0, 1, 5, 6, 7, 8, 9, 10};
+        constexpr int ib[8] = {EC_SMALL, EC_MEDIUM, EC_SMALL_ALL, EC_MID, EC_MID_ALL, EC_BIG, EC_UNCP_ALL, EC_UNCP};
         wg_claim_n<8, kPlanPer>(B, SB, p.cnt, ib, lds);
     }
 #pragma unroll

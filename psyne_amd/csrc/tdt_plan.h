@@ -1,0 +1,66 @@
+// tdt_plan.h — what the slotted calls' plan kernels, class kernels and host launchers share:
+// the names of the plan counters and the layout of the plan buffer.  Plain C++, no HIP types.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+
+namespace psy {
+
+// The counter block at the head of the plan buffer, by u64 index: the plan kernel claims list and
+// record ranges from the counters, the class kernels read a low word as a list length, and the host
+// reads it one call later (the pinned snapshot) to size grids and switch classes on and off.
+enum EncCount : int {
+    EC_SMALL = 0,        // small messages, listed
+    EC_MEDIUM = 1,       // medium messages, listed
+    EC_LARGE = 2,        // large-message entries claimed
+    EC_TILES = 3,        // tiles claimed
+    EC_SPANS = 4,        // spans claimed
+    EC_SMALL_ALL = 5,    // small messages, listed or not (switches the small class back on)
+    EC_MID = 6,          // mid-sized messages, listed
+    EC_MID_ALL = 7,      // mid-sized messages, listed or not
+    EC_BIG = 8,          // medium messages over big_min (their own list, dispatched first)
+    EC_UNCP_ALL = 9,     // passthrough (UNCP) messages up to large_min, listed or not
+    EC_UNCP = 10,        // UNCP messages, listed (the copy list)
+    EC_RECOUNT = 11      // tiles the map pass listed for the count pass (the highest)
+};
+enum DecCount : int {
+    DC_MAIN = 0,         // one-wave blobs (the main list)
+    DC_LARGE = 1,        // large blobs claimed
+    DC_TILES = 2,        // tiles claimed
+    DC_BLOCKS = 3,       // block slots claimed
+    DC_SMALL = 4,        // small blobs, listed
+    DC_SMALL_ALL = 5,    // small blobs, listed or not (switches the small list back on)
+    DC_BIG = 6,          // big one-wave blobs (their own list, dispatched first)
+    DC_UNCP_ALL = 7,     // UNCP blobs, listed or not
+    DC_UNCP = 8,         // UNCP blobs, listed (the copy list)
+    DC_DEFERRED = 15     // blobs of a generic word size the class kernels deferred (the highest)
+};
+
+// u32 view of the block: index of a counter's low word (the only place the two units meet)
+constexpr int lo32(EncCount k) { return 2 * (int)k; }
+constexpr int lo32(DecCount k) { return 2 * (int)k; }
+
+constexpr size_t kPlanCounterBytes = 256;  // the block
+constexpr size_t kPlanSnapBytes = 128;     // zeroed per call and copied to the host's snapshot
+static_assert(kPlanSnapBytes <= kPlanCounterBytes, "the snapshot is a prefix of the block");
+static_assert(8 * (EC_RECOUNT + 1) <= kPlanSnapBytes && 8 * (DC_DEFERRED + 1) <= kPlanSnapBytes,
+              "every counter is zeroed per call and snapshotted");
+
+// The lists behind the counters, n u32 entries each, in buffer order.
+enum EncList : int { EL_SMALL, EL_MEDIUM, EL_MID, EL_BIG, EL_COPY };
+enum DecList : int { DL_MAIN, DL_SMALL, DL_BIG, DL_COPY, DL_DEFERRED };
+constexpr int kPlanLists = 5;
+
+// The plan buffer of a batch of n messages: counters | five lists (256 + 20 * n bytes).
+struct PlanLayout {
+    size_t list[kPlanLists];  // byte offsets
+    size_t bytes;
+};
+constexpr PlanLayout plan_layout(uint32_t n) {
+    PlanLayout L{};
+    for (int i = 0; i < kPlanLists; ++i) L.list[i] = kPlanCounterBytes + 4ull * n * i;
+    L.bytes = kPlanCounterBytes + 4ull * n * kPlanLists;
+    return L;
+}
+
+}  // namespace psy
