@@ -8,7 +8,8 @@
 // requirements so that this header stands alone; a psyne build can equally
 // static_assert(psyne::concepts::Protocol<psyne_amd::HipTDTCompressionProtocol>).
 //
-// Batch extensions (encode_batch / decode_batch on device buffers) expose the batched
+// Batch extensions (encode_batch / decode_batch on device buffers, encode_batch_v / decode_batch_v
+// on one device buffer per message) expose the batched
 // kernels directly for callers that hold many messages (the hot path bench.py measures).
 #pragma once
 
@@ -168,6 +169,16 @@ public:
     int decode_batch(const uint8_t *d_in, const uint64_t *d_in_off, uint32_t n, uint8_t *d_out, uint64_t cap,
                      uint64_t *d_out_off, int32_t *d_status, void *stream = nullptr) {
         return tdt_decode_batch(ctx_, d_in, d_in_off, n, d_out, cap, d_out_off, d_status, stream);
+    }
+    // scattered batches: message i at d_msgs[i] (d_sizes[i] bytes), blob i at d_blobs[i] — one buffer
+    // per message, as a loop of encode / decode calls holds them (tdt_encode_batch_v)
+    int encode_batch_v(const uint8_t *const *d_msgs, const uint64_t *d_sizes, uint32_t n, uint8_t *const *d_blobs,
+                       const uint64_t *d_blob_cap, uint64_t *d_out_len, int32_t *d_status, void *stream = nullptr) {
+        return tdt_encode_batch_v(ctx_, d_msgs, d_sizes, n, d_blobs, d_blob_cap, d_out_len, d_status, stream);
+    }
+    int decode_batch_v(const uint8_t *const *d_blobs, const uint64_t *d_blob_len, uint32_t n, uint8_t *const *d_outs,
+                       const uint64_t *d_out_cap, uint64_t *d_out_len, int32_t *d_status, void *stream = nullptr) {
+        return tdt_decode_batch_v(ctx_, d_blobs, d_blob_len, n, d_outs, d_out_cap, d_out_len, d_status, stream);
     }
     tdt_ctx *context() { return ctx_; }
     int word_size() const { return config_.word_size; }

@@ -20,6 +20,10 @@
  *   tdt_decoded_sizes_batch           the output size decode would produce (header parse)
  *   tdt_encode_batch_into /           encode / decode into caller slots (one vector per
  *   tdt_decode_batch_into             message, as the reference returns them)
+ *   tdt_encode_batch_v /              a loop of encode :227-266 / decode :271-304 over messages
+ *   tdt_decode_batch_v                that lie in separate device buffers (one tensor, one
+ *                                     transport_send(void*, size_t) buffer per message)
+ *   tdt_decoded_sizes_v               tdt_decoded_sizes_batch over such blobs
  *   tdt_analyze_batch                 analyze_data / extract_features / perform_clustering
  *                                     :206-222, :434-525 (full-sample histograms, entropies,
  *                                     mapping per message)
@@ -155,6 +159,39 @@ int tdt_encode_batch_into(tdt_ctx *ctx, const uint8_t *d_in, const uint64_t *d_i
 int tdt_decode_batch_into(tdt_ctx *ctx, const uint8_t *d_in, const uint64_t *d_in_off, const uint64_t *d_in_len,
                           uint32_t n_msgs, uint8_t *d_out, const uint64_t *d_slot_off, uint64_t *d_out_len,
                           int32_t *d_status, void *hip_stream);
+/* SCATTERED batches — the slotted calls for messages that do not lie in one buffer: message i is
+ * d_msgs[i][0 .. d_sizes[i]) and blob i is written at d_blobs[i] with capacity d_blob_cap[i] (encode);
+ * blob i is d_blobs[i][0 .. d_blob_len[i]) and message i is written at d_outs[i] with capacity
+ * d_out_cap[i] (decode).  Every array holds n_msgs entries in device memory; the calls are
+ * asynchronous on hip_stream and the host reads nothing back.
+ *   Same bytes: per message, the result, its length (d_out_len[i]) and its status are exactly what
+ *     tdt_encode_batch_into / tdt_decode_batch_into give for the same message bytes and the same
+ *     capacity, in every message class.
+ *   Statuses: an output whose capacity is too small gets TDT_E_CAPACITY and length 0; an error blob
+ *     gets its usual status and length 0; a blob of a generic word size (1..64 other than 1, 2, 4,
+ *     8, 16) is decoded and may be mixed into any batch; a context of a generic word size encodes
+ *     through the generic kernels.
+ *   Addressing: the pointers may have any alignment and stand in any order (ascending, descending,
+ *     shuffled).  Inputs may alias each other (the same buffer may be listed twice); outputs must
+ *     not overlap each other or any input.  The pointer of a message or blob of size 0 is never
+ *     dereferenced and may be null.  No byte is written outside [ptr, ptr + cap) of any output,
+ *     whatever the status.
+ *   Context rules: those of the slotted calls — one stream at a time per context, the side stream
+ *     as there; capturable at every word size once one eager scattered call of the batch size has
+ *     grown the workspace (TDT_E_CAPTURE otherwise); n_msgs == 0 returns TDT_OK and touches nothing.
+ *   Mixed layouts: for gathered input into ONE slotted output buffer fill d_blobs[i] = out +
+ *     slot_off[i] and d_blob_cap[i] = slot_off[i+1] - slot_off[i].
+ * A batch's tiled-path threshold (1/4096 of its bytes) comes from the sum of the sizes, taken on
+ * the device.  Replaces a loop of TDTCompressionProtocol::encode / decode over per-message buffers. */
+int tdt_encode_batch_v(tdt_ctx *ctx, const uint8_t *const *d_msgs, const uint64_t *d_sizes, uint32_t n_msgs,
+                       uint8_t *const *d_blobs, const uint64_t *d_blob_cap, uint64_t *d_out_len, int32_t *d_status,
+                       void *hip_stream);
+int tdt_decode_batch_v(tdt_ctx *ctx, const uint8_t *const *d_blobs, const uint64_t *d_blob_len, uint32_t n_msgs,
+                       uint8_t *const *d_outs, const uint64_t *d_out_cap, uint64_t *d_out_len, int32_t *d_status,
+                       void *hip_stream);
+/* Decoded size of each scattered blob (0 with an error status), as tdt_decoded_sizes_batch. */
+int tdt_decoded_sizes_v(tdt_ctx *ctx, const uint8_t *const *d_blobs, const uint64_t *d_blob_len, uint32_t n_msgs,
+                        uint64_t *d_sizes, int32_t *d_status, void *hip_stream);
 /* d_slot_off (n+1 entries) = exclusive prefix sum of tdt_encode_bound(size_i, word_size). */
 int tdt_encode_slots(tdt_ctx *ctx, const uint64_t *d_in_off, uint32_t n_msgs, uint64_t *d_slot_off,
                      void *hip_stream);

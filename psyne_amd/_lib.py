@@ -45,6 +45,9 @@ SIGNATURES = {
     "tdt_decoded_sizes_batch": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp]),
     "tdt_encode_batch_into": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp]),
     "tdt_decode_batch_into": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp]),
+    "tdt_encode_batch_v": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp]),
+    "tdt_decode_batch_v": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp]),
+    "tdt_decoded_sizes_v": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp]),
     "tdt_encode_slots": (C.c_int, [_vp, _vp, C.c_uint32, _vp, _vp]),
     "tdt_decode_slots": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp]),
     "tdt_analyze_batch": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp]),
@@ -76,7 +79,14 @@ def load(path: pathlib.Path | None = None) -> C.CDLL:
         raise RuntimeError(f"{p} not built: run `python -m psyne_amd.build` (hipcc --offload-arch=gfx950)")
     lib = C.CDLL(str(p))
     for name, (res, args) in SIGNATURES.items():
-        f = getattr(lib, name)
+        f = getattr(lib, name, None)
+        if f is None:
+            # an older build chosen with PSYNE_TDT_LIB or `path` (A/B runs against a parent commit's
+            # library) may lack newer entry points: calling one then raises AttributeError.  The
+            # product library exports every one of them.
+            if p == LIB_PATH:
+                raise RuntimeError(f"{p} does not export {name}: rebuild it (`python -m psyne_amd.build`)")
+            continue
         f.restype = res
         f.argtypes = args
     if path is None:

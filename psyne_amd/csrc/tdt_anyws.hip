@@ -52,7 +52,7 @@ __device__ __forceinline__ uint32_t byte_of(const uint32_t (&w)[4], int i) { ret
 
 // ---------------------------------------------------------------------------------------
 // Encode.  HP: histogram positions held in LDS (>= ws; 1 for MODE_MAPPED, which has none).
-template <int MODE, int HP>
+template <int MODE, int HP, bool PAIR = false>
 __global__ __launch_bounds__(kAnyTeam) void tdt_encode_any_kernel(EncodeArgs a, uint32_t ws) {
     __shared__ uint32_t s_hist[HP * 256];
     __shared__ double s_ent[kAnyWsMax];
@@ -65,8 +65,8 @@ __global__ __launch_bounds__(kAnyTeam) void tdt_encode_any_kernel(EncodeArgs a, 
     const uint32_t tid = threadIdx.x, lane = (uint32_t)lane_id(), wv = tid >> 6;
     const uint32_t msg = blockIdx.x;
     if (msg >= a.n_msgs) return;
-    const uint64_t off0 = a.in_off[msg];
-    const uint64_t n = a.in_off[msg + 1] - off0;
+    const uint64_t off0 = a.in_off[table_at<PAIR>(msg, 0)];
+    const uint64_t n = a.in_off[table_at<PAIR>(msg, 1)] - off0;
     const uint8_t *base = a.in + off0;
     const uint8_t *lim = base + n;
 
@@ -84,8 +84,8 @@ __global__ __launch_bounds__(kAnyTeam) void tdt_encode_any_kernel(EncodeArgs a, 
     }
     uint64_t slot_b = 0, cap = 0;
     if constexpr (MODE != MODE_ANALYZE) {
-        slot_b = a.slot_off[msg];
-        cap = a.slot_off[msg + 1] - slot_b;
+        slot_b = a.slot_off[table_at<PAIR>(msg, 0)];
+        cap = a.slot_off[table_at<PAIR>(msg, 1)] - slot_b;
         if (!compress) {
             const uint64_t E = n + 4;
             const bool fits = E <= cap;
@@ -355,6 +355,7 @@ __global__ __launch_bounds__(kAnyTeam) void tdt_encode_any_kernel(EncodeArgs a, 
 // and at least one whole word.  Every output byte is written exactly once: by the pair that
 // covers it, or as zero (a stream shorter than its share of the words, the bytes past the
 // last whole word: recombine_byte_streams :614-637 over its zero-initialised result).
+template <bool PAIR = false>
 __global__ __launch_bounds__(kAnyTeam) void tdt_decode_any_kernel(DecodeArgs a) {
     __shared__ uint32_t s_map[kAnyWsMax], s_soff[kAnyWsMax], s_slen[kAnyWsMax], s_ptab[kAnyWsMax];
     __shared__ uint32_t s_slots[2][kAW];
@@ -373,8 +374,8 @@ __global__ __launch_bounds__(kAnyTeam) void tdt_decode_any_kernel(DecodeArgs a) 
         uint64_t ob;
         bool fits;
         if (a.slot_off) {
-            ob = a.slot_off[msg];
-            fits = orig <= a.slot_off[msg + 1] - ob;
+            ob = a.slot_off[table_at<PAIR>(msg, 0)];
+            fits = orig <= a.slot_off[table_at<PAIR>(msg, 1)] - ob;
         } else {
             ob = a.out_off[msg];  // (the look-back kernel placed it)
             fits = ob + orig <= a.out_cap;
@@ -471,8 +472,9 @@ __global__ __launch_bounds__(kAnyTeam) void tdt_decode_any_kernel(DecodeArgs a) 
 
 }  // namespace
 
-int launch_encode_any(const EncodeArgs &a, int ws, int mode, hipStream_t s) {
+int launch_encode_any(const EncodeArgs &a, int ws, int mode, hipStream_t s, bool pair) {
     if (a.n_msgs == 0) return 0;
+    if (pair && mode != MODE_ENCODE) return (int)hipErrorInvalidValue;
     const dim3 g(a.n_msgs), t(kAnyTeam);
     const uint32_t w = (uint32_t)ws;
 #define PSY_ANY_HP(MODE_)                                                                              \
@@ -482,15 +484,23 @@ int launch_encode_any(const EncodeArgs &a, int ws, int mode, hipStream_t s) {
         else if (ws <= 32) hipLaunchKernelGGL((tdt_encode_any_kernel<MODE_, 32>), g, t, 0, s, a, w);   \
         else hipLaunchKernelGGL((tdt_encode_any_kernel<MODE_, 64>), g, t, 0, s, a, w);                 \
     } while (0)
-    if (mode == MODE_ENCODE) PSY_ANY_HP(MODE_ENCODE);
+    if (pair) {
+#define PSY_ANY_PAIR(HP_) hipLaunchKernelGGL((tdt_encode_any_kernel<MODE_ENCODE, HP_, true>), g, t, 0, s, a, w)
+        if (ws <= 8) PSY_ANY_PAIR(8);
+        else if (ws <= 16) PSY_ANY_PAIR(16);
+        else if (ws <= 32) PSY_ANY_PAIR(32);
+        else PSY_ANY_PAIR(64);
+#undef PSY_ANY_PAIR
+    } else if (mode == MODE_ENCODE) PSY_ANY_HP(MODE_ENCODE);
     else if (mode == MODE_ANALYZE) PSY_ANY_HP(MODE_ANALYZE);
     else hipLaunchKernelGGL((tdt_encode_any_kernel<MODE_MAPPED, 1>), g, t, 0, s, a, w);
 #undef PSY_ANY_HP
     return (int)hipGetLastError();
 }
 
-int launch_decode_any(const DecodeArgs &a, uint32_t grid, hipStream_t s) {
-    hipLaunchKernelGGL(tdt_decode_any_kernel, dim3(grid ? grid : 1u), dim3(kAnyTeam), 0, s, a);
+int launch_decode_any(const DecodeArgs &a, uint32_t grid, hipStream_t s, bool pair) {
+    if (pair) hipLaunchKernelGGL(tdt_decode_any_kernel<true>, dim3(grid ? grid : 1u), dim3(kAnyTeam), 0, s, a);
+    else hipLaunchKernelGGL(tdt_decode_any_kernel<false>, dim3(grid ? grid : 1u), dim3(kAnyTeam), 0, s, a);
     return (int)hipGetLastError();
 }
 

@@ -32,9 +32,13 @@
 #if !defined(PSY_FAST_BUILD) && !(defined(PSY_PROF) && PSY_PROF) && !defined(PSY_SINGLE_TU)
 #define PSY_ENC_EXT(WS, T, G, M, L, TL, PS, PA) \
     extern template __global__ void psy::tdt_encode_kernel<WS, T, G, psy::M, L, TL, PS, PA>(psy::EncodeArgs);
-#define PSY_ENC_EXT_WS(WS)                 \
-    PSY_ENC_INSTANCES(PSY_ENC_EXT, WS)     \
-    extern template __global__ void psy::tdt_encode_lscan_kernel<WS>(psy::EncodeArgs, const uint32_t *, uint32_t);
+#define PSY_ENC_PAIR_EXT(WS, T, G, TL, PS, PA) \
+    extern template __global__ void psy::tdt_encode_kernel<WS, T, G, psy::MODE_ENCODE, 0, TL, PS, PA, true>(psy::EncodeArgs);
+#define PSY_ENC_EXT_WS(WS)                                                                                          \
+    PSY_ENC_INSTANCES(PSY_ENC_EXT, WS)                                                                              \
+    extern template __global__ void psy::tdt_encode_lscan_kernel<WS>(psy::EncodeArgs, const uint32_t *, uint32_t);  \
+    PSY_ENC_PAIR_INSTANCES(PSY_ENC_PAIR_EXT, WS)                                                                    \
+    extern template __global__ void psy::tdt_encode_lscan_kernel<WS, true>(psy::EncodeArgs, const uint32_t *, uint32_t);
 PSY_ENC_EXT_WS(1)
 PSY_ENC_EXT_WS(2)
 PSY_ENC_EXT_WS(4)
@@ -264,26 +268,26 @@ int ensure_ws(tdt_ctx *c, uint32_t n_msgs, hipStream_t s) {
 bool ws_supported(int ws) { return psy::anyws_tuned(ws) || (PSY_HAVE_ANYWS && psy::anyws_generic(ws)); }
 
 // the generic encode kernel (any word size in 1..64 the tuned kernels do not cover)
-int launch_any_encode(const psy::EncodeArgs &a, int ws, int mode, hipStream_t s) {
+int launch_any_encode(const psy::EncodeArgs &a, int ws, int mode, hipStream_t s, bool pair = false) {
 #if PSY_HAVE_ANYWS
     if (psy::anyws_generic(ws)) {
-        const int e = psy::launch_encode_any(a, ws, mode, s);
+        const int e = psy::launch_encode_any(a, ws, mode, s, pair);
         if (e) return set_err(TDT_E_HIP, std::string("generic encode launch: ") + hipGetErrorString((hipError_t)e));
         return TDT_OK;
     }
 #endif
-    (void)a, (void)mode, (void)s, (void)ws;
+    (void)a, (void)mode, (void)s, (void)ws, (void)pair;
     return set_err(TDT_E_UNSUPPORTED, "word_size not supported on the GPU path");
 }
 // the follow-up launch of a decode call: the blobs of a generic word size its kernels deferred
 // (grid: workgroups striding over the device-side list; any grid decodes every listed blob)
-int launch_any_decode(const psy::DecodeArgs &a, uint32_t grid, hipStream_t s) {
+int launch_any_decode(const psy::DecodeArgs &a, uint32_t grid, hipStream_t s, bool pair = false) {
 #if PSY_HAVE_ANYWS
     if (!a.dlist) return TDT_OK;
-    const int e = psy::launch_decode_any(a, std::max(1u, std::min(a.n_msgs, grid)), s);
+    const int e = psy::launch_decode_any(a, std::max(1u, std::min(a.n_msgs, grid)), s, pair);
     if (e) return set_err(TDT_E_HIP, std::string("generic decode launch: ") + hipGetErrorString((hipError_t)e));
 #else
-    (void)a, (void)grid, (void)s;
+    (void)a, (void)grid, (void)s, (void)pair;
 #endif
     return TDT_OK;
 }
@@ -335,15 +339,17 @@ __device__ __forceinline__ void lanes_copy_any(uint8_t *dst, const uint8_t *src,
     for (uint64_t k = head + 16 * nb + l; k < len; k += GL) dst[k] = src[k];
 }
 
-// encode: blob = "UNCP" + payload in the message's slot (slotted batches)
+// encode: blob = "UNCP" + payload in the message's slot (slotted batches; PAIR: a scattered batch's
+// pair tables, psy::table_at)
+template <bool PAIR = false>
 __global__ __launch_bounds__(256) void tdt_encode_copy_kernel(psy::EncodeArgs a) {
     const uint32_t n = __builtin_amdgcn_readfirstlane(*a.list_count);
     const uint32_t q = threadIdx.x >> 4, l = threadIdx.x & 15u;
     for (uint32_t i = blockIdx.x * 16u + q; i < n; i += gridDim.x * 16u) {
         const uint32_t msg = a.list[i];
-        const uint64_t off0 = a.in_off[msg], len = a.in_off[msg + 1] - off0;
-        const uint64_t sb = a.slot_off[msg], E = len + 4;
-        const bool fits = E <= a.slot_off[msg + 1] - sb;
+        const uint64_t off0 = a.in_off[psy::table_at<PAIR>(msg, 0)], len = a.in_off[psy::table_at<PAIR>(msg, 1)] - off0;
+        const uint64_t sb = a.slot_off[psy::table_at<PAIR>(msg, 0)], E = len + 4;
+        const bool fits = E <= a.slot_off[psy::table_at<PAIR>(msg, 1)] - sb;
         if (l == 0) {
             if (a.status) a.status[msg] = fits ? psy::ST_OK : psy::ST_CAPACITY;
             if (a.out_len) a.out_len[msg] = fits ? E : 0;
@@ -356,6 +362,7 @@ __global__ __launch_bounds__(256) void tdt_encode_copy_kernel(psy::EncodeArgs a)
 }
 
 // decode: payload of a UNCP blob into its slot
+template <bool PAIR = false>
 __global__ __launch_bounds__(256) void tdt_decode_copy_kernel(psy::DecodeArgs a) {
     const uint32_t n = __builtin_amdgcn_readfirstlane(*a.list_count);
     const uint32_t q = threadIdx.x >> 4, l = threadIdx.x & 15u;
@@ -363,8 +370,8 @@ __global__ __launch_bounds__(256) void tdt_decode_copy_kernel(psy::DecodeArgs a)
         const uint32_t msg = a.list[i];
         const uint64_t boff = a.in_off[msg];
         const uint64_t len = a.in_len ? a.in_len[msg] : a.in_off[msg + 1] - boff;  // >= 4 (the plan)
-        const uint64_t ob = a.slot_off[msg], osize = len - 4;
-        const bool fits = osize <= a.slot_off[msg + 1] - ob;
+        const uint64_t ob = a.slot_off[psy::table_at<PAIR>(msg, 0)], osize = len - 4;
+        const bool fits = osize <= a.slot_off[psy::table_at<PAIR>(msg, 1)] - ob;
         if (l == 0) {
             if (a.out_len) a.out_len[msg] = fits ? osize : 0;
             if (a.status) a.status[msg] = fits ? psy::ST_OK : psy::ST_CAPACITY;
@@ -414,8 +421,8 @@ uint32_t pow2_at_least(uint64_t x, uint32_t lo, uint32_t hi) {
     return (uint32_t)std::min<uint64_t>(p, hi);
 }
 
-int ensure_plan(PlanWS &w, uint32_t n, hipStream_t s) {
-    const size_t need = psy::plan_layout(n).bytes;
+int ensure_plan(PlanWS &w, uint32_t n, hipStream_t s, bool scattered = false) {
+    const size_t need = psy::plan_layout(n, scattered).bytes;
     if (need > w.bytes) {
         if (int st = no_growth_in_capture(s)) return st;
         if (w.buf) w.retired.push_back(w.buf);  // (a graph captured earlier may use it)
@@ -424,6 +431,59 @@ int ensure_plan(PlanWS &w, uint32_t n, hipStream_t s) {
         HIPCHK(hipMalloc(&w.buf, cap));
         w.bytes = cap;
     }
+    return TDT_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// Scattered batches (tdt_encode_batch_v / tdt_decode_batch_v): message i at ptr[i], size[i] bytes;
+// output i at out_ptr[i], capacity out_cap[i].  With null base pointers an address is an offset, so
+// the class kernels' PAIR instances read such a batch through (begin, end) pair tables (table_at,
+// tdt_plan.h) that one small kernel writes into the plan buffer in stream order.  It also sums the
+// sizes into a plan counter: the tiled-path threshold's "bytes of the batch", which no pointer
+// difference gives here.
+struct Scatter {
+    const uint64_t *ptr, *size;         // messages (encode) or blobs (decode)
+    const uint64_t *out_ptr, *out_cap;  // blobs (encode) or decoded messages (decode)
+};
+struct TableArgs {
+    Scatter v;
+    uint32_t n;
+    ulonglong2 *in_pair;        // null: no input table (decode reads ptr / size as in_off / in_len)
+    ulonglong2 *out_pair;
+    unsigned long long *bytes;  // += the sizes (zeroed with the plan's counters; null: no plan)
+};
+__global__ __launch_bounds__(256) void tdt_table_kernel(TableArgs t) {
+    __shared__ unsigned long long s_sum;
+    if (threadIdx.x == 0) s_sum = 0;
+    __syncthreads();
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    unsigned long long sz = 0;
+    if (i < t.n) {
+        sz = t.v.size[i];
+        if (t.in_pair) {
+            const uint64_t b = t.v.ptr[i];
+            t.in_pair[i] = make_ulonglong2(b, b + sz);
+        }
+        const uint64_t ob = t.v.out_ptr[i];
+        t.out_pair[i] = make_ulonglong2(ob, ob + t.v.out_cap[i]);
+    }
+    if (!t.bytes) return;  // (uniform)
+    for (int d = 32; d > 0; d >>= 1) sz += __shfl_down(sz, d, 64);
+    if ((threadIdx.x & 63u) == 0 && sz) atomicAdd(&s_sum, sz);
+    __syncthreads();
+    if (threadIdx.x == 0 && s_sum) atomicAdd(t.bytes, s_sum);
+}
+// the pair tables of a scattered call in plan buffer `pw` (ensure_plan(..., true) has made the room)
+int launch_table(PlanWS &pw, const Scatter &v, uint32_t n, bool in_table, unsigned long long *bytes,
+                 const uint64_t *&in_pair, const uint64_t *&out_pair, hipStream_t s) {
+    const psy::PlanLayout PL = psy::plan_layout(n, true);
+    if (pw.bytes < PL.bytes) return set_err(TDT_E_ARG, "plan buffer without room for the pair tables");
+    TableArgs t{v, n, in_table ? reinterpret_cast<ulonglong2 *>(pw.buf + PL.pair[psy::PT_IN]) : nullptr,
+                reinterpret_cast<ulonglong2 *>(pw.buf + PL.pair[psy::PT_OUT]), bytes};
+    hipLaunchKernelGGL(tdt_table_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, t);
+    HIPCHK(hipGetLastError());
+    in_pair = reinterpret_cast<const uint64_t *>(t.in_pair);
+    out_pair = reinterpret_cast<const uint64_t *>(t.out_pair);
     return TDT_OK;
 }
 
@@ -569,15 +629,17 @@ bool with_word_size(int ws, F &&f) {
     }
 }
 
-template <int WS>
-int launch_slotted(tdt_ctx *c, PlanWS &pw, psy::EncodeArgs a, hipStream_t s) {
+// PAIR: a scattered batch (`v`): its pair tables first, then the same classes through the PAIR instances
+template <int WS, bool PAIR = false>
+int launch_slotted(tdt_ctx *c, PlanWS &pw, psy::EncodeArgs a, hipStream_t s, const Scatter *v = nullptr) {
     using namespace psy;  // (counter, list and kernel names)
     const uint32_t n = a.n_msgs;
     // the list-entry prefetch of the slotted kernels (EncodeArgs::list) reads entry
     // min(i, n - 1) of a class list before its count: n >= 1, and every list holds n entries
     // (ensure_plan: five lists of n entries behind the counters)
     if (n == 0) return set_err(TDT_E_ARG, "slotted encode launch without messages");
-    int st = ensure_plan(pw, n, s);
+    if (PAIR != (v != nullptr)) return set_err(TDT_E_ARG, "scattered launch without its arrays");
+    int st = ensure_plan(pw, n, s, PAIR);
     if (st) return st;
     const PlanLayout PL = plan_layout(n);
     if (pw.bytes < PL.bytes) return set_err(TDT_E_ARG, "plan buffer smaller than five lists of n entries");
@@ -606,11 +668,13 @@ int launch_slotted(tdt_ctx *c, PlanWS &pw, psy::EncodeArgs a, hipStream_t s) {
     auto *tiles = reinterpret_cast<uint64_t *>(pw.elarge + EL.tiles);
     auto *spans = reinterpret_cast<uint64_t *>(pw.elarge + EL.spans);
     HIPCHK(hipMemsetAsync(cnt, 0, kPlanSnapBytes, s));
+    if constexpr (PAIR)  // the pair tables and the batch's byte count, then every kernel below as usual
+        if ((st = launch_table(pw, *v, n, true, cnt64 + EC_BYTES, a.in_off, a.slot_off, s))) return st;
     PlanArgs p{a.in, a.in_off, n, cnt64, list(EL_SMALL), list(EL_MEDIUM), list(EL_MID), list(EL_BIG), list(EL_COPY),
                tiles, spans, lmeta, lcap, tcap, kSmallMax, kMidMax, kBigMin, c->large_min, small_on ? 1u : 0u,
                mid_on ? 1u : 0u, a.min_tensor, (uint32_t)a.policy_on, (uint32_t)WS, copy_on ? 1u : 0u};
     const uint32_t per = kPlanThreads * kPlanPer;
-    hipLaunchKernelGGL(tdt_encode_plan_kernel, dim3((uint32_t)(((uint64_t)n + per - 1) / per)), dim3(kPlanThreads), 0, s,
+    hipLaunchKernelGGL(tdt_encode_plan_kernel<PAIR>, dim3((uint32_t)(((uint64_t)n + per - 1) / per)), dim3(kPlanThreads), 0, s,
                        p);
     HIPCHK(hipGetLastError());
     // (with tiles, the snapshot follows the map pass instead: it also holds the count pass's list length)
@@ -641,14 +705,14 @@ int launch_slotted(tdt_ctx *c, PlanWS &pw, psy::EncodeArgs a, hipStream_t s) {
         a.tcap = tcap;
         auto tile_pass = [&](auto TL, EncCount k, uint32_t bound) {  // (no main launch before any count is known)
             cls(nullptr, k, guess(H, k, bound, 0), bound, 512, ovf512, ts,
-                tdt_encode_kernel<WS, 512, 8, MODE_ENCODE, 0, TL(), 0>,
-                tdt_encode_kernel<WS, 512, 8, MODE_ENCODE, 0, TL(), 1>);
+                tdt_encode_kernel<WS, 512, 8, MODE_ENCODE, 0, TL(), 0, PATH_BOTH, PAIR>,
+                tdt_encode_kernel<WS, 512, 8, MODE_ENCODE, 0, TL(), 1, PATH_BOTH, PAIR>);
         };
         tile_pass(Int<1>{}, EC_SPANS, scap);  // span histograms (and counts under the speculated mapping)
         tile_pass(Int<4>{}, EC_LARGE, lcap);  // mapping per large message; lists the tiles to count again
         if (!capturing && (st = record_counts(H, cnt, n, ts))) return st;
         tile_pass(Int<2>{}, EC_RECOUNT, tcap);  // per-tile counts of the listed tiles
-        hipLaunchKernelGGL((tdt_encode_lscan_kernel<WS>), dim3(std::max(1u, std::min(lcap, 1024u))), dim3(64), 0, ts, a,
+        hipLaunchKernelGGL((tdt_encode_lscan_kernel<WS, PAIR>), dim3(std::max(1u, std::min(lcap, 1024u))), dim3(64), 0, ts, a,
                            cnt + lo32(EC_LARGE), lcap);
         tile_pass(Int<3>{}, EC_TILES, tcap);  // emit
     }
@@ -659,35 +723,44 @@ int launch_slotted(tdt_ctx *c, PlanWS &pw, psy::EncodeArgs a, hipStream_t s) {
     // is empty); the big list has no main launch when the history says it is empty
     a.list2 = nullptr;
     cls(list(EL_BIG), EC_BIG, H.valid && !H[EC_BIG] ? 0u : guess(H, EC_BIG, n, n), n, 512, ovf512, s,
-        tdt_encode_kernel<WS, 512, 8, MODE_ENCODE, 0, 0, 0, PATH_STREAM>,
-        tdt_encode_kernel<WS, 512, 8, MODE_ENCODE, 0, 0, 1, PATH_STREAM>);
+        tdt_encode_kernel<WS, 512, 8, MODE_ENCODE, 0, 0, 0, PATH_STREAM, PAIR>,
+        tdt_encode_kernel<WS, 512, 8, MODE_ENCODE, 0, 0, 1, PATH_STREAM, PAIR>);
     cls(list(EL_MEDIUM), EC_MEDIUM, guess(H, EC_MEDIUM, n, n), n, 512, ovf512, s,
-        tdt_encode_kernel<WS, 512, 8, MODE_ENCODE, 0, 0, 0, PATH_RES>,
-        tdt_encode_kernel<WS, 512, 8, MODE_ENCODE, 0, 0, 1, PATH_RES>);
+        tdt_encode_kernel<WS, 512, 8, MODE_ENCODE, 0, 0, 0, PATH_RES, PAIR>,
+        tdt_encode_kernel<WS, 512, 8, MODE_ENCODE, 0, 0, 1, PATH_RES, PAIR>);
     // the small, copy and mid-sized lists behind the tile pipeline on the side stream (the two
     // streams' loads balance better: C4's tile pipeline is shorter than its medium list)
     const hipStream_t ss = forked && !c->small_main ? pw.side : s;
     if (small_on)  // one-wave teams
         cls(list(EL_SMALL), EC_SMALL, guess(H, EC_SMALL, n, n), n, 64, ovf64, ss,
-            tdt_encode_kernel<WS, 64, 4, MODE_ENCODE, 0, 0, 0>, tdt_encode_kernel<WS, 64, 4, MODE_ENCODE, 0, 0, 1>);
+            tdt_encode_kernel<WS, 64, 4, MODE_ENCODE, 0, 0, 0, PATH_BOTH, PAIR>,
+            tdt_encode_kernel<WS, 64, 4, MODE_ENCODE, 0, 0, 1, PATH_BOTH, PAIR>);
     if (copy_on) {  // passthrough copies
         a.list = list(EL_COPY);
         a.list_count = cnt + lo32(EC_UNCP);
-        hipLaunchKernelGGL(tdt_encode_copy_kernel, dim3(std::max(1u, std::min((uint32_t)c->cus * c->copy_wgs, (n + 15) / 16))),
+        hipLaunchKernelGGL(tdt_encode_copy_kernel<PAIR>, dim3(std::max(1u, std::min((uint32_t)c->cus * c->copy_wgs, (n + 15) / 16))),
                            dim3(256), 0, ss, a);
     }
     if (mid_on)  // 256-lane teams
         cls(list(EL_MID), EC_MID, guess(H, EC_MID, n, n), n, 256, ovf256, ss,
-            tdt_encode_kernel<WS, 256, 8, MODE_ENCODE, 0, 0, 0>, tdt_encode_kernel<WS, 256, 8, MODE_ENCODE, 0, 0, 1>);
+            tdt_encode_kernel<WS, 256, 8, MODE_ENCODE, 0, 0, 0, PATH_BOTH, PAIR>,
+            tdt_encode_kernel<WS, 256, 8, MODE_ENCODE, 0, 0, 1, PATH_BOTH, PAIR>);
     if (forked) return join_side(pw, s);
     return TDT_OK;
 }
 
-int launch_slotted_any(tdt_ctx *c, PlanWS &pw, psy::EncodeArgs a, hipStream_t s) {
+int launch_slotted_any(tdt_ctx *c, PlanWS &pw, psy::EncodeArgs a, hipStream_t s, const Scatter *v = nullptr) {
     int st = TDT_OK;
-    if (with_word_size(c->cfg.word_size, [&](auto W) { st = launch_slotted<W()>(c, pw, a, s); })) return st;
+    if (with_word_size(c->cfg.word_size, [&](auto W) {
+            st = v ? launch_slotted<W(), true>(c, pw, a, s, v) : launch_slotted<W()>(c, pw, a, s);
+        }))
+        return st;
     // generic widths: one workgroup per message, message id = block index, no plan
-    return launch_any_encode(a, c->cfg.word_size, psy::MODE_ENCODE, s);
+    if (v && psy::anyws_generic(c->cfg.word_size)) {  // (the plan buffer holds the pair tables alone)
+        if ((st = ensure_plan(pw, a.n_msgs, s, true))) return st;
+        if ((st = launch_table(pw, *v, a.n_msgs, true, nullptr, a.in_off, a.slot_off, s))) return st;
+    }
+    return launch_any_encode(a, c->cfg.word_size, psy::MODE_ENCODE, s, v != nullptr);
 }
 
 // messages > 4 KiB: TEAM threads per message, G resident rounds per wave (64 KiB resident)
@@ -760,12 +833,13 @@ int encode_common(tdt_ctx *c, int mode, const uint8_t *d_in, const uint64_t *d_i
                   const int32_t *d_mapping, uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_off,
                   int32_t *d_status, uint32_t *d_hist, double *d_ent, int32_t *d_map, void *stream,
                   const uint64_t *d_slot_off = nullptr, uint64_t *d_out_len = nullptr, uint8_t *wsp = nullptr,
-                  PlanWS *pws = nullptr, int small_teams = -1) {
+                  PlanWS *pws = nullptr, int small_teams = -1, const Scatter *v = nullptr) {
     if (!c) return set_err(TDT_E_ARG, "null context");
     if (n_msgs == 0) return TDT_OK;
-    if (!d_in_off) return set_err(TDT_E_ARG, "null input offsets");  // d_in may be null: all-empty batch
-    const bool slotted = d_slot_off != nullptr;
-    if (mode != psy::MODE_ANALYZE && (!d_out || (!slotted && !d_out_off))) return set_err(TDT_E_ARG, "null output");
+    if (v && !(v->ptr && v->size && v->out_ptr && v->out_cap)) return set_err(TDT_E_ARG, "null pointer or size array");
+    if (!v && !d_in_off) return set_err(TDT_E_ARG, "null input offsets");  // d_in may be null: all-empty batch
+    const bool slotted = d_slot_off != nullptr || v;  // (a scattered batch: d_in, d_out and the offsets are null)
+    if (!v && mode != psy::MODE_ANALYZE && (!d_out || (!slotted && !d_out_off))) return set_err(TDT_E_ARG, "null output");
     if (mode == psy::MODE_MAPPED && !d_mapping) return set_err(TDT_E_ARG, "null mapping");
     hipStream_t s = (hipStream_t)stream;
     std::unique_lock<std::mutex> lk(c->mu, std::defer_lock);
@@ -792,7 +866,7 @@ int encode_common(tdt_ctx *c, int mode, const uint8_t *d_in, const uint64_t *d_i
     a.slot_off = d_slot_off;
     a.out_len = d_out_len;
     if (mode == psy::MODE_ENCODE) {
-        st = slotted ? launch_slotted_any(c, pws ? *pws : c->pw, a, s)
+        st = slotted ? launch_slotted_any(c, pws ? *pws : c->pw, a, s, v)
                      : launch_encode<psy::MODE_ENCODE, 1>(c, a, s, small_teams);
     } else if (mode == psy::MODE_MAPPED) {
         st = launch_encode<psy::MODE_MAPPED, 1>(c, a, s, small_teams);
@@ -840,10 +914,13 @@ int ensure_dlarge(PlanWS &w) {
     return TDT_OK;
 }
 
-int launch_decode_slotted(tdt_ctx *c, PlanWS &pw, psy::DecodeArgs a, hipStream_t s) {
+// PAIR: a scattered batch (`v`): its slot table first, then the same classes through the PAIR instances
+template <bool PAIR = false>
+int launch_decode_slotted(tdt_ctx *c, PlanWS &pw, psy::DecodeArgs a, hipStream_t s, const Scatter *v = nullptr) {
     using namespace psy;  // (counter, list and kernel names)
     const uint32_t n = a.n_msgs;
-    int st = ensure_plan(pw, n, s);
+    if (PAIR != (v != nullptr)) return set_err(TDT_E_ARG, "scattered launch without its arrays");
+    int st = ensure_plan(pw, n, s, PAIR);
     if (st) return st;
     const bool capturing = ::capturing(s);
     auto &H = pw.dh;
@@ -872,9 +949,13 @@ int launch_decode_slotted(tdt_ctx *c, PlanWS &pw, psy::DecodeArgs a, hipStream_t
     auto *bent = reinterpret_cast<uint32_t *>(pw.dlarge + DL.bent);
     auto *tent = reinterpret_cast<uint32_t *>(pw.dlarge + DL.tent);
     HIPCHK(hipMemsetAsync(cnt, 0, kPlanSnapBytes, s));
+    if constexpr (PAIR) {  // the blobs through in_off / in_len as they are, the slots through a pair table
+        const uint64_t *none = nullptr;
+        if ((st = launch_table(pw, *v, n, false, cnt + DC_BYTES, none, a.slot_off, s))) return st;
+    }
     DPlanArgs p{a.in, a.in_off, a.in_len, n, cnt, list(DL_MAIN), list(DL_SMALL), c->dsmall_max, list(DL_BIG), c->dbig_min,
                 list(DL_COPY), a.dmeta, bent, tent, lcap, bcap, tcap, c->large_min, small_on ? 1u : 0u, copy_on ? 1u : 0u};
-    hipLaunchKernelGGL(tdt_decode_plan_kernel, dim3((uint32_t)(((uint64_t)n + 4095) / 4096)), dim3(1024), 0, s, p);
+    hipLaunchKernelGGL(tdt_decode_plan_kernel<PAIR>, dim3((uint32_t)(((uint64_t)n + 4095) / 4096)), dim3(1024), 0, s, p);
     HIPCHK(hipGetLastError());
     if (!capturing && (st = record_counts(H, cnt, n, s))) return st;
     a.bent = bent;
@@ -900,7 +981,7 @@ int launch_decode_slotted(tdt_ctx *c, PlanWS &pw, psy::DecodeArgs a, hipStream_t
     }
     if (large_on) {
         const uint32_t gl = std::max(1u, std::min(lcap, 1024u));
-        hipLaunchKernelGGL(tdt_decode_lprep_kernel, dim3(gl), dim3(256), 0, ts, a);
+        hipLaunchKernelGGL(tdt_decode_lprep_kernel<PAIR>, dim3(gl), dim3(256), 0, ts, a);
         hipLaunchKernelGGL(tdt_decode_lblock_kernel, dim3(std::max(1u, std::min((bcap + 3) / 4, ovf / 4))), dim3(256), 0,
                            ts, a);
         hipLaunchKernelGGL(tdt_decode_lscan_kernel, dim3(gl, 2), dim3(64), 0, ts, a);
@@ -912,35 +993,37 @@ int launch_decode_slotted(tdt_ctx *c, PlanWS &pw, psy::DecodeArgs a, hipStream_t
     a.blist = list(DL_BIG);
     a.blist_count = cnt32 + lo32(DC_BIG);
     cls(list(DL_MAIN), DC_MAIN, (uint32_t)std::min<uint64_t>(n, (uint64_t)guess(H, DC_MAIN, n, n) + guess(H, DC_BIG, n, n)),
-        n, 64, ovf, s, tdt_decode_kernel<0, kDecWR, 0>, tdt_decode_kernel<0, kDecWR, 1>);
+        n, 64, ovf, s, tdt_decode_kernel<0, kDecWR, 0, PAIR>, tdt_decode_kernel<0, kDecWR, 1, PAIR>);
     a.blist = nullptr;
     const hipStream_t ss = forked && !c->small_main ? pw.side : s;
     // passthrough copies beside the main list
     if (copy_on) {
         a.list = list(DL_COPY);
         a.list_count = cnt32 + lo32(DC_UNCP);
-        hipLaunchKernelGGL(tdt_decode_copy_kernel, dim3(std::max(1u, std::min((uint32_t)c->cus * c->copy_wgs, (n + 15) / 16))),
+        hipLaunchKernelGGL(tdt_decode_copy_kernel<PAIR>, dim3(std::max(1u, std::min((uint32_t)c->cus * c->copy_wgs, (n + 15) / 16))),
                            dim3(256), 0, ss, a);
     }
     // small blobs: one-round windows (a third less LDS per wave: more blobs in flight per CU)
     if (small_on)
-        cls(list(DL_SMALL), DC_SMALL, guess(H, DC_SMALL, n, n), n, 64, ovf, ss, tdt_decode_kernel<0, 1, 0>,
-            tdt_decode_kernel<0, 1, 1>);
+        cls(list(DL_SMALL), DC_SMALL, guess(H, DC_SMALL, n, n), n, 64, ovf, ss, tdt_decode_kernel<0, 1, 0, PAIR>,
+            tdt_decode_kernel<0, 1, 1, PAIR>);
     if (forked && (st = join_side(pw, s))) return st;
     // the deferred blobs (generic word sizes): near-empty when no kernel above listed one.  (A
     // fixed grid: the plan's count snapshot is taken before the class kernels append to the list,
     // so the history cannot size it — 64 workgroups for 4,096 listed blobs ran at a twelfth of the rate.)
-    return launch_any_decode(a, (uint32_t)c->cus * 4u, s);
+    return launch_any_decode(a, (uint32_t)c->cus * 4u, s, PAIR);
 }
 
 int decode_common(tdt_ctx *c, bool sizes_only, const uint8_t *d_in, const uint64_t *d_in_off, uint32_t n_msgs,
                   uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_off, uint64_t *d_sizes, int32_t *d_status,
                   void *stream, const uint64_t *d_slot_off = nullptr, uint64_t *d_out_len = nullptr,
-                  const uint64_t *d_in_len = nullptr, uint8_t *wsp = nullptr, PlanWS *pws = nullptr) {
+                  const uint64_t *d_in_len = nullptr, uint8_t *wsp = nullptr, PlanWS *pws = nullptr,
+                  const Scatter *v = nullptr) {
     if (!c) return set_err(TDT_E_ARG, "null context");
     if (n_msgs == 0) return TDT_OK;
+    if (v && !(v->ptr && v->size && v->out_ptr && v->out_cap)) return set_err(TDT_E_ARG, "null pointer or size array");
     if (!d_in_off) return set_err(TDT_E_ARG, "null input offsets");
-    const bool slotted = d_slot_off != nullptr;
+    const bool slotted = d_slot_off != nullptr || v;  // (a scattered batch: d_in_off / d_in_len are its blobs)
     if (!sizes_only && !slotted && !d_out_off) return set_err(TDT_E_ARG, "null output offsets");
     if (sizes_only && !d_sizes) return set_err(TDT_E_ARG, "null sizes");
     hipStream_t s = (hipStream_t)stream;
@@ -966,7 +1049,8 @@ int decode_common(tdt_ctx *c, bool sizes_only, const uint8_t *d_in, const uint64
     if (sizes_only) {
         hipLaunchKernelGGL(psy::tdt_decode_sizes_kernel, dim3((n_msgs + 255) / 256), dim3(256), 0, s, a);
     } else if (slotted) {
-        st = launch_decode_slotted(c, pws ? *pws : c->pw, a, s);
+        st = v ? launch_decode_slotted<true>(c, pws ? *pws : c->pw, a, s, v)
+               : launch_decode_slotted(c, pws ? *pws : c->pw, a, s);
         if (st) return st;
     } else {
 #if PSY_HAVE_ANYWS
@@ -2174,6 +2258,33 @@ int tdt_decode_batch_into(tdt_ctx *ctx, const uint8_t *d_in, const uint64_t *d_i
     if (n_msgs && !d_slot_off) return set_err(TDT_E_ARG, "null slot offsets");
     return decode_common(ctx, false, d_in, d_in_off, n_msgs, d_out, 0, nullptr, nullptr, d_status, stream, d_slot_off,
                          d_out_len, d_in_len);
+}
+
+int tdt_encode_batch_v(tdt_ctx *ctx, const uint8_t *const *d_msgs, const uint64_t *d_sizes, uint32_t n_msgs,
+                       uint8_t *const *d_blobs, const uint64_t *d_blob_cap, uint64_t *d_out_len, int32_t *d_status,
+                       void *stream) {
+    // (device addresses are 64 bits wide: a pointer table read as u64 is the offset table of a null base)
+    static_assert(sizeof(uint8_t *) == sizeof(uint64_t), "pointer tables are read as u64 offsets");
+    const Scatter v{reinterpret_cast<const uint64_t *>(d_msgs), d_sizes, reinterpret_cast<const uint64_t *>(d_blobs),
+                    d_blob_cap};
+    return encode_common(ctx, psy::MODE_ENCODE, nullptr, nullptr, n_msgs, nullptr, nullptr, 0, nullptr, d_status, nullptr,
+                         nullptr, nullptr, stream, nullptr, d_out_len, nullptr, nullptr, -1, &v);
+}
+
+int tdt_decode_batch_v(tdt_ctx *ctx, const uint8_t *const *d_blobs, const uint64_t *d_blob_len, uint32_t n_msgs,
+                       uint8_t *const *d_outs, const uint64_t *d_out_cap, uint64_t *d_out_len, int32_t *d_status,
+                       void *stream) {
+    const Scatter v{reinterpret_cast<const uint64_t *>(d_blobs), d_blob_len, reinterpret_cast<const uint64_t *>(d_outs),
+                    d_out_cap};
+    return decode_common(ctx, false, nullptr, v.ptr, n_msgs, nullptr, 0, nullptr, nullptr, d_status, stream, nullptr,
+                         d_out_len, d_blob_len, nullptr, nullptr, &v);
+}
+
+int tdt_decoded_sizes_v(tdt_ctx *ctx, const uint8_t *const *d_blobs, const uint64_t *d_blob_len, uint32_t n_msgs,
+                        uint64_t *d_sizes, int32_t *d_status, void *stream) {
+    if (n_msgs && !d_blob_len) return set_err(TDT_E_ARG, "null blob lengths");
+    return decode_common(ctx, true, nullptr, reinterpret_cast<const uint64_t *>(d_blobs), n_msgs, nullptr, 0, nullptr,
+                         d_sizes, d_status, stream, nullptr, nullptr, d_blob_len);
 }
 
 int tdt_encode_slots(tdt_ctx *ctx, const uint64_t *d_in_off, uint32_t n_msgs, uint64_t *d_slot_off, void *stream) {

@@ -930,8 +930,10 @@ __device__ __forceinline__ FastHdr parse_fast(const uint8_t *blob, uint64_t len,
     return h;
 }
 
-// One blob, one wave (LB: compacted output by look-back; else its slot).
-template <int LB, int WR = kDecWR>
+// One blob, one wave (LB: compacted output by look-back; else its slot).  PAIR: slot_off is a
+// (begin, end) pair table (table_at, tdt_plan.h) — the instances of the scattered batches
+// (tdt_decode_batch_v: in and out are null, in_off holds the blobs' addresses beside in_len).
+template <int LB, int WR = kDecWR, bool PAIR = false>
 __device__ __forceinline__ void decode_one(const DecodeArgs &a, uint8_t *smem, uint32_t msg) {
     using Lay = DecLayoutT<WR>;
     uint32_t *misc = reinterpret_cast<uint32_t *>(smem + Lay::OFF_MISC);
@@ -944,8 +946,8 @@ __device__ __forceinline__ void decode_one(const DecodeArgs &a, uint8_t *smem, u
     // the slot is read beside the offsets (it depends on msg only): one dependent trip fewer
     uint64_t slot_b = 0, slot_e = 0;
     if constexpr (!LB) {
-        slot_b = a.slot_off[msg];
-        slot_e = a.slot_off[msg + 1];
+        slot_b = a.slot_off[table_at<PAIR>(msg, 0)];
+        slot_e = a.slot_off[table_at<PAIR>(msg, 1)];
     }
     const uint8_t *blob = a.in + boff;
     const uint8_t *blim = blob + len;
@@ -1433,6 +1435,8 @@ struct DPlanArgs {
 };
 
 #ifndef PSY_DEC_INST_TU
+// PAIR: a scattered batch, whose bytes are counter DC_BYTES (the table kernel's sum)
+template <bool PAIR = false>
 __global__ __launch_bounds__(1024) void tdt_decode_plan_kernel(DPlanArgs p) {
     __shared__ uint64_t lds[6 * (4 * 16 + 1)];
     // one wave per blob keeps the chip busy while a blob is at most ~1/4096 of the batch's
@@ -1440,7 +1444,7 @@ __global__ __launch_bounds__(1024) void tdt_decode_plan_kernel(DPlanArgs p) {
     uint64_t thr = p.large_min;
     if (p.n_msgs) {
         const uint64_t last = p.in_len ? p.in_off[p.n_msgs - 1] + p.in_len[p.n_msgs - 1] : p.in_off[p.n_msgs];
-        const uint64_t share = (last - p.in_off[0]) / 4096;
+        const uint64_t share = (PAIR ? p.cnt[DC_BYTES] : last - p.in_off[0]) / 4096;
         thr = share > thr ? share : thr;
     }
     // the claims' values (A: large blobs, tiles, block slots; B: the lists) and their starts
@@ -1541,6 +1545,7 @@ __global__ __launch_bounds__(1024) void tdt_decode_plan_kernel(DPlanArgs p) {
 
 // Prep: one workgroup per large blob; wave 0 parses and places it, then every thread writes
 // its block-slot and tile entries (kNone where no pass has work).
+template <bool PAIR = false>
 __global__ __launch_bounds__(256) void tdt_decode_lprep_kernel(DecodeArgs a) {
     __shared__ __attribute__((aligned(16))) uint8_t smem[DecLayout::BYTES];
     __shared__ uint32_t s_tiled, s_fast;
@@ -1570,8 +1575,8 @@ __global__ __launch_bounds__(256) void tdt_decode_lprep_kernel(DecodeArgs a) {
         const FastHdr H = parse_fast(blob, len, hdrc, hcl);
         uint32_t tiled = 0, fast = 0;
         if (H.kind != 0) {
-            const uint64_t ob = a.slot_off[msg];
-            const bool fits = H.osize <= a.slot_off[msg + 1] - ob;
+            const uint64_t ob = a.slot_off[table_at<PAIR>(msg, 0)];
+            const bool fits = H.osize <= a.slot_off[table_at<PAIR>(msg, 1)] - ob;
             if (lane == 0) {
                 if (a.out_len) a.out_len[msg] = fits ? H.osize : 0;
                 if (a.status) a.status[msg] = fits ? ST_OK : ST_CAPACITY;
@@ -1591,7 +1596,7 @@ __global__ __launch_bounds__(256) void tdt_decode_lprep_kernel(DecodeArgs a) {
                 }
             }
         } else {
-            decode_one<0>(a, smem, msg);  // any other shape (or an error): one wave, whole
+            decode_one<0, kDecWR, PAIR>(a, smem, msg);  // any other shape (or an error): one wave, whole
         }
         if (lane == 0) {
             m->tiled = tiled;
@@ -1842,13 +1847,14 @@ __global__ __launch_bounds__(64 * NW) void tdt_decode_one_kernel(DecodeArgs a) {
 // them from the plan's list (or, without one, the workgroup id).
 // List entries are bounded by the plan's device-side count (main launch: one blob per wave over
 // [list_base, list_base + grid); overflow launch, PS = 1: the entries past it, grid-stride).
-template <int LB, int WR = kDecWR, int PS = 0>
+template <int LB, int WR = kDecWR, int PS = 0, bool PAIR = false>
 __global__ __launch_bounds__(64, LB ? 6 : 8) void tdt_decode_kernel(DecodeArgs a) {
+    static_assert(!PAIR || !LB, "scattered batches are slotted");
     __shared__ __attribute__((aligned(16))) uint8_t smem[DecLayoutT<WR>::BYTES];
     if constexpr (LB) {
         uint32_t t = 0;
         if (lane_id() == 0) t = atomicAdd(a.ticket, 1u);
-        decode_one<LB, WR>(a, smem, __builtin_amdgcn_readfirstlane(t));
+        decode_one<LB, WR, PAIR>(a, smem, __builtin_amdgcn_readfirstlane(t));
     } else {
         // (slotted launches always pass the plan's list; the main list's big blobs come first)
         const uint32_t nb = a.blist ? __builtin_amdgcn_readfirstlane(*a.blist_count) : 0u;
@@ -1858,7 +1864,7 @@ __global__ __launch_bounds__(64, LB ? 6 : 8) void tdt_decode_kernel(DecodeArgs a
         if constexpr (PS) {
             for (uint32_t i = i0; i < cnt; i += gridDim.x) {
                 if (i != i0) team_sync<1>();
-                decode_one<LB, WR>(a, smem, entry(i));
+                decode_one<LB, WR, PAIR>(a, smem, entry(i));
             }
         } else {
             // the list entries are read beside the counts, not after them (i0 < n_msgs = every
@@ -1866,7 +1872,7 @@ __global__ __launch_bounds__(64, LB ? 6 : 8) void tdt_decode_kernel(DecodeArgs a
             const uint32_t ic = i0 < a.n_msgs ? i0 : a.n_msgs - 1u;
             const uint32_t eb = a.blist ? a.blist[ic] : 0u, el = a.list[ic];
             if (i0 >= cnt) return;
-            decode_one<LB, WR>(a, smem, i0 < nb ? eb : (nb == 0u ? el : a.list[i0 - nb]));
+            decode_one<LB, WR, PAIR>(a, smem, i0 < nb ? eb : (nb == 0u ? el : a.list[i0 - nb]));
         }
     }
 }

@@ -14,3 +14,7 @@
     template __global__ void psy::tdt_encode_kernel<WS, T, G, psy::M, L, TL, PS, PA>(psy::EncodeArgs);
 PSY_ENC_INSTANCES(PSY_ENC_DEF, PSY_INST_WS)
 template __global__ void psy::tdt_encode_lscan_kernel<PSY_INST_WS>(psy::EncodeArgs, const uint32_t *, uint32_t);
+#define PSY_ENC_PAIR_DEF(WS, T, G, TL, PS, PA) \
+    template __global__ void psy::tdt_encode_kernel<WS, T, G, psy::MODE_ENCODE, 0, TL, PS, PA, true>(psy::EncodeArgs);
+PSY_ENC_PAIR_INSTANCES(PSY_ENC_PAIR_DEF, PSY_INST_WS)
+template __global__ void psy::tdt_encode_lscan_kernel<PSY_INST_WS, true>(psy::EncodeArgs, const uint32_t *, uint32_t);

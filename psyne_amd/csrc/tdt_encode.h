@@ -381,7 +381,9 @@ enum { PATH_BOTH = 0, PATH_RES = 1, PATH_STREAM = 2 };
 
 // CARM: the resident body also holds the post-mapping passes compiled for the speculated mapping's
 // slot layout as constants (the "constant arm"), taken when the message's mapping is that one.
-template <int WS, int TEAM, int G, int MODE, int LB, int TL, int PATH = PATH_BOTH, bool CARM = false>
+// PAIR: in_off and slot_off are (begin, end) pair tables (table_at, tdt_plan.h) — the instances of
+// the scattered batches (tdt_encode_batch_v: in and out are null, the pairs are addresses).
+template <int WS, int TEAM, int G, int MODE, int LB, int TL, int PATH = PATH_BOTH, bool CARM = false, bool PAIR = false>
 __device__ __forceinline__ void encode_one(const EncodeArgs &a, uint8_t *smem, uint32_t msg, uint32_t lj,
                                            uint32_t tile) {
     static_assert(TL == 0 || (TEAM * G == (int)kTileGroups && MODE == MODE_ENCODE && !LB), "tile shape");
@@ -401,16 +403,16 @@ __device__ __forceinline__ void encode_one(const EncodeArgs &a, uint8_t *smem, u
     if (msg >= a.n_msgs) return;
     PSY_PROF_MARK(0);
 
-    const uint64_t off0 = a.in_off[msg];
-    const uint64_t n = a.in_off[msg + 1] - off0;
+    const uint64_t off0 = a.in_off[table_at<PAIR>(msg, 0)];
+    const uint64_t n = a.in_off[table_at<PAIR>(msg, 1)] - off0;
     const uint8_t *base = a.in + off0;
     // slotted outputs: the slot is known now; loading it here keeps its latency off the
     // critical path between the count pass and the emit pass (round 6: loaded at its first use
     // instead, the C3 encode took 8.2-8.7 ms against 7.26)
     uint64_t slot_b = 0, slot_e = 0;
     if constexpr (!LB) {
-        slot_b = a.slot_off[msg];
-        slot_e = a.slot_off[msg + 1];
+        slot_b = a.slot_off[table_at<PAIR>(msg, 0)];
+        slot_e = a.slot_off[table_at<PAIR>(msg, 1)];
     }
 
     // Output placement of an E-byte result (all threads call it): returns the offset in
@@ -2178,8 +2180,9 @@ __device__ __forceinline__ uint32_t entry_count(const EncodeArgs &a) {
     return __builtin_amdgcn_readfirstlane(c);
 }
 
-template <int WS, int TEAM, int G, int MODE, int LB, int TL = 0, int PS = 0, int PATH = PATH_BOTH>
+template <int WS, int TEAM, int G, int MODE, int LB, int TL = 0, int PS = 0, int PATH = PATH_BOTH, bool PAIR = false>
 __global__ __launch_bounds__(TEAM, PSY_ENC_WAVES(TEAM, LB)) void tdt_encode_kernel(EncodeArgs a) {
+    static_assert(!PAIR || (!LB && MODE == MODE_ENCODE), "scattered batches are slotted encodes");
     using Lay = EncLayout<WS, TEAM, LB>;
     constexpr int W = Lay::W;
     __shared__ __attribute__((aligned(16))) uint8_t smem[Lay::BYTES];
@@ -2194,15 +2197,16 @@ __global__ __launch_bounds__(TEAM, PSY_ENC_WAVES(TEAM, LB)) void tdt_encode_kern
         const uint32_t n2 = TL == 0 && a.list2 ? __builtin_amdgcn_readfirstlane(*a.list2_count) : 0u;
         auto one = [&](uint32_t i) __attribute__((always_inline)) {
             if constexpr (TL == 0) {
-                encode_one<WS, TEAM, G, MODE, LB, 0, PATH>(a, smem, i < n2 ? a.list2[i] : a.list[i - n2], 0, 0);
+                encode_one<WS, TEAM, G, MODE, LB, 0, PATH, false, PAIR>(a, smem, i < n2 ? a.list2[i] : a.list[i - n2], 0, 0);
             } else if constexpr (TL == 4) {
                 const uint32_t msg = a.lmeta[i].msg;  // one large message per workgroup
-                if (msg != kNone) encode_one<WS, TEAM, G, MODE, LB, TL>(a, smem, msg, i, 0);
+                if (msg != kNone) encode_one<WS, TEAM, G, MODE, LB, TL, PATH_BOTH, false, PAIR>(a, smem, msg, i, 0);
             } else {
                 const uint64_t e = TL == 1 ? a.spans[i] : TL == 2 ? a.rtiles[i] : a.tiles[i];  // a span or tile
                 const uint32_t lj = (uint32_t)e;
                 if (lj == kNone) return;  // a message that did not fit the budgets
-                encode_one<WS, TEAM, G, MODE, LB, TL>(a, smem, a.lmeta[lj].msg, lj, (uint32_t)(e >> 32));
+                encode_one<WS, TEAM, G, MODE, LB, TL, PATH_BOTH, false, PAIR>(a, smem, a.lmeta[lj].msg, lj,
+                                                                              (uint32_t)(e >> 32));
             }
         };
         const uint32_t cnt = entry_count<TL>(a);
@@ -2221,8 +2225,8 @@ __global__ __launch_bounds__(TEAM, PSY_ENC_WAVES(TEAM, LB)) void tdt_encode_kern
             // the slotted main instance of the medium list holds the constant arm (word size 4:
             // float tensors; the other instances stay generic — code size and build time)
             constexpr bool CARM = PSY_ENC_DUAL && WS == 4 && TEAM == 512 && PATH == PATH_RES && MODE == MODE_ENCODE;
-            encode_one<WS, TEAM, G, MODE, LB, 0, PATH, CARM>(a, smem, i0 < n2 ? e2 : (n2 == 0u ? e1 : a.list[i0 - n2]),
-                                                             0, 0);
+            encode_one<WS, TEAM, G, MODE, LB, 0, PATH, CARM, PAIR>(a, smem,
+                                                                   i0 < n2 ? e2 : (n2 == 0u ? e1 : a.list[i0 - n2]), 0, 0);
         } else {
             if (i0 >= cnt) return;
             one(i0);
@@ -2260,6 +2264,8 @@ struct PlanArgs {
 constexpr uint32_t kPlanThreads = 1024, kPlanPer = 2;  // messages per plan workgroup: 2048
 
 #ifndef PSY_ENC_INST_TU  // (defined once, in tdt_api.hip)
+// PAIR: in_off is a pair table, and the batch's bytes are counter EC_BYTES (the table kernel's sum)
+template <bool PAIR = false>
 __global__ __launch_bounds__(kPlanThreads) void tdt_encode_plan_kernel(PlanArgs p) {
     __shared__ uint64_t lds[8 * (kPlanPer * 16 + 1)];
     const uint32_t scap = p.tile_cap / kSpanTiles;
@@ -2270,7 +2276,7 @@ __global__ __launch_bounds__(kPlanThreads) void tdt_encode_plan_kernel(PlanArgs 
     // messages in 24.6 GiB) encode 19.7 -> 18.8 ms with none of its messages tiled.
     uint64_t thr = p.large_min;
     if (p.n_msgs) {
-        const uint64_t share = (p.in_off[p.n_msgs] - p.in_off[0]) / 4096;
+        const uint64_t share = (PAIR ? p.cnt[EC_BYTES] : p.in_off[p.n_msgs] - p.in_off[0]) / 4096;
         thr = share > thr ? share : thr;
     }
     // the claims' values (A: large messages, tiles, spans; B: the lists) and their starts
@@ -2281,7 +2287,7 @@ __global__ __launch_bounds__(kPlanThreads) void tdt_encode_plan_kernel(PlanArgs 
 #pragma unroll
     for (int k = 0; k < (int)kPlanPer; ++k) {
         const uint32_t i = (blockIdx.x * kPlanPer + k) * kPlanThreads + threadIdx.x;
-        n[k] = i < p.n_msgs ? p.in_off[i + 1] - p.in_off[i] : 0;
+        n[k] = i < p.n_msgs ? p.in_off[table_at<PAIR>(i, 1)] - p.in_off[table_at<PAIR>(i, 0)] : 0;
         isl[k] = i < p.n_msgs && n[k] > thr ? 1u : 0u;
         T[k] = isl[k] ? (n[k] + 16ull * kTileGroups - 1) / (16ull * kTileGroups) : 0;
         S[k] = (T[k] + kSpanTiles - 1) / kSpanTiles;
@@ -2331,7 +2337,7 @@ __global__ __launch_bounds__(kPlanThreads) void tdt_encode_plan_kernel(PlanArgs 
         // the medium list's kernel holds only the resident body: longer or unaligned messages
         // (and those of size not a multiple of 16) take the big list's streaming kernel
         const bool res_ok = n[k] <= p.big_min && (n[k] & 15u) == 0 &&
-                            (((uintptr_t)p.in + (valid ? p.in_off[i] : 0ull)) & 15u) == 0;
+                            (((uintptr_t)p.in + (valid ? p.in_off[table_at<PAIR>(i, 0)] : 0ull)) & 15u) == 0;
         bm[k] = medium && p.blist && !res_ok ? 1u : 0u;
         md[k] = medium && !bm[k] ? 1u : 0u;
     }
@@ -2357,7 +2363,7 @@ __global__ __launch_bounds__(kPlanThreads) void tdt_encode_plan_kernel(PlanArgs 
 // the 255-cap chunk starts that carried run makes inside the tile before its first own run
 // start, prefix sums of the chunk starts — rewrites the records for the emit pass, and writes
 // the blob's size, status and header.
-template <int WS>
+template <int WS, bool PAIR = false>
 __global__ __launch_bounds__(64) void tdt_encode_lscan_kernel(EncodeArgs a, const uint32_t *lcnt, uint32_t lmax) {
     const uint32_t nl = umin(*lcnt, lmax);
     const int lane = lane_id();
@@ -2365,7 +2371,7 @@ __global__ __launch_bounds__(64) void tdt_encode_lscan_kernel(EncodeArgs a, cons
         LMeta *lm = a.lmeta + j;
         const uint32_t msg = lm->msg;
         if (msg == kNone) continue;  // fell back to the whole-message kernel
-        const uint64_t n = a.in_off[msg + 1] - a.in_off[msg];
+        const uint64_t n = a.in_off[table_at<PAIR>(msg, 1)] - a.in_off[table_at<PAIR>(msg, 0)];
         const bool compress = a.policy_on && n >= a.min_tensor && (n % 4 == 0) && n >= 64 && (n % WS == 0) &&
                               n < (1ull << 32);
         if (!compress) continue;  // UNCP: the histogram pass copied it
@@ -2411,8 +2417,8 @@ __global__ __launch_bounds__(64) void tdt_encode_lscan_kernel(EncodeArgs a, cons
         }
         const uint32_t hdr = 20 + 4 * WS;
         const uint64_t E = hdr + (4 + 2ull * Pt[0]) + (ns2 ? 4 + 2ull * Pt[1] : 0);
-        const uint64_t ob = a.slot_off[msg];
-        const bool fits = E <= a.slot_off[msg + 1] - ob;
+        const uint64_t ob = a.slot_off[table_at<PAIR>(msg, 0)];
+        const bool fits = E <= a.slot_off[table_at<PAIR>(msg, 1)] - ob;
         if (lane == 0) {
             if (a.status) a.status[msg] = fits ? ST_OK : ST_CAPACITY;
             if (a.out_len) a.out_len[msg] = fits ? E : 0;
@@ -2451,5 +2457,13 @@ __global__ __launch_bounds__(64) void tdt_encode_lscan_kernel(EncodeArgs a, cons
     X(WS, 256, 8, MODE_ENCODE, 0, 0, 1, 0) X(WS, 64, 4, MODE_ENCODE, 1, 0, 0, 0) X(WS, 512, 8, MODE_ENCODE, 1, 0, 0, 0)  \
     X(WS, 64, 4, MODE_MAPPED, 1, 0, 0, 0) X(WS, 512, 8, MODE_MAPPED, 1, 0, 0, 0) X(WS, 64, 4, MODE_ANALYZE, 1, 0, 0, 0)  \
     X(WS, 512, 8, MODE_ANALYZE, 1, 0, 0, 0) X(WS, 512, 8, MODE_ENCODE, 1, 0, 0, 1)
+
+// The slotted instances again for the scattered batches (PAIR): the contiguous calls' code objects
+// stay what they were, register for register, and a scattered batch runs the same bodies.
+#define PSY_ENC_PAIR_INSTANCES(X, WS)                                                                             \
+    X(WS, 512, 8, 0, 0, 1) X(WS, 512, 8, 0, 1, 1) X(WS, 512, 8, 0, 0, 2) X(WS, 512, 8, 0, 1, 2) X(WS, 512, 8, 1, 0, 0) \
+    X(WS, 512, 8, 2, 0, 0) X(WS, 512, 8, 3, 0, 0) X(WS, 512, 8, 4, 0, 0) X(WS, 64, 4, 0, 0, 0) X(WS, 512, 8, 1, 1, 0)  \
+    X(WS, 512, 8, 2, 1, 0) X(WS, 512, 8, 3, 1, 0) X(WS, 512, 8, 4, 1, 0) X(WS, 64, 4, 0, 1, 0) X(WS, 256, 8, 0, 0, 0)  \
+    X(WS, 256, 8, 0, 1, 0)
 
 }  // namespace psy

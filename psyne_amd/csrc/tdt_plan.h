@@ -21,7 +21,8 @@ enum EncCount : int {
     EC_BIG = 8,          // medium messages over big_min (their own list, dispatched first)
     EC_UNCP_ALL = 9,     // passthrough (UNCP) messages up to large_min, listed or not
     EC_UNCP = 10,        // UNCP messages, listed (the copy list)
-    EC_RECOUNT = 11      // tiles the map pass listed for the count pass (the highest)
+    EC_RECOUNT = 11,     // tiles the map pass listed for the count pass
+    EC_BYTES = 12        // scattered batches: the sum of the message sizes, by the table kernel (the highest)
 };
 enum DecCount : int {
     DC_MAIN = 0,         // one-wave blobs (the main list)
@@ -33,6 +34,7 @@ enum DecCount : int {
     DC_BIG = 6,          // big one-wave blobs (their own list, dispatched first)
     DC_UNCP_ALL = 7,     // UNCP blobs, listed or not
     DC_UNCP = 8,         // UNCP blobs, listed (the copy list)
+    DC_BYTES = 9,        // scattered batches: the sum of the blob lengths, by the table kernel
     DC_DEFERRED = 15     // blobs of a generic word size the class kernels deferred (the highest)
 };
 
@@ -43,7 +45,7 @@ constexpr int lo32(DecCount k) { return 2 * (int)k; }
 constexpr size_t kPlanCounterBytes = 256;  // the block
 constexpr size_t kPlanSnapBytes = 128;     // zeroed per call and copied to the host's snapshot
 static_assert(kPlanSnapBytes <= kPlanCounterBytes, "the snapshot is a prefix of the block");
-static_assert(8 * (EC_RECOUNT + 1) <= kPlanSnapBytes && 8 * (DC_DEFERRED + 1) <= kPlanSnapBytes,
+static_assert(8 * (EC_BYTES + 1) <= kPlanSnapBytes && 8 * (DC_DEFERRED + 1) <= kPlanSnapBytes,
               "every counter is zeroed per call and snapshotted");
 
 // The lists behind the counters, n u32 entries each, in buffer order.
@@ -51,15 +53,35 @@ enum EncList : int { EL_SMALL, EL_MEDIUM, EL_MID, EL_BIG, EL_COPY };
 enum DecList : int { DL_MAIN, DL_SMALL, DL_BIG, DL_COPY, DL_DEFERRED };
 constexpr int kPlanLists = 5;
 
-// The plan buffer of a batch of n messages: counters | five lists (256 + 20 * n bytes).
+// Index of message i's begin (k = 0) or end (k = 1) in an offset table: the n + 1 offsets of a
+// contiguous batch, message i = [off[i], off[i + 1]), or — PAIR, the scattered batches' kernel
+// instances — (begin, end) pairs, message i = [off[2i], off[2i + 1]).
+template <bool PAIR>
+constexpr uint64_t table_at(uint32_t i, uint32_t k) {
+    return PAIR ? 2ull * i + k : (uint64_t)(i + k);
+}
+
+// The (begin, end) tables of a scattered batch (the *_v calls), written by the table kernel from the
+// caller's pointer and size arrays: 2 * n u64 each, behind the lists.
+enum PairTable : int { PT_IN, PT_OUT };  // message bytes (encode only) | output slots
+constexpr int kPlanPairs = 2;
+
+// The plan buffer of a batch of n messages: counters | five lists (256 + 20 * n bytes), and for a
+// scattered batch | two pair tables (16-byte aligned, 32 * n bytes more).
 struct PlanLayout {
     size_t list[kPlanLists];  // byte offsets
+    size_t pair[kPlanPairs];  // (0: a contiguous batch has none)
     size_t bytes;
 };
-constexpr PlanLayout plan_layout(uint32_t n) {
+constexpr PlanLayout plan_layout(uint32_t n, bool scattered = false) {
     PlanLayout L{};
     for (int i = 0; i < kPlanLists; ++i) L.list[i] = kPlanCounterBytes + 4ull * n * i;
     L.bytes = kPlanCounterBytes + 4ull * n * kPlanLists;
+    if (scattered) {
+        L.bytes = (L.bytes + 15) & ~(size_t)15;
+        for (int i = 0; i < kPlanPairs; ++i) L.pair[i] = L.bytes + 16ull * n * i;
+        L.bytes += 16ull * n * kPlanPairs;
+    }
     return L;
 }
 

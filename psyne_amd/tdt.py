@@ -236,6 +236,85 @@ class TdtCodec:
                                                 _ptr(status), self._stream(stream)))
         return sizes[:n], status[:n]
 
+    # ---- scattered batches (one buffer per message: tensors of a training process) ------
+    def encode_v(self, ptrs, sizes, out_ptrs, out_caps, lengths=None, status=None, stream=None):
+        """Encode message i = sizes[i] bytes at address ptrs[i] into out_caps[i] bytes at address
+        out_ptrs[i] (int64 tensors on the GPU); returns (lengths, status)."""
+        import torch
+        n = sizes.numel()
+        if lengths is None:
+            lengths = torch.empty(max(n, 1), dtype=torch.int64, device=sizes.device)
+        if status is None:
+            status = torch.empty(max(n, 1), dtype=torch.int32, device=sizes.device)
+        check(self._lib.tdt_encode_batch_v(self._h, _ptr(ptrs), _ptr(sizes), n, _ptr(out_ptrs), _ptr(out_caps),
+                                           _ptr(lengths), _ptr(status), self._stream(stream)))
+        return lengths, status
+
+    def decode_v(self, ptrs, in_lengths, out_ptrs, out_caps, lengths=None, status=None, stream=None):
+        """Decode blob i = in_lengths[i] bytes at address ptrs[i] into out_caps[i] bytes at address
+        out_ptrs[i] (int64 tensors on the GPU); returns (lengths, status)."""
+        import torch
+        n = in_lengths.numel()
+        if lengths is None:
+            lengths = torch.empty(max(n, 1), dtype=torch.int64, device=in_lengths.device)
+        if status is None:
+            status = torch.empty(max(n, 1), dtype=torch.int32, device=in_lengths.device)
+        check(self._lib.tdt_decode_batch_v(self._h, _ptr(ptrs), _ptr(in_lengths), n, _ptr(out_ptrs), _ptr(out_caps),
+                                           _ptr(lengths), _ptr(status), self._stream(stream)))
+        return lengths, status
+
+    def decoded_sizes_v(self, ptrs, in_lengths, stream=None):
+        import torch
+        n = in_lengths.numel()
+        sizes = torch.empty(max(n, 1), dtype=torch.int64, device=in_lengths.device)
+        status = torch.empty(max(n, 1), dtype=torch.int32, device=in_lengths.device)
+        check(self._lib.tdt_decoded_sizes_v(self._h, _ptr(ptrs), _ptr(in_lengths), n, _ptr(sizes), _ptr(status),
+                                            self._stream(stream)))
+        return sizes[:n], status[:n]
+
+    @staticmethod
+    def _tensor_table(tensors):
+        """(addresses, byte sizes) of a list of contiguous GPU tensors, as host int64 arrays."""
+        for t in tensors:
+            if not t.is_cuda:
+                raise ValueError("encode_tensors / decode_tensors take GPU tensors")
+            if not t.is_contiguous():
+                raise ValueError("encode_tensors / decode_tensors take contiguous tensors")
+        sizes = np.array([t.numel() * t.element_size() for t in tensors], dtype=np.int64)
+        ptrs = np.array([t.data_ptr() if s else 0 for t, s in zip(tensors, sizes)], dtype=np.uint64).view(np.int64)
+        return ptrs, sizes
+
+    def encode_tensors(self, tensors, out=None, stream=None):
+        """Encode a list of contiguous GPU tensors (any dtypes; message i = the bytes of
+        tensors[i]) without packing them: blob i goes to out[slots[i]:slots[i+1]], the slots being
+        the prefix sum of the encode bounds.  Returns (out, slots, lengths, status)."""
+        import torch
+        ptrs, sizes = self._tensor_table(tensors)
+        n = len(tensors)
+        dev = tensors[0].device if n else torch.device("cuda", self.device)
+        ws = self.config.word_size
+        slots = np.zeros(n + 1, np.int64)
+        np.cumsum(np.maximum(sizes + 4, 28 + 4 * ws + 2 * sizes), out=slots[1:])
+        if out is None:
+            out = torch.empty(max(int(slots[-1]), 1), dtype=torch.uint8, device=dev)
+        elif out.numel() < int(slots[-1]):
+            raise ValueError("out holds %d bytes, the slots need %d" % (out.numel(), int(slots[-1])))
+        # one upload: addresses | sizes | blob addresses | capacities | slots
+        tab = np.concatenate([ptrs, sizes, out.data_ptr() + slots[:-1], np.diff(slots), slots])
+        d = torch.from_numpy(tab).to(dev, non_blocking=False)
+        lengths, status = self.encode_v(d[:n], d[n:2 * n], d[2 * n:3 * n], d[3 * n:4 * n], stream=stream)
+        return out, d[4 * n:], lengths, status
+
+    def decode_tensors(self, blobs, offsets, in_lengths, outs, stream=None):
+        """Decode blob i = blobs[offsets[i]:offsets[i]+in_lengths[i]] into the preallocated
+        contiguous GPU tensor outs[i] (capacity: its byte size).  Returns (lengths, status)."""
+        import torch
+        optrs, osizes = self._tensor_table(outs)
+        n = len(outs)
+        d = torch.from_numpy(np.concatenate([optrs, osizes])).to(blobs.device)
+        ptrs = offsets[:n].to(torch.int64) + blobs.data_ptr()
+        return self.decode_v(ptrs, in_lengths, d[:n], d[n:], stream=stream)
+
     def analyze_batch(self, data, offsets, stream=None):
         """Full-sample histograms (n, ws, 256), entropies (n, ws), mapping (n, ws), status."""
         import torch
