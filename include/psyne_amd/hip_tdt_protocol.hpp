@@ -176,6 +176,15 @@ public:
                        const uint64_t *d_blob_cap, uint64_t *d_out_len, int32_t *d_status, void *stream = nullptr) {
         return tdt_encode_batch_v(ctx_, d_msgs, d_sizes, n, d_blobs, d_blob_cap, d_out_len, d_status, stream);
     }
+    // the same with one record width per message (d_word_size[i]; width_mask: bit w - 1 set for
+    // every width that may occur, at most TDT_MIXED_MAX_WIDTHS of them) — a mixed-precision
+    // gradient list in one call, whatever this protocol's own word_size (tdt_encode_batch_vw)
+    int encode_batch_vw(const uint8_t *const *d_msgs, const uint64_t *d_sizes, const int32_t *d_word_size,
+                        uint64_t width_mask, uint32_t n, uint8_t *const *d_blobs, const uint64_t *d_blob_cap,
+                        uint64_t *d_out_len, int32_t *d_status, void *stream = nullptr) {
+        return tdt_encode_batch_vw(ctx_, d_msgs, d_sizes, d_word_size, width_mask, n, d_blobs, d_blob_cap, d_out_len,
+                                   d_status, stream);
+    }
     int decode_batch_v(const uint8_t *const *d_blobs, const uint64_t *d_blob_len, uint32_t n, uint8_t *const *d_outs,
                        const uint64_t *d_out_cap, uint64_t *d_out_len, int32_t *d_status, void *stream = nullptr) {
         return tdt_decode_batch_v(ctx_, d_blobs, d_blob_len, n, d_outs, d_out_cap, d_out_len, d_status, stream);

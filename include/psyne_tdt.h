@@ -189,6 +189,29 @@ int tdt_encode_batch_v(tdt_ctx *ctx, const uint8_t *const *d_msgs, const uint64_
 int tdt_decode_batch_v(tdt_ctx *ctx, const uint8_t *const *d_blobs, const uint64_t *d_blob_len, uint32_t n_msgs,
                        uint8_t *const *d_outs, const uint64_t *d_out_cap, uint64_t *d_out_len, int32_t *d_status,
                        void *hip_stream);
+/* MIXED WORD SIZES — tdt_encode_batch_v with one record width per message (a mixed-precision
+ * gradient list: bf16 / fp16 tensors at width 2 beside fp32 ones at 4 and fp64 / int64 ones at 8).
+ * d_word_size[i] (device memory, n_msgs entries) is message i's width; the context's own word_size
+ * plays no part.  width_mask is the host's statement of the widths that may occur: bit w - 1 set
+ * means "width w may occur" (the host reads no device array, so the mask is how it learns which
+ * pipelines to launch).  At most TDT_MIXED_MAX_WIDTHS bits may be set: the call keeps one pair of
+ * tables (32 bytes) per message and width, and launches one pipeline per width.  A zero mask (with
+ * n_msgs > 0) or one with more bits returns TDT_E_ARG.
+ *   Same bytes: blob i, d_out_len[i] and d_status[i] are exactly what tdt_encode_batch_v gives on a
+ *     context created with word_size = d_word_size[i] and the same metrics, min_tensor_size and
+ *     capacity — the UNCP routing (n % 4, n >= 64, n % word_size, the policy) and TDT_E_CAPACITY
+ *     included.
+ *   Rejected widths: d_word_size[i] <= 0 gives TDT_E_CONFIG, > 64 TDT_E_UNSUPPORTED, and a width in
+ *     1..64 whose mask bit is clear TDT_E_ARG; each with length 0 and no byte of the output written.
+ *   Everything else — addressing, aliasing, size-0 messages, one stream per context, asynchronous,
+ *     nothing read back — is as for tdt_encode_batch_v.  Capturable once one eager call of the same
+ *     n_msgs and mask has grown the workspaces (TDT_E_CAPTURE otherwise); n_msgs == 0 returns TDT_OK
+ *     and touches nothing.  Blobs carry their width, so tdt_decode_batch_v decodes the result as it is. */
+#define TDT_MIXED_MAX_WIDTHS 8
+int tdt_encode_batch_vw(tdt_ctx *ctx, const uint8_t *const *d_msgs, const uint64_t *d_sizes,
+                        const int32_t *d_word_size, uint64_t width_mask, uint32_t n_msgs,
+                        uint8_t *const *d_blobs, const uint64_t *d_blob_cap,
+                        uint64_t *d_out_len, int32_t *d_status, void *hip_stream);
 /* Decoded size of each scattered blob (0 with an error status), as tdt_decoded_sizes_batch. */
 int tdt_decoded_sizes_v(tdt_ctx *ctx, const uint8_t *const *d_blobs, const uint64_t *d_blob_len, uint32_t n_msgs,
                         uint64_t *d_sizes, int32_t *d_status, void *hip_stream);

@@ -66,6 +66,8 @@ __global__ __launch_bounds__(kAnyTeam) void tdt_encode_any_kernel(EncodeArgs a, 
     const uint32_t msg = blockIdx.x;
     if (msg >= a.n_msgs) return;
     const uint64_t off0 = a.in_off[table_at<PAIR>(msg, 0)];
+    // (a mixed-width batch: this message belongs to another width's pipeline — nothing is touched)
+    if (PAIR && pair_absent(off0, a.in_off[table_at<PAIR>(msg, 1)])) return;
     const uint64_t n = a.in_off[table_at<PAIR>(msg, 1)] - off0;
     const uint8_t *base = a.in + off0;
     const uint8_t *lim = base + n;

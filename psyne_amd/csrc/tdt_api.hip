@@ -219,6 +219,12 @@ struct tdt_ctx {
     // error flags of the host pipeline's chunks, OR-ed since the context was created
     std::atomic<uint32_t> host_flags{0};
     PlanWS pw;                        // the slotted calls' plan workspace
+    // mixed-width scattered encode (tdt_encode_batch_vw): a plan workspace and count history per
+    // tuned width (1, 2, 4, 8, 16 by log2; created on first use, `pw` is never touched), and the
+    // pair tables of every width of the call (psy::mixed_routes)
+    std::unique_ptr<PlanWS> mx_pw[5];
+    uint8_t *mx_tab = nullptr;
+    size_t mx_bytes = 0;
     // two-phase compacted encode (batches with messages > 64 KiB): slotted blobs, their slots
     // and lengths, then a scan and a gather into the caller's compacted buffer
     uint8_t *cp_buf = nullptr;
@@ -629,17 +635,25 @@ bool with_word_size(int ws, F &&f) {
     }
 }
 
-// PAIR: a scattered batch (`v`): its pair tables first, then the same classes through the PAIR instances
+// The tables of one width of a mixed-width batch (tdt_encode_batch_vw): the route kernel has written
+// them, behind the zeroing of this width's plan counters, and has summed the width's bytes into EC_BYTES
+struct Routed {
+    const uint64_t *in_pair, *out_pair;
+};
+
+// PAIR: a scattered batch (`v`): its pair tables first, then the same classes through the PAIR
+// instances; or one width of a mixed-width batch (`r`), whose tables are there already
 template <int WS, bool PAIR = false>
-int launch_slotted(tdt_ctx *c, PlanWS &pw, psy::EncodeArgs a, hipStream_t s, const Scatter *v = nullptr) {
+int launch_slotted(tdt_ctx *c, PlanWS &pw, psy::EncodeArgs a, hipStream_t s, const Scatter *v = nullptr,
+                   const Routed *r = nullptr) {
     using namespace psy;  // (counter, list and kernel names)
     const uint32_t n = a.n_msgs;
     // the list-entry prefetch of the slotted kernels (EncodeArgs::list) reads entry
     // min(i, n - 1) of a class list before its count: n >= 1, and every list holds n entries
     // (ensure_plan: five lists of n entries behind the counters)
     if (n == 0) return set_err(TDT_E_ARG, "slotted encode launch without messages");
-    if (PAIR != (v != nullptr)) return set_err(TDT_E_ARG, "scattered launch without its arrays");
-    int st = ensure_plan(pw, n, s, PAIR);
+    if (PAIR != (v != nullptr || r != nullptr)) return set_err(TDT_E_ARG, "scattered launch without its arrays");
+    int st = ensure_plan(pw, n, s, PAIR && !r);
     if (st) return st;
     const PlanLayout PL = plan_layout(n);
     if (pw.bytes < PL.bytes) return set_err(TDT_E_ARG, "plan buffer smaller than five lists of n entries");
@@ -667,9 +681,15 @@ int launch_slotted(tdt_ctx *c, PlanWS &pw, psy::EncodeArgs a, hipStream_t s, con
     auto *lmeta = reinterpret_cast<LMeta *>(pw.elarge);
     auto *tiles = reinterpret_cast<uint64_t *>(pw.elarge + EL.tiles);
     auto *spans = reinterpret_cast<uint64_t *>(pw.elarge + EL.spans);
-    HIPCHK(hipMemsetAsync(cnt, 0, kPlanSnapBytes, s));
-    if constexpr (PAIR)  // the pair tables and the batch's byte count, then every kernel below as usual
-        if ((st = launch_table(pw, *v, n, true, cnt64 + EC_BYTES, a.in_off, a.slot_off, s))) return st;
+    if (!r) HIPCHK(hipMemsetAsync(cnt, 0, kPlanSnapBytes, s));
+    if constexpr (PAIR) {  // the pair tables and the batch's byte count, then every kernel below as usual
+        if (r) {
+            a.in_off = r->in_pair;
+            a.slot_off = r->out_pair;
+        } else if ((st = launch_table(pw, *v, n, true, cnt64 + EC_BYTES, a.in_off, a.slot_off, s))) {
+            return st;
+        }
+    }
     PlanArgs p{a.in, a.in_off, n, cnt64, list(EL_SMALL), list(EL_MEDIUM), list(EL_MID), list(EL_BIG), list(EL_COPY),
                tiles, spans, lmeta, lcap, tcap, kSmallMax, kMidMax, kBigMin, c->large_min, small_on ? 1u : 0u,
                mid_on ? 1u : 0u, a.min_tensor, (uint32_t)a.policy_on, (uint32_t)WS, copy_on ? 1u : 0u};
@@ -761,6 +781,150 @@ int launch_slotted_any(tdt_ctx *c, PlanWS &pw, psy::EncodeArgs a, hipStream_t s,
         if ((st = launch_table(pw, *v, a.n_msgs, true, nullptr, a.in_off, a.slot_off, s))) return st;
     }
     return launch_any_encode(a, c->cfg.word_size, psy::MODE_ENCODE, s, v != nullptr);
+}
+
+// ---------------------------------------------------------------------------------------
+// Mixed word sizes (tdt_encode_batch_vw): a scattered batch with one record width per message.  The
+// host knows the widths that may occur (the caller's mask), never which message has which.  One
+// route kernel writes a pair of tables per width of the mask — a message's entry in its own
+// width's tables, psy's ABSENT entry in every other — and sums each width's sizes into that
+// width's EC_BYTES; then every width runs its usual pipeline over its tables: launch_slotted for a
+// tuned width (a PlanWS and count history of its own), the generic encode for any other.  A class
+// kernel reaches a message only through a plan list, the generic encode's workgroup leaves at an
+// absent entry, and status / out_len are indexed by message id: each message is written by its
+// width's pipeline alone, or — a width outside 1..64 or outside the mask — by the route kernel.
+struct RouteArgs {
+    Scatter v;
+    const int32_t *ws;  // width per message
+    uint32_t n, n_routes;
+    int32_t width[psy::kMixedMaxWidths];
+    ulonglong2 *in_pair[psy::kMixedMaxWidths], *out_pair[psy::kMixedMaxWidths];
+    unsigned long long *bytes[psy::kMixedMaxWidths];  // += the width's sizes (null: a generic width, no plan)
+    int32_t *status;
+    uint64_t *out_len;
+};
+__global__ __launch_bounds__(256) void tdt_route_kernel(RouteArgs t) {
+    __shared__ unsigned long long s_sum[psy::kMixedMaxWidths];
+    if (threadIdx.x < psy::kMixedMaxWidths) s_sum[threadIdx.x] = 0;
+    __syncthreads();
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    int route = -1;
+    unsigned long long sz = 0;
+    uint64_t ib = psy::kAbsentBegin, ie = psy::kAbsentEnd, ob = psy::kAbsentBegin, oe = psy::kAbsentEnd;
+    if (i < t.n) {
+        const int32_t w = t.ws[i];
+#pragma unroll  // (constant indices: the argument arrays stay in scalar registers)
+        for (uint32_t k = 0; k < (uint32_t)psy::kMixedMaxWidths; ++k)
+            if (k < t.n_routes && t.width[k] == w) route = (int)k;
+        if (route >= 0) {
+            sz = t.v.size[i];
+            ib = t.v.ptr[i];
+            ie = ib + sz;
+            ob = t.v.out_ptr[i];
+            oe = ob + t.v.out_cap[i];
+        } else {  // rejected: no pipeline sees it
+            if (t.status) t.status[i] = w <= 0 ? psy::ST_CONFIG : w > psy::kMixedWsMax ? psy::ST_UNSUPPORTED : psy::ST_ARG;
+            if (t.out_len) t.out_len[i] = 0;
+        }
+    }
+#pragma unroll
+    for (uint32_t k = 0; k < (uint32_t)psy::kMixedMaxWidths; ++k) {  // (uniform)
+        if (k >= t.n_routes) continue;
+        const bool mine = route == (int)k;
+        if (i < t.n) {
+            t.in_pair[k][i] = make_ulonglong2(mine ? ib : psy::kAbsentBegin, mine ? ie : psy::kAbsentEnd);
+            t.out_pair[k][i] = make_ulonglong2(mine ? ob : psy::kAbsentBegin, mine ? oe : psy::kAbsentEnd);
+        }
+        if (!t.bytes[k]) continue;
+        unsigned long long x = mine ? sz : 0ull;
+        for (int d = 32; d > 0; d >>= 1) x += __shfl_down(x, d, 64);
+        if ((threadIdx.x & 63u) == 0 && x) atomicAdd(&s_sum[k], x);
+    }
+    __syncthreads();
+#pragma unroll
+    for (uint32_t k = 0; k < (uint32_t)psy::kMixedMaxWidths; ++k)
+        if (threadIdx.x == k && k < t.n_routes && t.bytes[k] && s_sum[k]) atomicAdd(t.bytes[k], s_sum[k]);
+}
+
+int tuned_index(int ws) { return ws == 1 ? 0 : ws == 2 ? 1 : ws == 4 ? 2 : ws == 8 ? 3 : 4; }
+int prep(tdt_ctx *c, uint32_t n_msgs, hipStream_t s, uint8_t *&wsp, bool lookback);  // (below)
+
+int encode_mixed(tdt_ctx *c, const Scatter &v, const int32_t *d_word_size, uint64_t width_mask, uint32_t n,
+                 uint64_t *d_out_len, int32_t *d_status, hipStream_t s) {
+    if (!c) return set_err(TDT_E_ARG, "null context");
+    if (n == 0) return TDT_OK;
+    if (!(v.ptr && v.size && v.out_ptr && v.out_cap && d_word_size))
+        return set_err(TDT_E_ARG, "null pointer, size or word-size array");
+    psy::MixedRoutes R{};
+    if (!psy::mixed_routes(width_mask, n, R))
+        return set_err(TDT_E_ARG, "width_mask must name between 1 and 8 word sizes");
+    std::lock_guard<std::mutex> lk(c->mu);
+    uint8_t *wsp = nullptr;
+    int st = prep(c, n, s, wsp, false);
+    if (st) return st;
+    // the workspaces: the tables of every width, and a plan buffer per tuned width
+    if (R.bytes > c->mx_bytes) {
+        if ((st = no_growth_in_capture(s))) return st;
+        if (c->mx_tab) c->retired.push_back(c->mx_tab);  // (a graph captured earlier may use it)
+        c->mx_tab = nullptr;
+        const size_t cap = std::max(R.bytes, c->mx_bytes * 2);
+        HIPCHK(hipMalloc(&c->mx_tab, cap));
+        c->mx_bytes = cap;
+    }
+    RouteArgs t{};
+    t.v = v;
+    t.ws = d_word_size;
+    t.n = n;
+    t.n_routes = (uint32_t)R.n_routes;
+    t.status = d_status;
+    t.out_len = d_out_len;
+    for (int k = 0; k < R.n_routes; ++k) {
+        const psy::MixedRoute &q = R.route[k];
+        t.width[k] = q.ws;
+        t.in_pair[k] = reinterpret_cast<ulonglong2 *>(c->mx_tab + q.pair[psy::PT_IN]);
+        t.out_pair[k] = reinterpret_cast<ulonglong2 *>(c->mx_tab + q.pair[psy::PT_OUT]);
+        if (!q.tuned) {
+            if (!(PSY_HAVE_ANYWS)) return set_err(TDT_E_UNSUPPORTED, "this build holds no generic-width kernels");
+            continue;
+        }
+        if (!with_word_size(q.ws, [](auto) {})) return set_err(TDT_E_UNSUPPORTED, "this build holds word size 4 only");
+        auto &pw = c->mx_pw[tuned_index(q.ws)];
+        if (!pw) {
+            if ((st = no_growth_in_capture(s))) return st;
+            pw.reset(new PlanWS());
+        }
+        if ((st = ensure_plan(*pw, n, s))) return st;
+        HIPCHK(hipMemsetAsync(pw->buf, 0, psy::kPlanSnapBytes, s));
+        t.bytes[k] = reinterpret_cast<unsigned long long *>(pw->buf) + psy::EC_BYTES;
+    }
+    hipLaunchKernelGGL(tdt_route_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, t);
+    HIPCHK(hipGetLastError());
+    psy::EncodeArgs a{};
+    a.n_msgs = n;
+    a.status = d_status;
+    a.out_len = d_out_len;
+    a.ticket = reinterpret_cast<uint32_t *>(wsp);
+    a.errflags = reinterpret_cast<uint32_t *>(wsp) + 1;
+    a.lookback = reinterpret_cast<uint64_t *>(wsp + kCounterBytes);
+    a.min_tensor = c->cfg.min_tensor_size;
+    a.policy_on = policy_on(c) ? 1 : 0;
+    // one width after another on the caller's stream, each tuned one forking its own side stream
+    for (int k = 0; k < R.n_routes; ++k) {
+        const psy::MixedRoute &q = R.route[k];
+        const Routed r{reinterpret_cast<const uint64_t *>(t.in_pair[k]), reinterpret_cast<const uint64_t *>(t.out_pair[k])};
+        if (q.tuned) {
+            PlanWS &pw = *c->mx_pw[tuned_index(q.ws)];
+            with_word_size(q.ws, [&](auto W) { st = launch_slotted<W(), true>(c, pw, a, s, nullptr, &r); });
+        } else {
+            psy::EncodeArgs g = a;
+            g.in_off = r.in_pair;
+            g.slot_off = r.out_pair;
+            st = launch_any_encode(g, q.ws, psy::MODE_ENCODE, s, true);
+        }
+        if (st) return st;
+    }
+    HIPCHK(hipGetLastError());
+    return TDT_OK;
 }
 
 // messages > 4 KiB: TEAM threads per message, G resident rounds per wave (64 KiB resident)
@@ -1995,6 +2159,9 @@ void tdt_ctx_destroy(tdt_ctx *ctx) {
     for (void *p : ctx->retired) (void)hipFree(p);
     for (void *p : ctx->retired_host) (void)hipHostFree(p);
     ctx->pw.release();
+    for (auto &w : ctx->mx_pw)
+        if (w) w->release();
+    if (ctx->mx_tab) (void)hipFree(ctx->mx_tab);
     if (ctx->hbases) (void)hipFree(ctx->hbases);
     if (ctx->one_stream) (void)hipStreamSynchronize(ctx->one_stream);
     if (ctx->one) (void)hipHostFree(ctx->one);
@@ -2269,6 +2436,15 @@ int tdt_encode_batch_v(tdt_ctx *ctx, const uint8_t *const *d_msgs, const uint64_
                     d_blob_cap};
     return encode_common(ctx, psy::MODE_ENCODE, nullptr, nullptr, n_msgs, nullptr, nullptr, 0, nullptr, d_status, nullptr,
                          nullptr, nullptr, stream, nullptr, d_out_len, nullptr, nullptr, -1, &v);
+}
+
+int tdt_encode_batch_vw(tdt_ctx *ctx, const uint8_t *const *d_msgs, const uint64_t *d_sizes,
+                        const int32_t *d_word_size, uint64_t width_mask, uint32_t n_msgs, uint8_t *const *d_blobs,
+                        const uint64_t *d_blob_cap, uint64_t *d_out_len, int32_t *d_status, void *stream) {
+    static_assert(TDT_MIXED_MAX_WIDTHS == psy::kMixedMaxWidths, "the header states the routes' limit");
+    const Scatter v{reinterpret_cast<const uint64_t *>(d_msgs), d_sizes, reinterpret_cast<const uint64_t *>(d_blobs),
+                    d_blob_cap};
+    return encode_mixed(ctx, v, d_word_size, width_mask, n_msgs, d_out_len, d_status, (hipStream_t)stream);
 }
 
 int tdt_decode_batch_v(tdt_ctx *ctx, const uint8_t *const *d_blobs, const uint64_t *d_blob_len, uint32_t n_msgs,

@@ -2284,10 +2284,14 @@ __global__ __launch_bounds__(kPlanThreads) void tdt_encode_plan_kernel(PlanArgs 
     uint64_t n[kPlanPer];
     auto &isl = A[0], &T = A[1], &S = A[2];
     auto &j = SA[0], &t0 = SA[1], &s0 = SA[2];
+    bool absent[kPlanPer];  // PAIR: the entry of a message that another width's pipeline encodes
 #pragma unroll
     for (int k = 0; k < (int)kPlanPer; ++k) {
         const uint32_t i = (blockIdx.x * kPlanPer + k) * kPlanThreads + threadIdx.x;
-        n[k] = i < p.n_msgs ? p.in_off[table_at<PAIR>(i, 1)] - p.in_off[table_at<PAIR>(i, 0)] : 0;
+        absent[k] = false;
+        if constexpr (PAIR)
+            absent[k] = i < p.n_msgs && pair_absent(p.in_off[table_at<PAIR>(i, 0)], p.in_off[table_at<PAIR>(i, 1)]);
+        n[k] = i < p.n_msgs && !absent[k] ? p.in_off[table_at<PAIR>(i, 1)] - p.in_off[table_at<PAIR>(i, 0)] : 0;
         isl[k] = i < p.n_msgs && n[k] > thr ? 1u : 0u;
         T[k] = isl[k] ? (n[k] + 16ull * kTileGroups - 1) / (16ull * kTileGroups) : 0;
         S[k] = (T[k] + kSpanTiles - 1) / kSpanTiles;
@@ -2320,7 +2324,7 @@ __global__ __launch_bounds__(kPlanThreads) void tdt_encode_plan_kernel(PlanArgs 
             for (uint64_t t = 0; t < S[k] && s0[k] + t < scap; ++t)
                 p.spans[s0[k] + t] = large ? (t << 32 | j[k]) : (uint64_t)kNone;
         }
-        const bool valid = i < p.n_msgs;
+        const bool valid = i < p.n_msgs && !absent[k];  // (an absent entry: listed nowhere, counted nowhere)
         const bool transform = p.policy_on && n[k] >= p.min_tensor && (n[k] % 4 == 0) && n[k] >= 64 &&
                                (n[k] % p.ws == 0) && n[k] < (1ull << 32);
         const bool uncp = valid && !isl[k] && !transform;

@@ -85,4 +85,57 @@ constexpr PlanLayout plan_layout(uint32_t n, bool scattered = false) {
     return L;
 }
 
+// ------------------------------------------------------------------ mixed word sizes
+// tdt_encode_batch_vw: one scattered batch, one record width per message.  The route kernel writes
+// one pair of tables per width of the caller's mask; a message of another width (or a rejected
+// one) gets the ABSENT entry there.  No message equals it: a real entry has begin <= end.  The
+// PAIR plan kernel lists and counts an absent entry nowhere, and the generic encode's workgroup
+// for it exits at once, so each width's pipeline touches its own messages only.
+constexpr uint64_t kAbsentBegin = ~0ull, kAbsentEnd = 0;
+constexpr bool pair_absent(uint64_t begin, uint64_t end) { return begin == kAbsentBegin && end == kAbsentEnd; }
+
+constexpr int kMixedMaxWidths = 8;  // widths per call (TDT_MIXED_MAX_WIDTHS): the workspace and launch bound
+constexpr int kMixedWsMax = 64;     // widest record (kAnyWsMax)
+constexpr bool mixed_tuned(int ws) { return ws == 1 || ws == 2 || ws == 4 || ws == 8 || ws == 16; }
+
+// What a width mask (bit w - 1: width w may occur) launches: its widths in ascending order, each
+// with the byte offsets of its two pair tables (2 * n u64 each, 16-byte aligned) in the call's
+// table workspace.  A tuned width runs the slotted pipeline over its tables, a generic one the
+// generic encode.
+struct MixedRoute {
+    int ws;
+    bool tuned;
+    size_t pair[kPlanPairs];  // byte offsets of the PT_IN / PT_OUT tables
+};
+struct MixedRoutes {
+    int n_routes, n_tuned, n_generic;
+    MixedRoute route[kMixedMaxWidths];
+    size_t bytes;  // the table workspace: 32 bytes per message and width
+};
+// false: an empty mask, or more than kMixedMaxWidths widths (`r` is then empty)
+constexpr bool mixed_routes(uint64_t mask, uint32_t n, MixedRoutes &r) {
+    r = MixedRoutes{};
+    int bits = 0;
+    for (int w = 1; w <= kMixedWsMax; ++w) bits += (int)((mask >> (w - 1)) & 1u);
+    if (bits == 0 || bits > kMixedMaxWidths) return false;
+    for (int w = 1; w <= kMixedWsMax; ++w) {
+        if (!((mask >> (w - 1)) & 1u)) continue;
+        MixedRoute &q = r.route[r.n_routes++];
+        q.ws = w;
+        q.tuned = mixed_tuned(w);
+        (q.tuned ? r.n_tuned : r.n_generic)++;
+        for (int i = 0; i < kPlanPairs; ++i) {
+            q.pair[i] = r.bytes;
+            r.bytes += 16ull * n;
+        }
+    }
+    return true;
+}
+// route index of width `ws` in `r`, or -1
+constexpr int mixed_route_of(const MixedRoutes &r, int ws) {
+    for (int i = 0; i < r.n_routes; ++i)
+        if (r.route[i].ws == ws) return i;
+    return -1;
+}
+
 }  // namespace psy

@@ -250,6 +250,35 @@ class TdtCodec:
                                            _ptr(lengths), _ptr(status), self._stream(stream)))
         return lengths, status
 
+    @staticmethod
+    def width_mask(word_sizes) -> int:
+        """The mask encode_vw takes: bit w - 1 set for every width w in `word_sizes` (host ints)."""
+        mask = 0
+        for w in set(int(w) for w in word_sizes):
+            if not 1 <= w <= 64:
+                raise ValueError("word size %d is outside 1..64" % w)
+            mask |= 1 << (w - 1)
+        return mask
+
+    def encode_vw(self, ptrs, sizes, word_sizes, width_mask, out_ptrs, out_caps, lengths=None, status=None,
+                  stream=None):
+        """encode_v with one record width per message: word_sizes[i] (int32 tensor on the GPU) is
+        message i's, whatever this codec's own word_size; width_mask (a host int, bit w - 1 per width
+        that may occur, at most 8 of them) tells the host which pipelines to launch.  Blob i is what
+        a codec of word_size word_sizes[i] gives; returns (lengths, status)."""
+        import torch
+        n = sizes.numel()
+        if n and word_sizes.dtype != torch.int32:
+            raise ValueError("word_sizes must be an int32 tensor")
+        if lengths is None:
+            lengths = torch.empty(max(n, 1), dtype=torch.int64, device=sizes.device)
+        if status is None:
+            status = torch.empty(max(n, 1), dtype=torch.int32, device=sizes.device)
+        check(self._lib.tdt_encode_batch_vw(self._h, _ptr(ptrs), _ptr(sizes), _ptr(word_sizes), int(width_mask), n,
+                                            _ptr(out_ptrs), _ptr(out_caps), _ptr(lengths), _ptr(status),
+                                            self._stream(stream)))
+        return lengths, status
+
     def decode_v(self, ptrs, in_lengths, out_ptrs, out_caps, lengths=None, status=None, stream=None):
         """Decode blob i = in_lengths[i] bytes at address ptrs[i] into out_caps[i] bytes at address
         out_ptrs[i] (int64 tensors on the GPU); returns (lengths, status)."""
@@ -284,26 +313,58 @@ class TdtCodec:
         ptrs = np.array([t.data_ptr() if s else 0 for t, s in zip(tensors, sizes)], dtype=np.uint64).view(np.int64)
         return ptrs, sizes
 
-    def encode_tensors(self, tensors, out=None, stream=None):
-        """Encode a list of contiguous GPU tensors (any dtypes; message i = the bytes of
-        tensors[i]) without packing them: blob i goes to out[slots[i]:slots[i+1]], the slots being
-        the prefix sum of the encode bounds.  Returns (out, slots, lengths, status)."""
+    def encode_tensors(self, tensors, out=None, stream=None, word_sizes=None):
+        """Encode a list of contiguous GPU tensors (message i = the bytes of tensors[i]) without
+        packing them: blob i goes to out[slots[i]:slots[i+1]], the slots being the prefix sum of the
+        encode bounds.  Returns (out, slots, lengths, status).
+
+        Tensors of any dtypes are accepted; `word_sizes` says at which record width each is encoded:
+          None      every tensor at this codec's word_size, whatever its dtype (a bfloat16 tensor at
+                    word_size 4 is split on float32's byte planes, and a tensor whose byte size is
+                    no multiple of word_size goes through uncompressed);
+          "dtype"   tensor i at its element_size() (2 for bfloat16 / float16, 4 for float32, 8 for
+                    float64 / int64, 1 for uint8), in one call;
+          ints      one width in 1..64 per tensor.
+        With widths, at most 8 different ones may occur in a call; blob i is what a codec of that
+        word_size gives.  decode_tensors needs no widths: blobs carry theirs."""
         import torch
         ptrs, sizes = self._tensor_table(tensors)
         n = len(tensors)
         dev = tensors[0].device if n else torch.device("cuda", self.device)
-        ws = self.config.word_size
+        if word_sizes is None:
+            widths = None
+            ws = self.config.word_size
+        else:
+            if isinstance(word_sizes, str):
+                if word_sizes != "dtype":
+                    raise ValueError('word_sizes is None, "dtype" or one width per tensor')
+                widths = np.array([t.element_size() for t in tensors], dtype=np.int32)
+            else:
+                widths = np.array([int(w) for w in word_sizes], dtype=np.int32)
+            if widths.size != n:
+                raise ValueError("%d word sizes for %d tensors" % (widths.size, n))
+            mask = self.width_mask(widths)
+            if bin(mask).count("1") > 8:
+                raise ValueError("more than 8 different word sizes in one call")
+            ws = widths.astype(np.int64)
         slots = np.zeros(n + 1, np.int64)
         np.cumsum(np.maximum(sizes + 4, 28 + 4 * ws + 2 * sizes), out=slots[1:])
         if out is None:
             out = torch.empty(max(int(slots[-1]), 1), dtype=torch.uint8, device=dev)
         elif out.numel() < int(slots[-1]):
             raise ValueError("out holds %d bytes, the slots need %d" % (out.numel(), int(slots[-1])))
-        # one upload: addresses | sizes | blob addresses | capacities | slots
-        tab = np.concatenate([ptrs, sizes, out.data_ptr() + slots[:-1], np.diff(slots), slots])
-        d = torch.from_numpy(tab).to(dev, non_blocking=False)
-        lengths, status = self.encode_v(d[:n], d[n:2 * n], d[2 * n:3 * n], d[3 * n:4 * n], stream=stream)
-        return out, d[4 * n:], lengths, status
+        # one upload: addresses | sizes | blob addresses | capacities | slots (| widths, two per word)
+        parts = [ptrs, sizes, out.data_ptr() + slots[:-1], np.diff(slots), slots]
+        if widths is not None:
+            parts.append(np.concatenate([widths, np.zeros(n % 2, np.int32)]).view(np.int64))
+        d = torch.from_numpy(np.concatenate(parts)).to(dev, non_blocking=False)
+        if widths is None or n == 0:
+            lengths, status = self.encode_v(d[:n], d[n:2 * n], d[2 * n:3 * n], d[3 * n:4 * n], stream=stream)
+        else:
+            dw = d[5 * n + 1:].view(torch.int32)[:n]
+            lengths, status = self.encode_vw(d[:n], d[n:2 * n], dw, mask, d[2 * n:3 * n], d[3 * n:4 * n],
+                                             stream=stream)
+        return out, d[4 * n:5 * n + 1], lengths, status
 
     def decode_tensors(self, blobs, offsets, in_lengths, outs, stream=None):
         """Decode blob i = blobs[offsets[i]:offsets[i]+in_lengths[i]] into the preallocated
