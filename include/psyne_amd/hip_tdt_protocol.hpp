@@ -185,6 +185,20 @@ public:
         return tdt_encode_batch_vw(ctx_, d_msgs, d_sizes, d_word_size, width_mask, n, d_blobs, d_blob_cap, d_out_len,
                                    d_status, stream);
     }
+    // the packed wire buffer: blobs back to back in d_out with n + 1 offsets in d_out_off, one send per
+    // batch.  encode_batch_vp: the scattered encode (d_word_size null: this protocol's width; else
+    // one width per message) into such a buffer, total_bytes a host bound of the sum of d_sizes
+    // (tdt_encode_batch_vp); pack_v: blobs that exist already (tdt_pack_v)
+    int encode_batch_vp(const uint8_t *const *d_msgs, const uint64_t *d_sizes, const int32_t *d_word_size,
+                        uint64_t width_mask, uint32_t n, uint64_t total_bytes, uint8_t *d_out, uint64_t out_cap,
+                        uint64_t *d_out_off, int32_t *d_status, void *stream = nullptr) {
+        return tdt_encode_batch_vp(ctx_, d_msgs, d_sizes, d_word_size, width_mask, n, total_bytes, d_out, out_cap,
+                                   d_out_off, d_status, stream);
+    }
+    int pack_v(const uint8_t *const *d_blobs, const uint64_t *d_blob_len, uint32_t n, uint8_t *d_out, uint64_t out_cap,
+               uint64_t *d_out_off, int32_t *d_status, void *stream = nullptr) {
+        return tdt_pack_v(ctx_, d_blobs, d_blob_len, n, d_out, out_cap, d_out_off, d_status, stream);
+    }
     int decode_batch_v(const uint8_t *const *d_blobs, const uint64_t *d_blob_len, uint32_t n, uint8_t *const *d_outs,
                        const uint64_t *d_out_cap, uint64_t *d_out_len, int32_t *d_status, void *stream = nullptr) {
         return tdt_decode_batch_v(ctx_, d_blobs, d_blob_len, n, d_outs, d_out_cap, d_out_len, d_status, stream);

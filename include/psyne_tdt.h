@@ -24,6 +24,8 @@
  *   tdt_decode_batch_v                that lie in separate device buffers (one tensor, one
  *                                     transport_send(void*, size_t) buffer per message)
  *   tdt_decoded_sizes_v               tdt_decoded_sizes_batch over such blobs
+ *   tdt_encode_batch_vp /             a loop of encode :227-266 followed by a framed send of each
+ *   tdt_pack_v                        vector: the blobs back to back in one wire buffer, one send
  *   tdt_analyze_batch                 analyze_data / extract_features / perform_clustering
  *                                     :206-222, :434-525 (full-sample histograms, entropies,
  *                                     mapping per message)
@@ -212,6 +214,51 @@ int tdt_encode_batch_vw(tdt_ctx *ctx, const uint8_t *const *d_msgs, const uint64
                         const int32_t *d_word_size, uint64_t width_mask, uint32_t n_msgs,
                         uint8_t *const *d_blobs, const uint64_t *d_blob_cap,
                         uint64_t *d_out_len, int32_t *d_status, void *hip_stream);
+/* PACKED WIRE BUFFER — blobs back to back in message order with an offset table, so that one copy
+ * of d_out_off[n] bytes (or one send) ships the batch; tdt_decode_batch_v reads blobs at any
+ * offsets, so the receiving side needs nothing new.
+ *
+ * tdt_pack_v: blob i = d_blobs[i][0 .. d_blob_len[i]) -> d_out[d_out_off[i] .. d_out_off[i+1]), for
+ * anyone who holds slotted or scattered blobs (the output of tdt_encode_batch_into / _v / _vw).
+ * d_out_off (n_msgs + 1 entries, device memory) receives the exclusive prefix sum of the lengths,
+ * the total at [n_msgs]; it is complete whatever out_cap.  The copy is split by output bytes, one
+ * workgroup per 64 KiB of d_out, so one very long blob beside short ones costs what its bytes cost.
+ *   Capacity: a blob with d_out_off[i+1] > out_cap gets TDT_E_CAPACITY and not one of its bytes is
+ *     copied; every other blob gets TDT_OK (d_status may be NULL).  No byte is written outside
+ *     d_out[0 .. min(total, out_cap)).
+ *   Addressing: the sources may have any alignment and stand in any order, and may alias each
+ *     other; they must not overlap d_out.  The pointer of a zero-length blob is never dereferenced.
+ *   Context rules: asynchronous on hip_stream, nothing is read back, one stream at a time per
+ *     context; capturable once an eager call of the same n_msgs has grown the scan's workspace
+ *     (TDT_E_CAPTURE otherwise); n_msgs == 0 returns TDT_OK and touches nothing. */
+int tdt_pack_v(tdt_ctx *ctx, const uint8_t *const *d_blobs, const uint64_t *d_blob_len, uint32_t n_msgs,
+               uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_off, int32_t *d_status, void *hip_stream);
+/* tdt_encode_batch_vp: tdt_encode_batch_v (d_word_size == NULL: every message at the context's
+ * width, width_mask ignored) or tdt_encode_batch_vw (one width per message, width_mask as there)
+ * into a packed buffer.  Two phases on the device: every message is encoded into a slot of its
+ * encode bound in the context's scratch, then the blobs are packed into d_out as by tdt_pack_v.
+ * total_bytes is the host's upper bound of the sum of d_sizes: it sizes the scratch, 2 * total_bytes
+ * + n_msgs * (28 + 4 * wmax) bytes, wmax being the context's width or the highest mask bit (the host
+ * reads no device array).  A message whose slot would end past a scratch sized by an understated
+ * total_bytes gets TDT_E_CAPACITY; nothing is ever written outside the scratch.
+ *   Same bytes: blob i at d_out[d_out_off[i] .. d_out_off[i+1]) and d_status[i] are exactly what
+ *     tdt_encode_batch_v / _vw give for message i with a capacity of its encode bound.  A message
+ *     with an error status (a rejected width, ...) has length 0 and occupies no bytes.
+ *   Capacity: a blob with d_out_off[i+1] > out_cap gets TDT_E_CAPACITY (only if its status was
+ *     TDT_OK) and is not copied; d_out_off[n_msgs] is the number of bytes the whole batch needs,
+ *     whether or not it fit.
+ *   Context rules: addressing, aliasing and size-0 messages as for tdt_encode_batch_v, mask errors
+ *     at call level as for _vw; the messages must not overlap d_out.  Asynchronous, nothing read back,
+ *     one stream at a time per context, n_msgs == 0 touches nothing.  Capturable at every word size
+ *     once one eager call with the same n_msgs, the same mask and a total_bytes at least as large
+ *     has run (TDT_E_CAPTURE otherwise) — tdt_encode_batch, the compacted call for contiguous
+ *     input, is not at generic widths.
+ * Replaces a loop of TDTCompressionProtocol::encode (:227-266) followed by a framed send of each
+ * vector. */
+int tdt_encode_batch_vp(tdt_ctx *ctx, const uint8_t *const *d_msgs, const uint64_t *d_sizes,
+                        const int32_t *d_word_size, uint64_t width_mask, uint32_t n_msgs, uint64_t total_bytes,
+                        uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_off, int32_t *d_status,
+                        void *hip_stream);
 /* Decoded size of each scattered blob (0 with an error status), as tdt_decoded_sizes_batch. */
 int tdt_decoded_sizes_v(tdt_ctx *ctx, const uint8_t *const *d_blobs, const uint64_t *d_blob_len, uint32_t n_msgs,
                         uint64_t *d_sizes, int32_t *d_status, void *hip_stream);

@@ -47,6 +47,9 @@ SIGNATURES = {
     "tdt_decode_batch_into": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp]),
     "tdt_encode_batch_v": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp]),
     "tdt_encode_batch_vw": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint64, C.c_uint32, _vp, _vp, _vp, _vp, _vp]),
+    "tdt_pack_v": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _vp, C.c_uint64, _vp, _vp, _vp]),
+    "tdt_encode_batch_vp": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint64, C.c_uint32, C.c_uint64, _vp, C.c_uint64, _vp, _vp,
+                                      _vp]),
     "tdt_decode_batch_v": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp]),
     "tdt_decoded_sizes_v": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp]),
     "tdt_encode_slots": (C.c_int, [_vp, _vp, C.c_uint32, _vp, _vp]),

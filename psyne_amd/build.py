@@ -22,6 +22,8 @@ ENC_WS_SRC = CSRC / "tdt_enc_ws.hip"  # the encode kernels of one word size
 WORD_SIZES = (1, 2, 4, 8, 16)
 ANYWS_SRC = CSRC / "tdt_anyws.hip"  # encode and decode of every other word size up to 64
 SOURCES.append(ANYWS_SRC)
+PACK_SRC = CSRC / "tdt_pack.hip"  # the pack kernel of tdt_pack_v / tdt_encode_batch_vp
+SOURCES.append(PACK_SRC)
 # every source and header under csrc/ (tdt_api.hip includes the headers, directly or not)
 DEPS = SOURCES + [ENC_WS_SRC] + sorted(CSRC.glob("*.h")) + [ROOT / "include" / "psyne_tdt.h"]
 OBJ_DIR = PKG / "build"
@@ -35,7 +37,7 @@ def needs_build() -> bool:
 
 
 def build(force: bool = False, verbose: bool = False) -> pathlib.Path:
-    """Compile tdt_api.hip, tdt_anyws.hip and one tdt_enc_ws.hip object per word size in parallel
+    """Compile tdt_api.hip, tdt_anyws.hip, tdt_pack.hip and one tdt_enc_ws.hip object per word size in parallel
     (the encode kernels dominate the compile time), then link libpsyne_tdt.so."""
     if force or needs_build():
         OBJ_DIR.mkdir(exist_ok=True)

@@ -24,6 +24,7 @@
 #include "tdt_copypool.h"
 #include "tdt_decode.h"
 #include "tdt_encode.h"
+#include "tdt_pack.h"
 #include "tdt_plan.h"
 #include "tdt_slots.h"
 
@@ -231,6 +232,12 @@ struct tdt_ctx {
     size_t cp_bytes = 0;
     uint64_t *cp_idx = nullptr;  // slots (n + 1) | lengths (n) | flag
     size_t cp_idx_n = 0;
+    // packed scattered encode (tdt_encode_batch_vp) keeps its slots in cp_buf and its tables in
+    // cp_idx: slots (n + 1) | blob addresses (n) | capacities (n) | lengths (n).  That call may be
+    // captured, so from its first capture on a buffer replaced by a larger one is retired, not freed
+    bool cp_in_graph = false;
+    // the pack kernel's knobs (PSYNE_TDT_PACK_CUT, PSYNE_TDT_PACK_GRID: tools/pack_bench.py)
+    uint32_t pack_cut = psy::kPackCut, pack_grid = psy::kPackGridCap;
     uint64_t large_min = 256 * 1024;  // messages (decode: decoded blobs) above this take the tiled path
     uint32_t tile_cap = ~0u;          // lower tile budget (tests)
     // diagnostic knobs (read once at tdt_ctx_create from the environment, or tdt_ctx_set_option)
@@ -2032,6 +2039,14 @@ __global__ __launch_bounds__(256) void cp_gather_kernel(const uint8_t *src, cons
 }  // namespace
 
 static int scan_sizes(tdt_ctx *ctx, uint64_t *d_off, uint32_t n_msgs, hipStream_t stream);
+// A cp_buf / cp_idx buffer that a larger one replaces (under ctx->mu): freed, unless a captured
+// tdt_encode_batch_vp may still point at it — then it lives as long as the context.
+static hipError_t cp_drop(tdt_ctx *ctx, void *p) {
+    if (!p) return hipSuccess;
+    if (!ctx->cp_in_graph) return hipFree(p);
+    ctx->retired.push_back(p);
+    return hipSuccess;
+}
 // The two-phase compaction reads a few bytes back to choose its path: not under stream capture
 // (the one-pass kernels need no read-back), nor with the no-two-phase knob.
 static bool two_phase_ok(const tdt_ctx *ctx, void *stream) {
@@ -2136,6 +2151,9 @@ int tdt_ctx_create(int device, const tdt_config *cfg, tdt_ctx **out) {
     if (const char *e = std::getenv("PSYNE_TDT_DBIG_MIN")) x->dbig_min = std::strtoull(e, nullptr, 10);
     if (const char *e = std::getenv("PSYNE_TDT_DSMALL_MAX")) x->dsmall_max = std::strtoull(e, nullptr, 10);
     if (const char *e = std::getenv("PSYNE_TDT_COPY_WGS")) x->copy_wgs = std::max(1ul, std::strtoul(e, nullptr, 10));
+    if (const char *e = std::getenv("PSYNE_TDT_PACK_CUT")) x->pack_cut = (uint32_t)std::strtoul(e, nullptr, 10);
+    if (const char *e = std::getenv("PSYNE_TDT_PACK_GRID"))
+        x->pack_grid = (uint32_t)std::max(1ul, std::min(1ul << 30, std::strtoul(e, nullptr, 10)));
     int cus = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0)
         x->cus = cus;
@@ -2262,7 +2280,7 @@ static int encode_two_phase_any(tdt_ctx *ctx, int mode, const uint8_t *d_in, con
         std::lock_guard<std::mutex> lk(ctx->mu);
         const size_t need = 2ull * n_msgs + 2;
         if (need > ctx->cp_idx_n) {
-            if (ctx->cp_idx) HIPCHK(hipFree(ctx->cp_idx));
+            HIPCHK(cp_drop(ctx, ctx->cp_idx));
             ctx->cp_idx = nullptr;
             HIPCHK(hipMalloc(&ctx->cp_idx, 8 * need));
             ctx->cp_idx_n = need;
@@ -2273,7 +2291,7 @@ static int encode_two_phase_any(tdt_ctx *ctx, int mode, const uint8_t *d_in, con
         // Σ encode bounds = 2·(input bytes) + n·(28 + 4·ws)
         const uint64_t bound = 2 * (h2[1] - h2[0]) + (uint64_t)n_msgs * (28 + 4ull * (uint64_t)ctx->cfg.word_size + 4);
         if (bound > ctx->cp_bytes) {
-            if (ctx->cp_buf) HIPCHK(hipFree(ctx->cp_buf));
+            HIPCHK(cp_drop(ctx, ctx->cp_buf));
             ctx->cp_buf = nullptr;
             HIPCHK(hipMalloc(&ctx->cp_buf, bound));
             ctx->cp_bytes = bound;
@@ -2310,7 +2328,7 @@ int tdt_encode_batch(tdt_ctx *ctx, const uint8_t *d_in, const uint64_t *d_in_off
         std::lock_guard<std::mutex> lk(ctx->mu);
         const size_t need = 2ull * n_msgs + 2;
         if (need > ctx->cp_idx_n) {
-            if (ctx->cp_idx) HIPCHK(hipFree(ctx->cp_idx));
+            HIPCHK(cp_drop(ctx, ctx->cp_idx));
             ctx->cp_idx = nullptr;
             HIPCHK(hipMalloc(&ctx->cp_idx, 8 * need));
             ctx->cp_idx_n = need;
@@ -2338,7 +2356,7 @@ int tdt_encode_batch(tdt_ctx *ctx, const uint8_t *d_in, const uint64_t *d_in_off
     {
         std::lock_guard<std::mutex> lk(ctx->mu);
         if (bound > ctx->cp_bytes) {
-            if (ctx->cp_buf) HIPCHK(hipFree(ctx->cp_buf));
+            HIPCHK(cp_drop(ctx, ctx->cp_buf));
             ctx->cp_buf = nullptr;
             HIPCHK(hipMalloc(&ctx->cp_buf, bound));
             ctx->cp_bytes = bound;
@@ -2391,7 +2409,7 @@ int tdt_decode_batch(tdt_ctx *ctx, const uint8_t *d_in, const uint64_t *d_in_off
             std::lock_guard<std::mutex> lk(ctx->mu);
             const size_t need = 2ull * n_msgs + 2;
             if (need > ctx->cp_idx_n) {
-                if (ctx->cp_idx) HIPCHK(hipFree(ctx->cp_idx));
+                HIPCHK(cp_drop(ctx, ctx->cp_idx));
                 ctx->cp_idx = nullptr;
                 HIPCHK(hipMalloc(&ctx->cp_idx, 8 * need));
                 ctx->cp_idx_n = need;
@@ -2445,6 +2463,86 @@ int tdt_encode_batch_vw(tdt_ctx *ctx, const uint8_t *const *d_msgs, const uint64
     const Scatter v{reinterpret_cast<const uint64_t *>(d_msgs), d_sizes, reinterpret_cast<const uint64_t *>(d_blobs),
                     d_blob_cap};
     return encode_mixed(ctx, v, d_word_size, width_mask, n_msgs, d_out_len, d_status, (hipStream_t)stream);
+}
+
+// lengths → d_out_off, scanned in place, then the byte-balanced pack kernel (tdt_pack.h)
+static int pack_common(tdt_ctx *ctx, const uint64_t *d_blobs, const uint64_t *d_blob_len, uint32_t n_msgs, uint8_t *d_out,
+                       uint64_t out_cap, uint64_t *d_out_off, int32_t *d_status, bool keep_errors, hipStream_t s) {
+    hipLaunchKernelGGL(cp_len_kernel, dim3((n_msgs + 255) / 256), dim3(256), 0, s, d_blob_len, d_out_off, n_msgs);
+    HIPCHK(hipGetLastError());
+    if (int st = scan_sizes(ctx, d_out_off, n_msgs, s)) return st;  // exclusive, total at [n]
+    HIPCHK((hipError_t)psy::launch_pack(d_blobs, d_out_off, n_msgs, d_out, out_cap, d_status, keep_errors, ctx->pack_cut,
+                                        ctx->pack_grid, s));
+    return TDT_OK;
+}
+
+int tdt_pack_v(tdt_ctx *ctx, const uint8_t *const *d_blobs, const uint64_t *d_blob_len, uint32_t n_msgs, uint8_t *d_out,
+               uint64_t out_cap, uint64_t *d_out_off, int32_t *d_status, void *stream) {
+    if (!ctx) return set_err(TDT_E_ARG, "null context");
+    if (n_msgs == 0) return TDT_OK;
+    if (!d_blobs || !d_blob_len || !d_out_off) return set_err(TDT_E_ARG, "null pointer, length or offset array");
+    if (!d_out && out_cap) return set_err(TDT_E_ARG, "null output");
+    HIPCHK(hipSetDevice(ctx->device));
+    return pack_common(ctx, reinterpret_cast<const uint64_t *>(d_blobs), d_blob_len, n_msgs, d_out, out_cap, d_out_off,
+                       d_status, false, (hipStream_t)stream);
+}
+
+int tdt_encode_batch_vp(tdt_ctx *ctx, const uint8_t *const *d_msgs, const uint64_t *d_sizes, const int32_t *d_word_size,
+                        uint64_t width_mask, uint32_t n_msgs, uint64_t total_bytes, uint8_t *d_out, uint64_t out_cap,
+                        uint64_t *d_out_off, int32_t *d_status, void *stream) {
+    if (!ctx) return set_err(TDT_E_ARG, "null context");
+    if (n_msgs == 0) return TDT_OK;
+    if (!d_msgs || !d_sizes || !d_out_off) return set_err(TDT_E_ARG, "null pointer, size or offset array");
+    if (!d_out && out_cap) return set_err(TDT_E_ARG, "null output");
+    uint64_t wmax = (uint64_t)ctx->cfg.word_size;
+    if (d_word_size) {
+        psy::MixedRoutes R{};
+        if (!psy::mixed_routes(width_mask, n_msgs, R))
+            return set_err(TDT_E_ARG, "width_mask must name between 1 and 8 word sizes");
+        wmax = 64u - (uint64_t)__builtin_clzll(width_mask);
+    }
+    if (total_bytes > (1ull << 62)) return set_err(TDT_E_ARG, "total_bytes too large");
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(hipSetDevice(ctx->device));
+    // the scratch: every blob in a slot of its encode bound, Σ bounds <= 2·total_bytes + n·(28 + 4·wmax)
+    const uint64_t need = 2 * total_bytes + (uint64_t)n_msgs * (28 + 4 * wmax);
+    const size_t need_idx = 4ull * n_msgs + 2;
+    uint8_t *buf;
+    uint64_t buf_bytes, *idx;
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        if (capturing(s)) ctx->cp_in_graph = true;
+        if (need_idx > ctx->cp_idx_n) {
+            if (int st = no_growth_in_capture(s)) return st;
+            HIPCHK(cp_drop(ctx, ctx->cp_idx));
+            ctx->cp_idx = nullptr;
+            ctx->cp_idx_n = 0;
+            HIPCHK(hipMalloc(&ctx->cp_idx, 8 * need_idx));
+            ctx->cp_idx_n = need_idx;
+        }
+        if (need > ctx->cp_bytes) {
+            if (int st = no_growth_in_capture(s)) return st;
+            HIPCHK(cp_drop(ctx, ctx->cp_buf));
+            ctx->cp_buf = nullptr;
+            ctx->cp_bytes = 0;
+            HIPCHK(hipMalloc(&ctx->cp_buf, need));
+            ctx->cp_bytes = need;
+        }
+        buf = ctx->cp_buf, buf_bytes = ctx->cp_bytes, idx = ctx->cp_idx;
+    }
+    uint64_t *slot = idx, *ptr = idx + n_msgs + 1, *cap = ptr + n_msgs, *len = cap + n_msgs;
+    HIPCHK((hipError_t)psy::launch_pack_bounds(d_sizes, d_word_size, ctx->cfg.word_size, width_mask, slot, n_msgs, s));
+    if (int st = scan_sizes(ctx, slot, n_msgs, s)) return st;
+    // (a slot that would end past the scratch — total_bytes was understated — gets capacity 0:
+    // TDT_E_CAPACITY for that message, never a write outside the scratch)
+    HIPCHK((hipError_t)psy::launch_pack_slots(slot, buf, buf_bytes, ptr, cap, n_msgs, s));
+    const Scatter v{reinterpret_cast<const uint64_t *>(d_msgs), d_sizes, ptr, cap};
+    const int st = d_word_size ? encode_mixed(ctx, v, d_word_size, width_mask, n_msgs, len, d_status, s)
+                               : encode_common(ctx, psy::MODE_ENCODE, nullptr, nullptr, n_msgs, nullptr, nullptr, 0, nullptr,
+                                               d_status, nullptr, nullptr, nullptr, stream, nullptr, len, nullptr, nullptr,
+                                               -1, &v);
+    if (st) return st;
+    return pack_common(ctx, ptr, len, n_msgs, d_out, out_cap, d_out_off, d_status, true, s);
 }
 
 int tdt_decode_batch_v(tdt_ctx *ctx, const uint8_t *const *d_blobs, const uint64_t *d_blob_len, uint32_t n_msgs,

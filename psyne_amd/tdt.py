@@ -301,6 +301,43 @@ class TdtCodec:
                                             self._stream(stream)))
         return sizes[:n], status[:n]
 
+    # ---- packed wire buffer (blobs back to back, one copy or send per batch) ----------------
+    def pack_v(self, ptrs, lengths, out, out_offsets=None, status=None, stream=None):
+        """Pack blob i = lengths[i] bytes at address ptrs[i] (int64 tensors on the GPU: the slots and
+        lengths of encode_into, or the blobs of encode_v / encode_vw) into out[offsets[i]:offsets[i+1]],
+        offsets (n + 1, int64, device) being the prefix sum of the lengths.  A blob that ends past
+        out.numel() gets status 5 (TDT_E_CAPACITY) and is not copied; offsets[n] is the full need
+        either way.  Returns (out_offsets, status)."""
+        import torch
+        n = lengths.numel()
+        if out_offsets is None:
+            out_offsets = torch.zeros(n + 1, dtype=torch.int64, device=lengths.device)
+        if status is None:
+            status = torch.zeros(max(n, 1), dtype=torch.int32, device=lengths.device)
+        check(self._lib.tdt_pack_v(self._h, _ptr(ptrs), _ptr(lengths), n, _ptr(out), out.numel(), _ptr(out_offsets),
+                                   _ptr(status), self._stream(stream)))
+        return out_offsets, status
+
+    def encode_vp(self, ptrs, sizes, total_bytes, out, word_sizes=None, width_mask=0, out_offsets=None, status=None,
+                  stream=None):
+        """encode_v (word_sizes None) or encode_vw (word_sizes an int32 tensor on the GPU, width_mask
+        as there) into the packed buffer `out`: blob i at out[offsets[i]:offsets[i+1]].  total_bytes
+        (a host int) is an upper bound of sizes.sum(): it sizes the codec's scratch, and the host
+        reads nothing back.  A blob that ends past out.numel() gets status 5 (TDT_E_CAPACITY);
+        offsets[n] is the full need either way.  Returns (out_offsets, status)."""
+        import torch
+        n = sizes.numel()
+        if n and word_sizes is not None and word_sizes.dtype != torch.int32:
+            raise ValueError("word_sizes must be an int32 tensor")
+        if out_offsets is None:
+            out_offsets = torch.zeros(n + 1, dtype=torch.int64, device=sizes.device)
+        if status is None:
+            status = torch.zeros(max(n, 1), dtype=torch.int32, device=sizes.device)
+        check(self._lib.tdt_encode_batch_vp(self._h, _ptr(ptrs), _ptr(sizes), _ptr(word_sizes), int(width_mask), n,
+                                            int(total_bytes), _ptr(out), out.numel(), _ptr(out_offsets), _ptr(status),
+                                            self._stream(stream)))
+        return out_offsets, status
+
     @staticmethod
     def _tensor_table(tensors):
         """(addresses, byte sizes) of a list of contiguous GPU tensors, as host int64 arrays."""
@@ -313,7 +350,7 @@ class TdtCodec:
         ptrs = np.array([t.data_ptr() if s else 0 for t, s in zip(tensors, sizes)], dtype=np.uint64).view(np.int64)
         return ptrs, sizes
 
-    def encode_tensors(self, tensors, out=None, stream=None, word_sizes=None):
+    def encode_tensors(self, tensors, out=None, stream=None, word_sizes=None, packed=False):
         """Encode a list of contiguous GPU tensors (message i = the bytes of tensors[i]) without
         packing them: blob i goes to out[slots[i]:slots[i+1]], the slots being the prefix sum of the
         encode bounds.  Returns (out, slots, lengths, status).
@@ -326,7 +363,17 @@ class TdtCodec:
                     float64 / int64, 1 for uint8), in one call;
           ints      one width in 1..64 per tensor.
         With widths, at most 8 different ones may occur in a call; blob i is what a codec of that
-        word_size gives.  decode_tensors needs no widths: blobs carry theirs."""
+        word_size gives.  decode_tensors needs no widths: blobs carry theirs.
+
+        packed=True gives the wire form instead: the blobs back to back in `out`, and the return value
+        is (out, offsets, status) with offsets holding n + 1 entries on the GPU, so that
+        out[:offsets[n]] is what one copy or one send ships.  The round trip:
+            out, offsets, status = codec.encode_tensors(tensors, packed=True)
+            codec.decode_tensors(out, offsets, offsets[1:] - offsets[:-1], outs)
+        `out` defaults to the sum of the encode bounds, as in the slotted form: TDT does not fall back
+        to the raw bytes when its run-length streams grow, so a blob of incompressible records reaches
+        28 + 4*ws + 2*size and a buffer of the sizes plus a margin would not hold it.  A smaller `out`
+        may be passed: a blob that ends past it gets status 5 and offsets[n] still reports the need."""
         import torch
         ptrs, sizes = self._tensor_table(tensors)
         n = len(tensors)
@@ -349,6 +396,17 @@ class TdtCodec:
             ws = widths.astype(np.int64)
         slots = np.zeros(n + 1, np.int64)
         np.cumsum(np.maximum(sizes + 4, 28 + 4 * ws + 2 * sizes), out=slots[1:])
+        if packed:
+            if out is None:
+                out = torch.empty(max(int(slots[-1]), 1), dtype=torch.uint8, device=dev)
+            parts = [ptrs, sizes]  # one upload: addresses | sizes (| widths, two per word)
+            if widths is not None:
+                parts.append(np.concatenate([widths, np.zeros(n % 2, np.int32)]).view(np.int64))
+            d = torch.from_numpy(np.concatenate(parts)).to(dev, non_blocking=False)
+            dw = d[2 * n:].view(torch.int32)[:n] if widths is not None and n else None
+            offsets, status = self.encode_vp(d[:n], d[n:2 * n], int(sizes.sum()), out, word_sizes=dw,
+                                             width_mask=mask if dw is not None else 0, stream=stream)
+            return out, offsets, status
         if out is None:
             out = torch.empty(max(int(slots[-1]), 1), dtype=torch.uint8, device=dev)
         elif out.numel() < int(slots[-1]):
