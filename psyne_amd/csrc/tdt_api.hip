@@ -24,6 +24,7 @@
 #include "tdt_copypool.h"
 #include "tdt_decode.h"
 #include "tdt_encode.h"
+#include "tdt_grow.h"
 #include "tdt_pack.h"
 #include "tdt_plan.h"
 #include "tdt_slots.h"
@@ -82,6 +83,37 @@ int no_growth_in_capture(hipStream_t s) {
     if (!capturing(s)) return TDT_OK;
     return set_err(TDT_E_CAPTURE, "workspace too small for this batch under stream capture: issue one eager call "
                                   "of the same batch size on this context before capturing");
+}
+
+// The grower's callables (psy::grow, tdt_grow.h).  Allocation: `unit` bytes per counted element.
+int hip_status(hipError_t e, const char *what) {
+    return e == hipSuccess ? TDT_OK : set_err(TDT_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+struct DevAlloc {
+    size_t unit = 1;
+    template <class T>
+    int operator()(T **p, size_t cap) const { return hip_status(hipMalloc(p, unit * cap), "hipMalloc"); }
+};
+struct PinAlloc {
+    size_t unit = 1;
+    unsigned flags = hipHostMallocDefault;
+    template <class T>
+    int operator()(T **p, size_t cap) const { return hip_status(hipHostMalloc(p, unit * cap, flags), "hipHostMalloc"); }
+};
+// Dropping the old buffer: freed (the device waits for everything queued), or retired to a list its
+// owner frees with itself — a graph captured earlier, or calls still queued, may point at it.
+int dev_free(void *p) { return hip_status(hipFree(p), "hipFree"); }
+int pin_free(void *p) { return hip_status(hipHostFree(p), "hipHostFree"); }
+auto retire_to(std::vector<void *> &list) {
+    return [&list](void *p) { return list.push_back(p), TDT_OK; };
+}
+// A device buffer that a graph captured on the context may point at: it does not grow under
+// capture (no_growth_in_capture), and the buffer it replaces is retired
+template <class T, class S>
+int grow_retiring(T *&p, S &have, size_t need, size_t cap, std::vector<void *> &retired, hipStream_t s, size_t unit = 1) {
+    if (need <= have) return TDT_OK;
+    if (int st = no_growth_in_capture(s)) return st;
+    return psy::grow(p, have, need, cap, retire_to(retired), DevAlloc{unit});
 }
 
 }  // namespace
@@ -190,7 +222,7 @@ struct tdt_ctx {
         hipEvent_t ev = nullptr;
         uint8_t *dev = nullptr;
         size_t dev_bytes = 0;
-        uint64_t *pin = nullptr;  // pinned: in_off (n+1) | out_off (n+1) | status (n, int32 pairs)
+        uint64_t *pin = nullptr;  // pinned: in_off (n+1) | slots (n+1) | out_off or lengths (n+1) | status (n int32)
         size_t pin_words = 0;
         uint32_t *flag = nullptr;  // pinned: the last chunk's device error flags
         uint8_t *stage_in = nullptr, *stage_out = nullptr;  // pinned staging for pageable callers
@@ -267,15 +299,7 @@ constexpr size_t kCounterBytes = 64;
 // compacted decode (one u32 per message, tdt_anyws.h)
 int ensure_ws(tdt_ctx *c, uint32_t n_msgs, hipStream_t s) {
     const size_t need = kCounterBytes + 8ull * (n_msgs + 1) + 4ull * n_msgs;
-    if (need > c->ws_bytes) {
-        if (int st = no_growth_in_capture(s)) return st;
-        if (c->ws) c->retired.push_back(c->ws);  // (a graph captured earlier may use it)
-        c->ws = nullptr;
-        size_t cap = std::max<size_t>(need, c->ws_bytes * 2);
-        HIPCHK(hipMalloc(&c->ws, cap));
-        c->ws_bytes = cap;
-    }
-    return TDT_OK;
+    return grow_retiring(c->ws, c->ws_bytes, need, psy::cap_double(need, c->ws_bytes), c->retired, s);
 }
 
 bool ws_supported(int ws) { return psy::anyws_tuned(ws) || (PSY_HAVE_ANYWS && psy::anyws_generic(ws)); }
@@ -436,15 +460,7 @@ uint32_t pow2_at_least(uint64_t x, uint32_t lo, uint32_t hi) {
 
 int ensure_plan(PlanWS &w, uint32_t n, hipStream_t s, bool scattered = false) {
     const size_t need = psy::plan_layout(n, scattered).bytes;
-    if (need > w.bytes) {
-        if (int st = no_growth_in_capture(s)) return st;
-        if (w.buf) w.retired.push_back(w.buf);  // (a graph captured earlier may use it)
-        w.buf = nullptr;
-        const size_t cap = std::max(need, w.bytes * 2);
-        HIPCHK(hipMalloc(&w.buf, cap));
-        w.bytes = cap;
-    }
-    return TDT_OK;
+    return grow_retiring(w.buf, w.bytes, need, psy::cap_double(need, w.bytes), w.retired, s);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -853,6 +869,41 @@ __global__ __launch_bounds__(256) void tdt_route_kernel(RouteArgs t) {
         if (threadIdx.x == k && k < t.n_routes && t.bytes[k] && s_sum[k]) atomicAdd(t.bytes[k], s_sum[k]);
 }
 
+// Where a batch call runs.  What it works on goes in psy::EncodeArgs / psy::DecodeArgs, whose
+// caller-visible fields the entry points fill by name (in, in_off, n_msgs, out, out_cap, out_off,
+// status, mapping_in, hist_out, ent_out, map_out, slot_off, out_len, in_len, sizes_out).
+struct Where {
+    hipStream_t stream = nullptr;
+    uint8_t *wsp = nullptr;     // an explicit workspace (host-pipeline slots own theirs); null: the context's
+    PlanWS *pws = nullptr;      // the slotted calls' plan workspace; null: the context's
+    int small_teams = -1;       // look-back team shape (launch_encode)
+    const Scatter *v = nullptr; // a scattered batch: in, out and the offset tables are null
+    Where(void *s) : stream((hipStream_t)s) {}
+};
+
+// The fields no caller sets: the workspace's words (a null `wsp`: the one-message block, which
+// holds its own error flags) and, for encode, the context's policy.
+template <class Args>
+void wire_workspace(Args &a, uint8_t *wsp) {
+    a.ticket = reinterpret_cast<uint32_t *>(wsp);
+    a.errflags = reinterpret_cast<uint32_t *>(wsp) + 1;
+    a.lookback = reinterpret_cast<uint64_t *>(wsp + kCounterBytes);
+}
+void wire_encode(const tdt_ctx *c, psy::EncodeArgs &a, uint8_t *wsp) {
+    if (wsp) wire_workspace(a, wsp);
+    a.min_tensor = c->cfg.min_tensor_size;
+    a.policy_on = policy_on(c) ? 1 : 0;
+}
+// lookback: the one-pass route, whose deferred-blob list (generic word sizes) lies in the workspace
+// behind the look-back words (the slotted route keeps it in the plan buffer)
+void wire_decode(psy::DecodeArgs &a, uint8_t *wsp, bool lookback) {
+    wire_workspace(a, wsp);
+    if (PSY_HAVE_ANYWS && lookback) {
+        a.dlist = reinterpret_cast<uint32_t *>(wsp + kCounterBytes + 8ull * (a.n_msgs + 1));
+        a.dcount = reinterpret_cast<uint32_t *>(wsp) + 2;  // (zeroed with the counters by prep)
+    }
+}
+
 int tuned_index(int ws) { return ws == 1 ? 0 : ws == 2 ? 1 : ws == 4 ? 2 : ws == 8 ? 3 : 4; }
 int prep(tdt_ctx *c, uint32_t n_msgs, hipStream_t s, uint8_t *&wsp, bool lookback);  // (below)
 
@@ -870,14 +921,8 @@ int encode_mixed(tdt_ctx *c, const Scatter &v, const int32_t *d_word_size, uint6
     int st = prep(c, n, s, wsp, false);
     if (st) return st;
     // the workspaces: the tables of every width, and a plan buffer per tuned width
-    if (R.bytes > c->mx_bytes) {
-        if ((st = no_growth_in_capture(s))) return st;
-        if (c->mx_tab) c->retired.push_back(c->mx_tab);  // (a graph captured earlier may use it)
-        c->mx_tab = nullptr;
-        const size_t cap = std::max(R.bytes, c->mx_bytes * 2);
-        HIPCHK(hipMalloc(&c->mx_tab, cap));
-        c->mx_bytes = cap;
-    }
+    st = grow_retiring(c->mx_tab, c->mx_bytes, R.bytes, psy::cap_double(R.bytes, c->mx_bytes), c->retired, s);
+    if (st) return st;
     RouteArgs t{};
     t.v = v;
     t.ws = d_word_size;
@@ -910,11 +955,7 @@ int encode_mixed(tdt_ctx *c, const Scatter &v, const int32_t *d_word_size, uint6
     a.n_msgs = n;
     a.status = d_status;
     a.out_len = d_out_len;
-    a.ticket = reinterpret_cast<uint32_t *>(wsp);
-    a.errflags = reinterpret_cast<uint32_t *>(wsp) + 1;
-    a.lookback = reinterpret_cast<uint64_t *>(wsp + kCounterBytes);
-    a.min_tensor = c->cfg.min_tensor_size;
-    a.policy_on = policy_on(c) ? 1 : 0;
+    wire_encode(c, a, wsp);
     // one width after another on the caller's stream, each tuned one forking its own side stream
     for (int k = 0; k < R.n_routes; ++k) {
         const psy::MixedRoute &q = R.route[k];
@@ -1000,49 +1041,29 @@ int prep(tdt_ctx *c, uint32_t n_msgs, hipStream_t s, uint8_t *&wsp, bool lookbac
     return TDT_OK;
 }
 
-int encode_common(tdt_ctx *c, int mode, const uint8_t *d_in, const uint64_t *d_in_off, uint32_t n_msgs,
-                  const int32_t *d_mapping, uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_off,
-                  int32_t *d_status, uint32_t *d_hist, double *d_ent, int32_t *d_map, void *stream,
-                  const uint64_t *d_slot_off = nullptr, uint64_t *d_out_len = nullptr, uint8_t *wsp = nullptr,
-                  PlanWS *pws = nullptr, int small_teams = -1, const Scatter *v = nullptr) {
+int encode_common(tdt_ctx *c, int mode, psy::EncodeArgs a, const Where &w) {
+    const Scatter *v = w.v;
     if (!c) return set_err(TDT_E_ARG, "null context");
-    if (n_msgs == 0) return TDT_OK;
+    if (a.n_msgs == 0) return TDT_OK;
     if (v && !(v->ptr && v->size && v->out_ptr && v->out_cap)) return set_err(TDT_E_ARG, "null pointer or size array");
-    if (!v && !d_in_off) return set_err(TDT_E_ARG, "null input offsets");  // d_in may be null: all-empty batch
-    const bool slotted = d_slot_off != nullptr || v;  // (a scattered batch: d_in, d_out and the offsets are null)
-    if (!v && mode != psy::MODE_ANALYZE && (!d_out || (!slotted && !d_out_off))) return set_err(TDT_E_ARG, "null output");
-    if (mode == psy::MODE_MAPPED && !d_mapping) return set_err(TDT_E_ARG, "null mapping");
-    hipStream_t s = (hipStream_t)stream;
+    if (!v && !a.in_off) return set_err(TDT_E_ARG, "null input offsets");  // a.in may be null: all-empty batch
+    const bool slotted = a.slot_off != nullptr || v;
+    if (!v && mode != psy::MODE_ANALYZE && (!a.out || (!slotted && !a.out_off))) return set_err(TDT_E_ARG, "null output");
+    if (mode == psy::MODE_MAPPED && !a.mapping_in) return set_err(TDT_E_ARG, "null mapping");
+    hipStream_t s = w.stream;
     std::unique_lock<std::mutex> lk(c->mu, std::defer_lock);
+    uint8_t *wsp = w.wsp;
     if (!wsp) lk.lock();  // pipeline slots own their workspace
-    int st = prep(c, n_msgs, s, wsp, !slotted);
+    int st = prep(c, a.n_msgs, s, wsp, !slotted);
     if (st) return st;
-    psy::EncodeArgs a{};
-    a.in = d_in;
-    a.in_off = d_in_off;
-    a.n_msgs = n_msgs;
-    a.out = d_out;
-    a.out_cap = out_cap;
-    a.out_off = d_out_off;
-    a.status = d_status;
-    a.mapping_in = d_mapping;
-    a.hist_out = d_hist;
-    a.ent_out = d_ent;
-    a.map_out = d_map;
-    a.ticket = reinterpret_cast<uint32_t *>(wsp);
-    a.errflags = reinterpret_cast<uint32_t *>(wsp) + 1;
-    a.lookback = reinterpret_cast<uint64_t *>(wsp + kCounterBytes);
-    a.min_tensor = c->cfg.min_tensor_size;
-    a.policy_on = policy_on(c) ? 1 : 0;
-    a.slot_off = d_slot_off;
-    a.out_len = d_out_len;
+    wire_encode(c, a, wsp);
     if (mode == psy::MODE_ENCODE) {
-        st = slotted ? launch_slotted_any(c, pws ? *pws : c->pw, a, s, v)
-                     : launch_encode<psy::MODE_ENCODE, 1>(c, a, s, small_teams);
+        st = slotted ? launch_slotted_any(c, w.pws ? *w.pws : c->pw, a, s, v)
+                     : launch_encode<psy::MODE_ENCODE, 1>(c, a, s, w.small_teams);
     } else if (mode == psy::MODE_MAPPED) {
-        st = launch_encode<psy::MODE_MAPPED, 1>(c, a, s, small_teams);
+        st = launch_encode<psy::MODE_MAPPED, 1>(c, a, s, w.small_teams);
     } else {
-        st = launch_encode<psy::MODE_ANALYZE, 1>(c, a, s, small_teams);
+        st = launch_encode<psy::MODE_ANALYZE, 1>(c, a, s, w.small_teams);
     }
     if (st) return st;
     HIPCHK(hipGetLastError());
@@ -1185,49 +1206,31 @@ int launch_decode_slotted(tdt_ctx *c, PlanWS &pw, psy::DecodeArgs a, hipStream_t
     return launch_any_decode(a, (uint32_t)c->cus * 4u, s, PAIR);
 }
 
-int decode_common(tdt_ctx *c, bool sizes_only, const uint8_t *d_in, const uint64_t *d_in_off, uint32_t n_msgs,
-                  uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_off, uint64_t *d_sizes, int32_t *d_status,
-                  void *stream, const uint64_t *d_slot_off = nullptr, uint64_t *d_out_len = nullptr,
-                  const uint64_t *d_in_len = nullptr, uint8_t *wsp = nullptr, PlanWS *pws = nullptr,
-                  const Scatter *v = nullptr) {
+int decode_common(tdt_ctx *c, bool sizes_only, psy::DecodeArgs a, const Where &w) {
+    const Scatter *v = w.v;
+    const uint32_t n_msgs = a.n_msgs;
     if (!c) return set_err(TDT_E_ARG, "null context");
     if (n_msgs == 0) return TDT_OK;
     if (v && !(v->ptr && v->size && v->out_ptr && v->out_cap)) return set_err(TDT_E_ARG, "null pointer or size array");
-    if (!d_in_off) return set_err(TDT_E_ARG, "null input offsets");
-    const bool slotted = d_slot_off != nullptr || v;  // (a scattered batch: d_in_off / d_in_len are its blobs)
-    if (!sizes_only && !slotted && !d_out_off) return set_err(TDT_E_ARG, "null output offsets");
-    if (sizes_only && !d_sizes) return set_err(TDT_E_ARG, "null sizes");
-    hipStream_t s = (hipStream_t)stream;
+    if (!a.in_off) return set_err(TDT_E_ARG, "null input offsets");
+    const bool slotted = a.slot_off != nullptr || v;  // (a scattered batch: in_off / in_len are its blobs)
+    if (!sizes_only && !slotted && !a.out_off) return set_err(TDT_E_ARG, "null output offsets");
+    if (sizes_only && !a.sizes_out) return set_err(TDT_E_ARG, "null sizes");
+    hipStream_t s = w.stream;
     std::unique_lock<std::mutex> lk(c->mu, std::defer_lock);
+    uint8_t *wsp = w.wsp;
     if (!wsp) lk.lock();
-    int st = prep(c, n_msgs, s, wsp, !(slotted || sizes_only));
+    const bool lookback = !(slotted || sizes_only);
+    int st = prep(c, n_msgs, s, wsp, lookback);
     if (st) return st;
-    psy::DecodeArgs a{};
-    a.in = d_in;
-    a.in_off = d_in_off;
-    a.n_msgs = n_msgs;
-    a.out = d_out;
-    a.out_cap = out_cap;
-    a.out_off = d_out_off;
-    a.status = d_status;
-    a.sizes_out = d_sizes;
-    a.ticket = reinterpret_cast<uint32_t *>(wsp);
-    a.errflags = reinterpret_cast<uint32_t *>(wsp) + 1;
-    a.lookback = reinterpret_cast<uint64_t *>(wsp + kCounterBytes);
-    a.slot_off = d_slot_off;
-    a.out_len = d_out_len;
-    a.in_len = d_in_len;
+    wire_decode(a, wsp, lookback);
     if (sizes_only) {
         hipLaunchKernelGGL(psy::tdt_decode_sizes_kernel, dim3((n_msgs + 255) / 256), dim3(256), 0, s, a);
     } else if (slotted) {
-        st = v ? launch_decode_slotted<true>(c, pws ? *pws : c->pw, a, s, v)
-               : launch_decode_slotted(c, pws ? *pws : c->pw, a, s);
+        st = v ? launch_decode_slotted<true>(c, w.pws ? *w.pws : c->pw, a, s, v)
+               : launch_decode_slotted(c, w.pws ? *w.pws : c->pw, a, s);
         if (st) return st;
     } else {
-#if PSY_HAVE_ANYWS
-        a.dlist = reinterpret_cast<uint32_t *>(wsp + kCounterBytes + 8ull * (n_msgs + 1));
-        a.dcount = reinterpret_cast<uint32_t *>(wsp) + 2;  // (zeroed with the counters by prep)
-#endif
         launch_list(n_msgs, 64, [&](uint32_t, uint32_t g) {  // ids from the ticket
             hipLaunchKernelGGL((psy::tdt_decode_kernel<1>), dim3(g), dim3(64), 0, s, a);
         });
@@ -1239,14 +1242,7 @@ int decode_common(tdt_ctx *c, bool sizes_only, const uint8_t *d_in, const uint64
 }
 
 int ensure_host_dev(tdt_ctx *c, size_t bytes) {
-    if (bytes > c->h_dev_bytes) {
-        if (c->h_dev) HIPCHK(hipFree(c->h_dev));
-        c->h_dev = nullptr;
-        size_t cap = std::max(bytes, c->h_dev_bytes * 2);
-        HIPCHK(hipMalloc(&c->h_dev, cap));
-        c->h_dev_bytes = cap;
-    }
-    return TDT_OK;
+    return psy::grow(c->h_dev, c->h_dev_bytes, bytes, psy::cap_double(bytes, c->h_dev_bytes), dev_free, DevAlloc{});
 }
 
 size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
@@ -1289,39 +1285,20 @@ int ensure_slot(tdt_ctx *c, int k, size_t dev_bytes, size_t pin_words, size_t si
         HIPCHK(hipHostMalloc(&h.flag, 4, hipHostMallocDefault));
         *h.flag = 0;
     }
-    // growth takes 1.5x (whole MiB) and retires the old buffer until tdt_ctx_destroy instead of
-    // freeing it: a hipFree waits for the whole device (every stream, the other contexts' of
-    // the process too: a C1 loopback end stalled the other end's pipeline for milliseconds), and
-    // pinning host memory costs milliseconds, so buffers sized by the chunks of varying calls
-    // settle after a few (the retired ones sum to less than twice the last)
-    auto grown = [](size_t need, size_t have) {
-        return (std::max(need, have + have / 2) + (1u << 20) - 1) & ~size_t((1u << 20) - 1);
-    };
-    if (dev_bytes > h.dev_bytes) {
-        const size_t cap = grown(dev_bytes, h.dev_bytes);
-        if (h.dev) c->retired.push_back(h.dev);  // (the slot's earlier chunks are done: synced)
-        h.dev = nullptr;
-        h.dev_bytes = 0;
-        HIPCHK(hipMalloc(&h.dev, cap));
-        h.dev_bytes = cap;
-    }
-    auto pinned = [&](uint8_t *&buf, size_t &have, size_t need) -> int {
-        if (need <= have) return TDT_OK;
-        const size_t cap = grown(need, have);
-        if (buf) c->retired_host.push_back(buf);
-        buf = nullptr;
-        have = 0;
-        HIPCHK(hipHostMalloc(&buf, cap, hipHostMallocDefault));
-        have = cap;
-        return TDT_OK;
-    };
-    uint8_t *pw = reinterpret_cast<uint8_t *>(h.pin);
-    size_t pb = 8 * h.pin_words;
-    int st = pinned(pw, pb, 8 * pin_words);
+    // growth takes 1.5x (whole MiB, psy::cap_slot) and retires the old buffer until tdt_ctx_destroy
+    // instead of freeing it: a hipFree waits for the whole device (every stream, the other contexts'
+    // of the process too: a C1 loopback end stalled the other end's pipeline for milliseconds), and
+    // pinning host memory costs milliseconds
+    int st = psy::grow(h.dev, h.dev_bytes, dev_bytes, psy::cap_slot(dev_bytes, h.dev_bytes), retire_to(c->retired),
+                       DevAlloc{});  // (the slot's earlier chunks are done: synced)
     if (st) return st;
-    h.pin = reinterpret_cast<uint64_t *>(pw);
-    h.pin_words = pb / 8;
-    if ((st = pinned(h.stage_in, h.sin_bytes, sin)) || (st = pinned(h.stage_out, h.sout_bytes, sout))) return st;
+    auto pinned = [&](auto *&buf, size_t &have, size_t need, size_t unit) {
+        return psy::grow(buf, have, need, psy::cap_slot(unit * need, unit * have) / unit, retire_to(c->retired_host),
+                         PinAlloc{unit});
+    };
+    if ((st = pinned(h.pin, h.pin_words, pin_words, 8)) || (st = pinned(h.stage_in, h.sin_bytes, sin, 1)) ||
+        (st = pinned(h.stage_out, h.sout_bytes, sout, 1)))
+        return st;
     return TDT_OK;
 }
 
@@ -1556,8 +1533,63 @@ int host_loop(size_t nc, I &&issue, F &&finish) {
     return TDT_OK;
 }
 
-// msgs / sizes (gather input, tdt_encode_host_v): message i = msgs[i][0 .. sizes[i]); h_in is then
-// unused and h_in_off holds the prefix sums of sizes
+// A host call's input: one buffer with offsets, or (msgs / sizes: gather input, tdt_encode_host_v)
+// message i = msgs[i][0 .. sizes[i]), h_in then unused and h_in_off the prefix sums of sizes.
+// direct: the caller's memory is pinned and DMA'd as it is, not staged by the copy pool.
+struct HostIn {
+    const uint8_t *h_in;
+    const uint64_t *h_in_off;
+    const uint8_t *const *msgs;
+    const uint64_t *sizes;
+    bool direct;
+};
+// What a chunk's issue works with once its prologue is done
+struct ChunkView {
+    uint64_t *doff, *dslot, *dooff, *dlen;  // device: in_off, slots, out_off, lengths
+    int32_t *dst;                           // device: statuses
+    const uint8_t *src;        // the chunk's input in pinned memory (null: pinned gather input, copied run by run)
+    uint64_t slot_bytes;       // Σ slot sizes (0 without a slot table)
+    hipStream_t s_in, s_ex;    // the input copies' stream, the kernels' and read-backs' stream
+};
+// The prologue of a chunk's issue, encode and decode alike: the slot's buffers (stage_out bytes:
+// `sout`), the wait for the slot's previous chunk, the pinned offset table and — slots — the slot
+// table (slot_size(i): message i's slot, the encode bound or the decoded size), the staged input,
+// the chunk's device pointers and its two streams.
+template <class SlotSize>
+int chunk_prologue(tdt_ctx *c, const Chunk &k, size_t ci, const HostIn &in, size_t sout, bool slots, SlotSize &&slot_size,
+                   ChunkView &v) {
+    const int si = (int)(ci % kHostSlots);
+    auto &h = c->hs[si];
+    int st = ensure_slot(c, si, chunk_dev_bytes(k), chunk_pin_words(k), in.direct ? 0 : k.in_bytes, sout);
+    if (st || (st = sync_slot(c, h))) return st;  // (the slot's previous chunk is done with its buffers)
+    uint64_t *pin_in_off = h.pin, *pin_slot = pin_slots(h, k);
+    const uint64_t b0 = in.h_in_off[k.m0];
+    uint64_t acc = 0;
+    for (uint32_t i = 0; i <= k.n; ++i) {
+        pin_in_off[i] = in.h_in_off[k.m0 + i] - b0;
+        if (slots) {
+            pin_slot[i] = acc;
+            if (i < k.n) acc += slot_size(k.m0 + i);
+        }
+    }
+    v.src = in.msgs ? nullptr : in.h_in + b0;
+    if (!in.direct) {
+        if (in.msgs) c->pool->gather(h.stage_in, in.msgs + k.m0, in.sizes + k.m0, k.n);
+        else c->pool->copy(h.stage_in, v.src, k.in_bytes);
+        v.src = h.stage_in;
+    }
+    uint8_t *d = h.dev;
+    v.doff = reinterpret_cast<uint64_t *>(d + k.o_off);
+    v.dslot = v.doff + (k.n + 1);
+    v.dooff = reinterpret_cast<uint64_t *>(d + k.o_ooff);
+    v.dst = reinterpret_cast<int32_t *>(d + k.o_st);
+    v.dlen = reinterpret_cast<uint64_t *>(d + k.o_len);
+    v.slot_bytes = acc;
+    v.s_in = c->slot_streams ? h.stream : c->hin;
+    v.s_ex = c->slot_streams ? h.stream : c->hex;
+    return TDT_OK;
+}
+
 int host_encode(tdt_ctx *c, const uint8_t *h_in, const uint64_t *h_in_off, uint32_t n_msgs, uint8_t *h_out,
                 uint64_t out_cap, uint64_t *h_out_off, int32_t *h_status, const uint8_t *const *msgs = nullptr,
                 const uint64_t *sizes = nullptr) {
@@ -1587,77 +1619,61 @@ int host_encode(tdt_ctx *c, const uint8_t *h_in, const uint64_t *h_in_off, uint3
         ch.push_back(plan_chunk(h_in_off, m, n_msgs, true, !lb, ws, nullptr, cb));
         m += ch.back().n;
     }
-    if (ch.size() + 1 > c->hbases_n) {
-        if (c->hbases) HIPCHK(hipFree(c->hbases));
-        c->hbases = nullptr;
-        HIPCHK(hipMalloc(&c->hbases, 8 * (ch.size() + 1)));
-        c->hbases_n = ch.size() + 1;
-    }
+    if (int st = psy::grow(c->hbases, c->hbases_n, ch.size() + 1, psy::cap_exact(ch.size() + 1, c->hbases_n), dev_free,
+                           DevAlloc{8}))
+        return st;
     uint64_t base = 0;  // output bytes of the chunks finished so far
     bool capacity = false;
+    const HostIn in{h_in, h_in_off, msgs, sizes, pin_in || msgs_pinned};
+    auto bound_of = [&](uint32_t i) { return tdt_encode_bound(h_in_off[i + 1] - h_in_off[i], ws); };
     auto issue = [&](size_t ci) -> int {
         const Chunk &k = ch[ci];
-        const int si = (int)(ci % kHostSlots);
-        auto &h = c->hs[si];
-        int st = ensure_slot(c, si, chunk_dev_bytes(k), chunk_pin_words(k), pin_in || msgs_pinned ? 0 : k.in_bytes,
-                             pin_out ? 0 : k.cap);
+        auto &h = c->hs[ci % kHostSlots];
+        ChunkView v;
+        int st = chunk_prologue(c, k, ci, in, pin_out ? 0 : k.cap, k.scap != 0, bound_of, v);
         if (st) return st;
-        st = sync_slot(c, h);  // the slot's previous chunk is done with its buffers
-        if (st) return st;
-        uint64_t *pin_in_off = h.pin, *pin_slot = pin_slots(h, k);
-        const uint64_t b0 = h_in_off[k.m0];
-        uint64_t acc = 0;
-        for (uint32_t i = 0; i <= k.n; ++i) {
-            pin_in_off[i] = h_in_off[k.m0 + i] - b0;
-            if (k.scap) {
-                pin_slot[i] = acc;
-                if (i < k.n) acc += tdt_encode_bound(h_in_off[k.m0 + i + 1] - h_in_off[k.m0 + i], ws);
-            }
-        }
-        const uint8_t *src = msgs ? nullptr : h_in + b0;
-        if (msgs && !msgs_pinned) {
-            c->pool->gather(h.stage_in, msgs + k.m0, sizes + k.m0, k.n);
-            src = h.stage_in;
-        } else if (!msgs && !pin_in) {
-            c->pool->copy(h.stage_in, src, k.in_bytes);
-            src = h.stage_in;
-        }
         uint8_t *d = h.dev;
-        auto *doff = reinterpret_cast<uint64_t *>(d + k.o_off);
-        auto *dslot = doff + (k.n + 1);
-        auto *dooff = reinterpret_cast<uint64_t *>(d + k.o_ooff);
-        auto *dst = reinterpret_cast<int32_t *>(d + k.o_st);
-        auto *dlen = reinterpret_cast<uint64_t *>(d + k.o_len);
-        const hipStream_t s_in = c->slot_streams ? h.stream : c->hin, s_ex = c->slot_streams ? h.stream : c->hex;
-        if (src) {
-            HIPCHK(hipMemcpyAsync(d, src, k.in_bytes, hipMemcpyHostToDevice, s_in));
-        } else {
+        const hipStream_t s_in = v.s_in, s_ex = v.s_ex;
+        if (v.src) {
+            HIPCHK(hipMemcpyAsync(d, v.src, k.in_bytes, hipMemcpyHostToDevice, s_in));
+        } else {  // pinned gather input: DMA'd run by run of adjacent messages
             for (uint32_t i = 0; i < k.n;) {
                 const uint8_t *p0 = msgs[k.m0 + i];
                 uint64_t len = sizes[k.m0 + i];
                 uint32_t j = i + 1;
                 while (j < k.n && msgs[k.m0 + j] == p0 + len) len += sizes[k.m0 + j++];
-                if (len) HIPCHK(hipMemcpyAsync(d + pin_in_off[i], p0, len, hipMemcpyHostToDevice, s_in));
+                if (len) HIPCHK(hipMemcpyAsync(d + h.pin[i], p0, len, hipMemcpyHostToDevice, s_in));
                 i = j;
             }
         }
         // in_off and (slotted) the slots: one copy
-        HIPCHK(hipMemcpyAsync(doff, pin_in_off, (k.scap ? 16ull : 8ull) * (k.n + 1), hipMemcpyHostToDevice, s_in));
+        HIPCHK(hipMemcpyAsync(v.doff, h.pin, (k.scap ? 16ull : 8ull) * (k.n + 1), hipMemcpyHostToDevice, s_in));
         if (s_in != s_ex) {
             HIPCHK(hipEventRecord(h.evi, s_in));
             HIPCHK(hipStreamWaitEvent(s_ex, h.evi, 0));
         }
+        psy::EncodeArgs a{};
+        a.in = d;
+        a.in_off = v.doff;
+        a.n_msgs = k.n;
+        a.status = v.dst;
+        Where w(s_ex);
+        w.wsp = d + k.o_ws;
         if (k.scap) {
-            st = encode_common(c, psy::MODE_ENCODE, d, doff, k.n, nullptr, d + k.o_sbuf, k.scap, nullptr, dst, nullptr,
-                               nullptr, nullptr, s_ex, dslot, dlen, d + k.o_ws, &h.pw);
-            if (st) return st;
-            hipLaunchKernelGGL(host_scan_kernel, dim3(1), dim3(1024), 0, s_ex, dlen, dooff, k.n);
+            a.out = d + k.o_sbuf;
+            a.out_cap = k.scap;
+            a.slot_off = v.dslot;
+            a.out_len = v.dlen;
+            w.pws = &h.pw;
+            if ((st = encode_common(c, psy::MODE_ENCODE, a, w))) return st;
+            hipLaunchKernelGGL(host_scan_kernel, dim3(1), dim3(1024), 0, s_ex, v.dlen, v.dooff, k.n);
             HIPCHK(hipGetLastError());
         } else {
-            st = encode_common(c, psy::MODE_ENCODE, d, doff, k.n, nullptr, d + k.o_out, k.cap, dooff, dst, nullptr,
-                               nullptr, nullptr, s_ex, nullptr, nullptr, d + k.o_ws, nullptr,
-                               k.in_bytes <= kSmallMax * k.n ? 1 : 0);  // (the chunk's sizes are host data)
-            if (st) return st;
+            a.out = d + k.o_out;
+            a.out_cap = k.cap;
+            a.out_off = v.dooff;
+            w.small_teams = k.in_bytes <= kSmallMax * k.n ? 1 : 0;  // (the chunk's sizes are host data)
+            if ((st = encode_common(c, psy::MODE_ENCODE, a, w))) return st;
         }
         // the output, in chunk order (each copy follows the previous chunk's: the running base)
         if (ci == 0) HIPCHK(hipMemsetAsync(c->hbases, 0, 8, s_ex));
@@ -1666,16 +1682,16 @@ int host_encode(tdt_ctx *c, const uint8_t *h_in, const uint64_t *h_in_off, uint3
         if (k.scap) {
             const uint32_t P = (uint32_t)std::min<uint64_t>(64, std::max<uint64_t>(1, k.in_bytes / k.n / 16384));
             const uint32_t grid = (uint32_t)std::min<uint64_t>(2048, ((uint64_t)k.n * P + 3) / 4);
-            hipLaunchKernelGGL(host_gather_kernel, dim3(grid), dim3(256), 0, s_ex, d + k.o_sbuf, dslot, dlen, dooff,
+            hipLaunchKernelGGL(host_gather_kernel, dim3(grid), dim3(256), 0, s_ex, d + k.o_sbuf, v.dslot, v.dlen, v.dooff,
                                k.n, P, odst, c->hbases, (uint32_t)ci, out_cap, pin_out ? 1 : 0);
         } else {
             const uint32_t grid = (uint32_t)std::min<uint64_t>(1024, k.cap / 4096 + 1);
-            hipLaunchKernelGGL(host_out_kernel, dim3(grid), dim3(256), 0, s_ex, d + k.o_out, dooff, k.n, odst,
+            hipLaunchKernelGGL(host_out_kernel, dim3(grid), dim3(256), 0, s_ex, d + k.o_out, v.dooff, k.n, odst,
                                c->hbases, (uint32_t)ci, out_cap, pin_out ? 1 : 0);
         }
         HIPCHK(hipGetLastError());
         if (c->slot_streams) HIPCHK(hipEventRecord(h.evc, s_ex));
-        if ((st = small_copies(s_ex, d + k.o_ws + 4, h.flag, 4, dooff, pin_back(h, k), 8ull * (k.n + 1), dst,
+        if ((st = small_copies(s_ex, d + k.o_ws + 4, h.flag, 4, v.dooff, pin_back(h, k), 8ull * (k.n + 1), v.dst,
                                pin_status(h, k), 4ull * k.n)))
             return st;
         HIPCHK(hipEventRecord(h.ev, s_ex));
@@ -1735,45 +1751,37 @@ int host_decode(tdt_ctx *c, const uint8_t *h_in, const uint64_t *h_in_off, uint3
     }
     std::vector<uint64_t> lens(n_msgs);
     std::vector<int32_t> stv(n_msgs);
+    const HostIn in{h_in, h_in_off, nullptr, nullptr, pin_in};
     auto issue = [&](size_t ci) -> int {
         const Chunk &k = ch[ci];
-        const int si = (int)(ci % kHostSlots);
-        auto &h = c->hs[si];
-        int st = ensure_slot(c, si, chunk_dev_bytes(k), chunk_pin_words(k), pin_in ? 0 : k.in_bytes, pin_out ? 0 : k.cap);
+        auto &h = c->hs[ci % kHostSlots];
+        ChunkView v;
+        int st = chunk_prologue(c, k, ci, in, pin_out ? 0 : k.cap, true, [&](uint32_t i) { return dsz[i]; }, v);
         if (st) return st;
-        st = sync_slot(c, h);
-        if (st) return st;
-        uint64_t *pin_in_off = h.pin, *pin_slot = pin_slots(h, k);
-        const uint64_t b0 = h_in_off[k.m0];
-        uint64_t acc = 0;
-        for (uint32_t i = 0; i <= k.n; ++i) {
-            pin_in_off[i] = h_in_off[k.m0 + i] - b0;
-            pin_slot[i] = acc;
-            if (i < k.n) acc += dsz[k.m0 + i];
-        }
-        const uint8_t *src = h_in + b0;
-        if (!pin_in) {
-            c->pool->copy(h.stage_in, src, k.in_bytes);
-            src = h.stage_in;
-        }
         uint8_t *d = h.dev;
-        auto *doff = reinterpret_cast<uint64_t *>(d + k.o_off);
-        auto *dslot = doff + (k.n + 1);
-        auto *dst = reinterpret_cast<int32_t *>(d + k.o_st);
-        auto *dlen = reinterpret_cast<uint64_t *>(d + k.o_len);
+        const uint64_t acc = v.slot_bytes;  // the chunk's decoded bytes
         // input copies in chunk order, each after the previous chunk's: concurrent copies of
         // several slots share the link and all land late, the earliest-needed one included
         // (decode 31 -> 37 GiB/s pinned; the same ordering cost host_encode 44 -> 36 GiB/s,
         // profiles/r05_diag/host_decode/)
-        const hipStream_t s_in = c->slot_streams ? h.stream : c->hin, s_ex = c->slot_streams ? h.stream : c->hex;
+        const hipStream_t s_in = v.s_in, s_ex = v.s_ex;
         if (ci > 0 && c->slot_streams) HIPCHK(hipStreamWaitEvent(s_in, c->hs[(ci - 1) % kHostSlots].evi, 0));
-        HIPCHK(hipMemcpyAsync(d, src, k.in_bytes, hipMemcpyHostToDevice, s_in));
-        HIPCHK(hipMemcpyAsync(doff, pin_in_off, 16ull * (k.n + 1), hipMemcpyHostToDevice, s_in));  // offsets + slots
+        HIPCHK(hipMemcpyAsync(d, v.src, k.in_bytes, hipMemcpyHostToDevice, s_in));
+        HIPCHK(hipMemcpyAsync(v.doff, h.pin, 16ull * (k.n + 1), hipMemcpyHostToDevice, s_in));  // offsets + slots
         HIPCHK(hipEventRecord(h.evi, s_in));
         if (s_in != s_ex) HIPCHK(hipStreamWaitEvent(s_ex, h.evi, 0));
-        st = decode_common(c, false, d, doff, k.n, d + k.o_out, 0, nullptr, nullptr, dst, s_ex, dslot, dlen,
-                           nullptr, d + k.o_ws, &h.pw);
-        if (st) return st;
+        psy::DecodeArgs a{};
+        a.in = d;
+        a.in_off = v.doff;
+        a.n_msgs = k.n;
+        a.out = d + k.o_out;
+        a.status = v.dst;
+        a.slot_off = v.dslot;
+        a.out_len = v.dlen;
+        Where w(s_ex);
+        w.wsp = d + k.o_ws;
+        w.pws = &h.pw;
+        if ((st = decode_common(c, false, a, w))) return st;
         if (acc && dma_out) {
             HIPCHK(hipMemcpyAsync(pin_out ? h_out + k.base : h.stage_out, d + k.o_out, acc, hipMemcpyDeviceToHost,
                                   s_ex));
@@ -1784,7 +1792,7 @@ int host_decode(tdt_ctx *c, const uint8_t *h_in, const uint64_t *h_in_off, uint3
                                s_ex, d + k.o_out, pin_out ? d_hout + k.base : h.stage_out, acc);
             HIPCHK(hipGetLastError());
         }
-        if ((st = small_copies(s_ex, d + k.o_ws + 4, h.flag, 4, dlen, pin_back(h, k), 8ull * k.n, dst,
+        if ((st = small_copies(s_ex, d + k.o_ws + 4, h.flag, 4, v.dlen, pin_back(h, k), 8ull * k.n, v.dst,
                                pin_status(h, k), 4ull * k.n)))
             return st;
         HIPCHK(hipEventRecord(h.ev, s_ex));
@@ -1836,17 +1844,11 @@ struct OneArgs {
 
 int ensure_one(tdt_ctx *c, size_t bytes) {
     if (!c->one_stream) HIPCHK(hipStreamCreateWithFlags(&c->one_stream, hipStreamNonBlocking));
-    if (bytes <= c->one_bytes) return TDT_OK;
-    if (c->one) HIPCHK(hipHostFree(c->one));
-    c->one = nullptr;
-    c->one_bytes = 0;
-    const size_t cap = std::max<size_t>(bytes, 64 * 1024);
     // coherent (fine-grained, uncached on the device): the kernel's result stores reach host
     // memory before the stream writes the completion word the host spins on, with no cache
     // write-back to order; the block is read and written once per call anyway
-    HIPCHK(hipHostMalloc(&c->one, cap, hipHostMallocCoherent));
-    c->one_bytes = cap;
-    return TDT_OK;
+    return psy::grow(c->one, c->one_bytes, bytes, std::max<size_t>(bytes, 64 * 1024), pin_free,
+                     PinAlloc{1, hipHostMallocCoherent});
 }
 
 template <int WS>
@@ -1914,9 +1916,8 @@ int host_one(tdt_ctx *c, bool encode, const uint8_t *h_in, const uint64_t *h_in_
         a.slot_off = dA->slot;
         a.out_len = const_cast<uint64_t *>(&dA->len);
         a.status = const_cast<int32_t *>(&dA->status);
+        wire_encode(c, a, nullptr);  // (no workspace: the block's own flag word)
         a.errflags = const_cast<uint32_t *>(&dA->flags);
-        a.min_tensor = c->cfg.min_tensor_size;
-        a.policy_on = policy_on(c) ? 1 : 0;
         a.list = &dA->list;
         a.list_count = &dA->cnt;
         if (!with_word_size(c->cfg.word_size, [&](auto W) { launch_one_encode<W()>(a, len, s); }))
@@ -1974,8 +1975,10 @@ int host_one(tdt_ctx *c, bool encode, const uint8_t *h_in, const uint64_t *h_in_
     return TDT_OK;
 }
 
+// msgs / sizes: gather input (encode, more than one message; HostIn)
 int host_path(tdt_ctx *c, bool encode, const uint8_t *h_in, const uint64_t *h_in_off, uint32_t n_msgs,
-              uint8_t *h_out, uint64_t out_cap, uint64_t *h_out_off, int32_t *h_status) {
+              uint8_t *h_out, uint64_t out_cap, uint64_t *h_out_off, int32_t *h_status,
+              const uint8_t *const *msgs = nullptr, const uint64_t *sizes = nullptr) {
     if (!c) return set_err(TDT_E_ARG, "null context");
     if (n_msgs == 0) {
         if (h_out_off) h_out_off[0] = 0;
@@ -1984,12 +1987,12 @@ int host_path(tdt_ctx *c, bool encode, const uint8_t *h_in, const uint64_t *h_in
     if (!h_in_off || !h_out_off) return set_err(TDT_E_ARG, "null offsets");
     HIPCHK(hipSetDevice(c->device));
     std::lock_guard<std::mutex> lk(c->hmu);  // the pipeline slots belong to the context
-    if (n_msgs == 1 && !c->no_one) {
+    if (n_msgs == 1 && !msgs && !c->no_one) {
         const int st1 = host_one(c, encode, h_in, h_in_off, h_out, out_cap, h_out_off, h_status);
         if (st1 >= 0) return st1;
     }
     if (!c->pool) c->pool.reset(new CopyPool(c->copy_threads));
-    const int st = encode ? host_encode(c, h_in, h_in_off, n_msgs, h_out, out_cap, h_out_off, h_status)
+    const int st = encode ? host_encode(c, h_in, h_in_off, n_msgs, h_out, out_cap, h_out_off, h_status, msgs, sizes)
                           : host_decode(c, h_in, h_in_off, n_msgs, h_out, out_cap, h_out_off, h_status);
     if (st != TDT_OK) {
         // an error mid-pipeline: the other slot's copies and kernels may still read the caller's
@@ -2003,7 +2006,6 @@ int host_path(tdt_ctx *c, bool encode, const uint8_t *h_in, const uint64_t *h_in
 }  // namespace
 
 namespace {
-// any message longer than `lim` bytes → *flag = 1 (one atomic per workgroup)
 // any message longer than `lim` bytes → *flag |= 1; any message that the resident-only kernel
 // cannot hold (unaligned start, a partial 16-byte group, over 64 KiB) → *flag |= 2 (one atomic
 // per workgroup and bit)
@@ -2041,12 +2043,47 @@ __global__ __launch_bounds__(256) void cp_gather_kernel(const uint8_t *src, cons
 static int scan_sizes(tdt_ctx *ctx, uint64_t *d_off, uint32_t n_msgs, hipStream_t stream);
 // A cp_buf / cp_idx buffer that a larger one replaces (under ctx->mu): freed, unless a captured
 // tdt_encode_batch_vp may still point at it — then it lives as long as the context.
-static hipError_t cp_drop(tdt_ctx *ctx, void *p) {
-    if (!p) return hipSuccess;
-    if (!ctx->cp_in_graph) return hipFree(p);
-    ctx->retired.push_back(p);
-    return hipSuccess;
+static int cp_drop(tdt_ctx *ctx, void *p) { return ctx->cp_in_graph ? retire_to(ctx->retired)(p) : dev_free(p); }
+// Room in the compaction buffers: idx_words u64 in cp_idx, buf_bytes in cp_buf (exact sizes), under
+// ctx->mu — the caller lets go of it before encode_common takes it.  capturable: the call may run
+// under stream capture (tdt_encode_batch_vp), where nothing grows and from which on nothing is freed.
+static int ensure_cp(tdt_ctx *ctx, size_t idx_words, size_t buf_bytes, hipStream_t s, bool capturable = false) {
+    if (capturable && capturing(s)) ctx->cp_in_graph = true;
+    auto room = [&](auto *&p, size_t &have, size_t need, size_t unit) -> int {
+        if (need <= have) return TDT_OK;
+        if (capturable)
+            if (int st = no_growth_in_capture(s)) return st;
+        return psy::grow(p, have, need, psy::cap_exact(need, have), [ctx](void *old) { return cp_drop(ctx, old); },
+                         DevAlloc{unit});
+    };
+    if (int st = room(ctx->cp_idx, ctx->cp_idx_n, idx_words, 8)) return st;
+    return room(ctx->cp_buf, ctx->cp_bytes, buf_bytes, 1);
 }
+// The caller-visible fields every batch over one input buffer sets; the rest by name at the call.
+template <class Args>
+static Args batch_args(const uint8_t *d_in, const uint64_t *d_in_off, uint32_t n_msgs, uint8_t *d_out, int32_t *d_status) {
+    Args a{};
+    a.in = d_in;
+    a.in_off = d_in_off;
+    a.n_msgs = n_msgs;
+    a.out = d_out;
+    a.status = d_status;
+    return a;
+}
+static const Scatter scatter_of(const uint8_t *const *d_ptr, const uint64_t *d_size, uint8_t *const *d_out_ptr,
+                                const uint64_t *d_out_cap) {
+    // (device addresses are 64 bits wide: a pointer table read as u64 is the offset table of a null base)
+    static_assert(sizeof(uint8_t *) == sizeof(uint64_t), "pointer tables are read as u64 offsets");
+    return {reinterpret_cast<const uint64_t *>(d_ptr), d_size, reinterpret_cast<const uint64_t *>(d_out_ptr), d_out_cap};
+}
+
+// lengths → d_out_off, scanned in place: exclusive offsets, the total at [n]
+static int scan_lengths(tdt_ctx *ctx, const uint64_t *d_len, uint64_t *d_out_off, uint32_t n_msgs, hipStream_t s) {
+    hipLaunchKernelGGL(cp_len_kernel, dim3((n_msgs + 255) / 256), dim3(256), 0, s, d_len, d_out_off, n_msgs);
+    HIPCHK(hipGetLastError());
+    return scan_sizes(ctx, d_out_off, n_msgs, s);
+}
+
 // The two-phase compaction reads a few bytes back to choose its path: not under stream capture
 // (the one-pass kernels need no read-back), nor with the no-two-phase knob.
 static bool two_phase_ok(const tdt_ctx *ctx, void *stream) {
@@ -2170,17 +2207,16 @@ int tdt_ctx_create(int device, const tdt_config *cfg, tdt_ctx **out) {
 void tdt_ctx_destroy(tdt_ctx *ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
-    if (ctx->ws) (void)hipFree(ctx->ws);
-    if (ctx->slot_sums) (void)hipFree(ctx->slot_sums);
-    if (ctx->cp_buf) (void)hipFree(ctx->cp_buf);
-    if (ctx->cp_idx) (void)hipFree(ctx->cp_idx);
+    // every buffer the grower replaces is either freed at once or retired to exactly one list
+    // (ctx->retired, ctx->retired_host, a PlanWS's own): the current buffers here, each list once
+    for (void *p : {(void *)ctx->ws, (void *)ctx->slot_sums, (void *)ctx->cp_buf, (void *)ctx->cp_idx, (void *)ctx->mx_tab,
+                    (void *)ctx->hbases})
+        if (p) (void)hipFree(p);
     for (void *p : ctx->retired) (void)hipFree(p);
     for (void *p : ctx->retired_host) (void)hipHostFree(p);
     ctx->pw.release();
     for (auto &w : ctx->mx_pw)
         if (w) w->release();
-    if (ctx->mx_tab) (void)hipFree(ctx->mx_tab);
-    if (ctx->hbases) (void)hipFree(ctx->hbases);
     if (ctx->one_stream) (void)hipStreamSynchronize(ctx->one_stream);
     if (ctx->one) (void)hipHostFree(ctx->one);
     if (ctx->one_stream) (void)hipStreamDestroy(ctx->one_stream);
@@ -2261,14 +2297,40 @@ uint64_t tdt_encode_bound(uint64_t n, int32_t word_size) {
 // successors waiting in the look-back would stall every CU (head-of-line blocking); batches of
 // small messages: the per-message ticket / look-back chain bounds the rate.  Both are encoded
 // slotted (the message-class kernels), then the lengths are scanned and the blobs gathered.
-// Compacted encode at a generic word size (tdt_anyws.h): always the two phases — slots, the
-// generic kernel into cp_buf, a scan of the lengths, the gather.  The scan's input needs the
-// batch's byte count on the host, so not under stream capture (nor with the no-two-phase knob).
-static int encode_two_phase_any(tdt_ctx *ctx, int mode, const uint8_t *d_in, const uint64_t *d_in_off, uint32_t n_msgs,
-                                const int32_t *d_mapping, uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_off,
-                                int32_t *d_status, void *stream) {
-    if (!d_in_off || !d_out || !d_out_off) return set_err(TDT_E_ARG, "null argument");
-    if (mode == psy::MODE_MAPPED && !d_mapping) return set_err(TDT_E_ARG, "null mapping");
+//
+// The two phases, once the host knows the batch's input bytes: the batch `a` (a compacted call's
+// fields) slotted into cp_buf, its lengths scanned into a.out_off, its blobs gathered into a.out.
+static int encode_two_phase(tdt_ctx *ctx, int mode, const psy::EncodeArgs &a, uint64_t in_bytes, void *stream) {
+    hipStream_t s = (hipStream_t)stream;
+    const uint32_t n = a.n_msgs;
+    // Σ encode bounds <= 2·(input bytes) + n·(28 + 4·ws) (and >= n + 4 per message)
+    const uint64_t bound = 2 * in_bytes + (uint64_t)n * (28 + 4ull * (uint64_t)ctx->cfg.word_size + 4);
+    psy::EncodeArgs e = a;  // the slotted call: no compacted output
+    e.out_cap = 0;
+    e.out_off = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        if (int st = ensure_cp(ctx, 2ull * n + 2, bound, s)) return st;
+        e.out = ctx->cp_buf;
+        e.slot_off = ctx->cp_idx;
+        e.out_len = ctx->cp_idx + n + 1;
+    }
+    int st = tdt_encode_slots(ctx, a.in_off, n, ctx->cp_idx, stream);
+    if (st) return st;
+    if ((st = encode_common(ctx, mode, e, Where(stream)))) return st;
+    if ((st = scan_lengths(ctx, e.out_len, a.out_off, n, s))) return st;
+    hipLaunchKernelGGL(cp_gather_kernel, dim3((n + 3) / 4), dim3(256), 0, s, e.out, e.slot_off, e.out_len, a.out, a.out_off,
+                       a.out_cap, a.status, n);
+    HIPCHK(hipGetLastError());
+    return TDT_OK;
+}
+
+// Compacted encode at a generic word size (tdt_anyws.h): always the two phases, the generic kernel
+// filling the slots.  The scratch is sized by the batch's byte count on the host, so not under
+// stream capture (nor with the no-two-phase knob).
+static int encode_two_phase_any(tdt_ctx *ctx, int mode, const psy::EncodeArgs &a, void *stream) {
+    if (!a.in_off || !a.out || !a.out_off) return set_err(TDT_E_ARG, "null argument");
+    if (mode == psy::MODE_MAPPED && !a.mapping_in) return set_err(TDT_E_ARG, "null mapping");
     if (!two_phase_ok(ctx, stream))
         return set_err(TDT_E_UNSUPPORTED, "compacted encode at a word size other than 1, 2, 4, 8, 16 reads the batch "
                                           "size back: not under stream capture or TDT_OPT_NO_TWO_PHASE (use the "
@@ -2276,63 +2338,26 @@ static int encode_two_phase_any(tdt_ctx *ctx, int mode, const uint8_t *d_in, con
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(hipSetDevice(ctx->device));
     uint64_t h2[2];
-    {
-        std::lock_guard<std::mutex> lk(ctx->mu);
-        const size_t need = 2ull * n_msgs + 2;
-        if (need > ctx->cp_idx_n) {
-            HIPCHK(cp_drop(ctx, ctx->cp_idx));
-            ctx->cp_idx = nullptr;
-            HIPCHK(hipMalloc(&ctx->cp_idx, 8 * need));
-            ctx->cp_idx_n = need;
-        }
-        HIPCHK(hipMemcpyAsync(&h2[0], d_in_off, 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(&h2[1], d_in_off + n_msgs, 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        // Σ encode bounds = 2·(input bytes) + n·(28 + 4·ws)
-        const uint64_t bound = 2 * (h2[1] - h2[0]) + (uint64_t)n_msgs * (28 + 4ull * (uint64_t)ctx->cfg.word_size + 4);
-        if (bound > ctx->cp_bytes) {
-            HIPCHK(cp_drop(ctx, ctx->cp_buf));
-            ctx->cp_buf = nullptr;
-            HIPCHK(hipMalloc(&ctx->cp_buf, bound));
-            ctx->cp_bytes = bound;
-        }
-    }
-    uint64_t *slot = ctx->cp_idx, *len = ctx->cp_idx + n_msgs + 1;
-    int st = tdt_encode_slots(ctx, d_in_off, n_msgs, slot, stream);
-    if (st) return st;
-    st = encode_common(ctx, mode, d_in, d_in_off, n_msgs, d_mapping, ctx->cp_buf, 0, nullptr, d_status, nullptr, nullptr,
-                       nullptr, stream, slot, len);
-    if (st) return st;
-    hipLaunchKernelGGL(cp_len_kernel, dim3((n_msgs + 255) / 256), dim3(256), 0, s, len, d_out_off, n_msgs);
-    HIPCHK(hipGetLastError());
-    st = scan_sizes(ctx, d_out_off, n_msgs, s);  // exclusive, total at [n]
-    if (st) return st;
-    hipLaunchKernelGGL(cp_gather_kernel, dim3((n_msgs + 3) / 4), dim3(256), 0, s, ctx->cp_buf, slot, len, d_out,
-                       d_out_off, out_cap, d_status, n_msgs);
-    HIPCHK(hipGetLastError());
-    return TDT_OK;
+    HIPCHK(hipMemcpyAsync(&h2[0], a.in_off, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&h2[1], a.in_off + a.n_msgs, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return encode_two_phase(ctx, mode, a, h2[1] - h2[0], stream);
 }
 
 int tdt_encode_batch(tdt_ctx *ctx, const uint8_t *d_in, const uint64_t *d_in_off, uint32_t n_msgs, uint8_t *d_out,
                      uint64_t out_cap, uint64_t *d_out_off, int32_t *d_status, void *stream) {
-    if (ctx && n_msgs && psy::anyws_generic(ctx->cfg.word_size))
-        return encode_two_phase_any(ctx, psy::MODE_ENCODE, d_in, d_in_off, n_msgs, nullptr, d_out, out_cap, d_out_off,
-                                    d_status, stream);
+    auto a = batch_args<psy::EncodeArgs>(d_in, d_in_off, n_msgs, d_out, d_status);
+    a.out_cap = out_cap;
+    a.out_off = d_out_off;
+    if (ctx && n_msgs && psy::anyws_generic(ctx->cfg.word_size)) return encode_two_phase_any(ctx, psy::MODE_ENCODE, a, stream);
     if (!ctx || n_msgs == 0 || !d_in_off || !d_out || !d_out_off || !two_phase_ok(ctx, stream))
-        return encode_common(ctx, psy::MODE_ENCODE, d_in, d_in_off, n_msgs, nullptr, d_out, out_cap, d_out_off,
-                             d_status, nullptr, nullptr, nullptr, stream);
+        return encode_common(ctx, psy::MODE_ENCODE, a, Where(stream));
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(hipSetDevice(ctx->device));
     uint64_t h3[3];
     {
         std::lock_guard<std::mutex> lk(ctx->mu);
-        const size_t need = 2ull * n_msgs + 2;
-        if (need > ctx->cp_idx_n) {
-            HIPCHK(cp_drop(ctx, ctx->cp_idx));
-            ctx->cp_idx = nullptr;
-            HIPCHK(hipMalloc(&ctx->cp_idx, 8 * need));
-            ctx->cp_idx_n = need;
-        }
+        if (int st = ensure_cp(ctx, 2ull * n_msgs + 2, 0, s)) return st;  // (the probe's flag word)
         uint64_t *flag = ctx->cp_idx + 2ull * n_msgs + 1;
         HIPCHK(hipMemsetAsync(flag, 0, 8, s));
         hipLaunchKernelGGL(cp_big_kernel, dim3((n_msgs + 255) / 256), dim3(256), 0, s, d_in, d_in_off, n_msgs,
@@ -2346,50 +2371,32 @@ int tdt_encode_batch(tdt_ctx *ctx, const uint8_t *d_in, const uint64_t *d_in_off
     // one pass with the look-back for batches of medium messages (all <= 64 KiB, 16 KiB or more
     // on average); small messages make the per-message ticket and look-back chain the limit
     // (C2: 12 ms for 1 Mi x 1 KiB), long ones stall it — both take the two phases
-    if (!(h3[0] & 1) && (h3[2] - h3[1]) >= 16384ull * n_msgs)  // (16 KiB on average: 512-lane teams)
-        return encode_common(ctx, psy::MODE_ENCODE, d_in, d_in_off, n_msgs, nullptr, d_out, out_cap, d_out_off,
-                             d_status, nullptr, nullptr, nullptr, stream, nullptr, nullptr, nullptr, nullptr,
-                             (h3[0] & 2) ? 0 : 2);
-    uint64_t *slot = ctx->cp_idx, *len = ctx->cp_idx + n_msgs + 1;
-    // Σ encode bounds <= 2·(input bytes) + n·(28 + 4·ws) (and >= n + 4 per message)
-    const uint64_t bound = 2 * (h3[2] - h3[1]) + (uint64_t)n_msgs * (28 + 4ull * (uint64_t)ctx->cfg.word_size + 4);
-    {
-        std::lock_guard<std::mutex> lk(ctx->mu);
-        if (bound > ctx->cp_bytes) {
-            HIPCHK(cp_drop(ctx, ctx->cp_buf));
-            ctx->cp_buf = nullptr;
-            HIPCHK(hipMalloc(&ctx->cp_buf, bound));
-            ctx->cp_bytes = bound;
-        }
+    if (!(h3[0] & 1) && (h3[2] - h3[1]) >= 16384ull * n_msgs) {  // (16 KiB on average: 512-lane teams)
+        Where w(stream);
+        w.small_teams = (h3[0] & 2) ? 0 : 2;
+        return encode_common(ctx, psy::MODE_ENCODE, a, w);
     }
-    int st = tdt_encode_slots(ctx, d_in_off, n_msgs, slot, stream);
-    if (st) return st;
-    st = tdt_encode_batch_into(ctx, d_in, d_in_off, n_msgs, ctx->cp_buf, slot, len, d_status, stream);
-    if (st) return st;
-    hipLaunchKernelGGL(cp_len_kernel, dim3((n_msgs + 255) / 256), dim3(256), 0, s, len, d_out_off, n_msgs);
-    HIPCHK(hipGetLastError());
-    st = scan_sizes(ctx, d_out_off, n_msgs, s);  // exclusive, total at [n]
-    if (st) return st;
-    hipLaunchKernelGGL(cp_gather_kernel, dim3((n_msgs + 3) / 4), dim3(256), 0, s, ctx->cp_buf, slot, len, d_out,
-                       d_out_off, out_cap, d_status, n_msgs);
-    HIPCHK(hipGetLastError());
-    return TDT_OK;
+    return encode_two_phase(ctx, psy::MODE_ENCODE, a, h3[2] - h3[1], stream);
 }
 
 int tdt_encode_with_mapping_batch(tdt_ctx *ctx, const uint8_t *d_in, const uint64_t *d_in_off, uint32_t n_msgs,
                                   const int32_t *d_mapping, uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_off,
                                   int32_t *d_status, void *stream) {
-    if (ctx && n_msgs && psy::anyws_generic(ctx->cfg.word_size))
-        return encode_two_phase_any(ctx, psy::MODE_MAPPED, d_in, d_in_off, n_msgs, d_mapping, d_out, out_cap, d_out_off,
-                                    d_status, stream);
-    return encode_common(ctx, psy::MODE_MAPPED, d_in, d_in_off, n_msgs, d_mapping, d_out, out_cap, d_out_off,
-                         d_status, nullptr, nullptr, nullptr, stream);
+    auto a = batch_args<psy::EncodeArgs>(d_in, d_in_off, n_msgs, d_out, d_status);
+    a.mapping_in = d_mapping;
+    a.out_cap = out_cap;
+    a.out_off = d_out_off;
+    if (ctx && n_msgs && psy::anyws_generic(ctx->cfg.word_size)) return encode_two_phase_any(ctx, psy::MODE_MAPPED, a, stream);
+    return encode_common(ctx, psy::MODE_MAPPED, a, Where(stream));
 }
 
 int tdt_analyze_batch(tdt_ctx *ctx, const uint8_t *d_in, const uint64_t *d_in_off, uint32_t n_msgs, uint32_t *d_hist,
                       double *d_entropy, int32_t *d_mapping, int32_t *d_status, void *stream) {
-    return encode_common(ctx, psy::MODE_ANALYZE, d_in, d_in_off, n_msgs, nullptr, nullptr, 0, nullptr, d_status,
-                         d_hist, d_entropy, d_mapping, stream);
+    auto a = batch_args<psy::EncodeArgs>(d_in, d_in_off, n_msgs, nullptr, d_status);
+    a.hist_out = d_hist;
+    a.ent_out = d_entropy;
+    a.map_out = d_mapping;
+    return encode_common(ctx, psy::MODE_ANALYZE, a, Where(stream));
 }
 
 // Compacted decode.  Decoded sizes are in the headers, so the output offsets are computed
@@ -2407,13 +2414,7 @@ int tdt_decode_batch(tdt_ctx *ctx, const uint8_t *d_in, const uint64_t *d_in_off
         uint64_t total = 0;
         {
             std::lock_guard<std::mutex> lk(ctx->mu);
-            const size_t need = 2ull * n_msgs + 2;
-            if (need > ctx->cp_idx_n) {
-                HIPCHK(cp_drop(ctx, ctx->cp_idx));
-                ctx->cp_idx = nullptr;
-                HIPCHK(hipMalloc(&ctx->cp_idx, 8 * need));
-                ctx->cp_idx_n = need;
-            }
+            if ((st = ensure_cp(ctx, 2ull * n_msgs + 2, 0, s))) return st;  // (the decoded lengths)
             HIPCHK(hipMemcpyAsync(&total, d_out_off + n_msgs, 8, hipMemcpyDeviceToHost, s));
             HIPCHK(hipStreamSynchronize(s));
         }
@@ -2421,56 +2422,70 @@ int tdt_decode_batch(tdt_ctx *ctx, const uint8_t *d_in, const uint64_t *d_in_off
             return tdt_decode_batch_into(ctx, d_in, d_in_off, nullptr, n_msgs, d_out, d_out_off, ctx->cp_idx, d_status,
                                          stream);
     }
-    return decode_common(ctx, false, d_in, d_in_off, n_msgs, d_out, out_cap, d_out_off, nullptr, d_status, stream);
+    auto a = batch_args<psy::DecodeArgs>(d_in, d_in_off, n_msgs, d_out, d_status);
+    a.out_cap = out_cap;
+    a.out_off = d_out_off;
+    return decode_common(ctx, false, a, Where(stream));
 }
 
 int tdt_decoded_sizes_batch(tdt_ctx *ctx, const uint8_t *d_in, const uint64_t *d_in_off, uint32_t n_msgs,
                             uint64_t *d_sizes, int32_t *d_status, void *stream) {
-    return decode_common(ctx, true, d_in, d_in_off, n_msgs, nullptr, 0, nullptr, d_sizes, d_status, stream);
+    auto a = batch_args<psy::DecodeArgs>(d_in, d_in_off, n_msgs, nullptr, d_status);
+    a.sizes_out = d_sizes;
+    return decode_common(ctx, true, a, Where(stream));
 }
 
 int tdt_encode_batch_into(tdt_ctx *ctx, const uint8_t *d_in, const uint64_t *d_in_off, uint32_t n_msgs,
                           uint8_t *d_out, const uint64_t *d_slot_off, uint64_t *d_out_len, int32_t *d_status,
                           void *stream) {
     if (n_msgs && !d_slot_off) return set_err(TDT_E_ARG, "null slot offsets");
-    return encode_common(ctx, psy::MODE_ENCODE, d_in, d_in_off, n_msgs, nullptr, d_out, 0, nullptr, d_status, nullptr,
-                         nullptr, nullptr, stream, d_slot_off, d_out_len);
+    auto a = batch_args<psy::EncodeArgs>(d_in, d_in_off, n_msgs, d_out, d_status);
+    a.slot_off = d_slot_off;
+    a.out_len = d_out_len;
+    return encode_common(ctx, psy::MODE_ENCODE, a, Where(stream));
 }
 
 int tdt_decode_batch_into(tdt_ctx *ctx, const uint8_t *d_in, const uint64_t *d_in_off, const uint64_t *d_in_len,
                           uint32_t n_msgs, uint8_t *d_out, const uint64_t *d_slot_off, uint64_t *d_out_len,
                           int32_t *d_status, void *stream) {
     if (n_msgs && !d_slot_off) return set_err(TDT_E_ARG, "null slot offsets");
-    return decode_common(ctx, false, d_in, d_in_off, n_msgs, d_out, 0, nullptr, nullptr, d_status, stream, d_slot_off,
-                         d_out_len, d_in_len);
+    auto a = batch_args<psy::DecodeArgs>(d_in, d_in_off, n_msgs, d_out, d_status);
+    a.in_len = d_in_len;
+    a.slot_off = d_slot_off;
+    a.out_len = d_out_len;
+    return decode_common(ctx, false, a, Where(stream));
+}
+
+// A scattered encode: the batch is `v` alone (no base pointers, no offset tables)
+static int encode_scattered(tdt_ctx *ctx, const Scatter &v, uint32_t n_msgs, uint64_t *d_out_len, int32_t *d_status,
+                            void *stream) {
+    psy::EncodeArgs a{};
+    a.n_msgs = n_msgs;
+    a.status = d_status;
+    a.out_len = d_out_len;
+    Where w(stream);
+    w.v = &v;
+    return encode_common(ctx, psy::MODE_ENCODE, a, w);
 }
 
 int tdt_encode_batch_v(tdt_ctx *ctx, const uint8_t *const *d_msgs, const uint64_t *d_sizes, uint32_t n_msgs,
                        uint8_t *const *d_blobs, const uint64_t *d_blob_cap, uint64_t *d_out_len, int32_t *d_status,
                        void *stream) {
-    // (device addresses are 64 bits wide: a pointer table read as u64 is the offset table of a null base)
-    static_assert(sizeof(uint8_t *) == sizeof(uint64_t), "pointer tables are read as u64 offsets");
-    const Scatter v{reinterpret_cast<const uint64_t *>(d_msgs), d_sizes, reinterpret_cast<const uint64_t *>(d_blobs),
-                    d_blob_cap};
-    return encode_common(ctx, psy::MODE_ENCODE, nullptr, nullptr, n_msgs, nullptr, nullptr, 0, nullptr, d_status, nullptr,
-                         nullptr, nullptr, stream, nullptr, d_out_len, nullptr, nullptr, -1, &v);
+    return encode_scattered(ctx, scatter_of(d_msgs, d_sizes, d_blobs, d_blob_cap), n_msgs, d_out_len, d_status, stream);
 }
 
 int tdt_encode_batch_vw(tdt_ctx *ctx, const uint8_t *const *d_msgs, const uint64_t *d_sizes,
                         const int32_t *d_word_size, uint64_t width_mask, uint32_t n_msgs, uint8_t *const *d_blobs,
                         const uint64_t *d_blob_cap, uint64_t *d_out_len, int32_t *d_status, void *stream) {
     static_assert(TDT_MIXED_MAX_WIDTHS == psy::kMixedMaxWidths, "the header states the routes' limit");
-    const Scatter v{reinterpret_cast<const uint64_t *>(d_msgs), d_sizes, reinterpret_cast<const uint64_t *>(d_blobs),
-                    d_blob_cap};
-    return encode_mixed(ctx, v, d_word_size, width_mask, n_msgs, d_out_len, d_status, (hipStream_t)stream);
+    return encode_mixed(ctx, scatter_of(d_msgs, d_sizes, d_blobs, d_blob_cap), d_word_size, width_mask, n_msgs, d_out_len,
+                        d_status, (hipStream_t)stream);
 }
 
 // lengths → d_out_off, scanned in place, then the byte-balanced pack kernel (tdt_pack.h)
 static int pack_common(tdt_ctx *ctx, const uint64_t *d_blobs, const uint64_t *d_blob_len, uint32_t n_msgs, uint8_t *d_out,
                        uint64_t out_cap, uint64_t *d_out_off, int32_t *d_status, bool keep_errors, hipStream_t s) {
-    hipLaunchKernelGGL(cp_len_kernel, dim3((n_msgs + 255) / 256), dim3(256), 0, s, d_blob_len, d_out_off, n_msgs);
-    HIPCHK(hipGetLastError());
-    if (int st = scan_sizes(ctx, d_out_off, n_msgs, s)) return st;  // exclusive, total at [n]
+    if (int st = scan_lengths(ctx, d_blob_len, d_out_off, n_msgs, s)) return st;
     HIPCHK((hipError_t)psy::launch_pack(d_blobs, d_out_off, n_msgs, d_out, out_cap, d_status, keep_errors, ctx->pack_cut,
                                         ctx->pack_grid, s));
     return TDT_OK;
@@ -2504,30 +2519,14 @@ int tdt_encode_batch_vp(tdt_ctx *ctx, const uint8_t *const *d_msgs, const uint64
     if (total_bytes > (1ull << 62)) return set_err(TDT_E_ARG, "total_bytes too large");
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(hipSetDevice(ctx->device));
-    // the scratch: every blob in a slot of its encode bound, Σ bounds <= 2·total_bytes + n·(28 + 4·wmax)
-    const uint64_t need = 2 * total_bytes + (uint64_t)n_msgs * (28 + 4 * wmax);
-    const size_t need_idx = 4ull * n_msgs + 2;
+    // the scratch: every blob in a slot of its encode bound, Σ bounds <= 2·total_bytes + n·(28 + 4·wmax);
+    // the tables: slots (n + 1) | blob addresses (n) | capacities (n) | lengths (n)
     uint8_t *buf;
     uint64_t buf_bytes, *idx;
     {
         std::lock_guard<std::mutex> lk(ctx->mu);
-        if (capturing(s)) ctx->cp_in_graph = true;
-        if (need_idx > ctx->cp_idx_n) {
-            if (int st = no_growth_in_capture(s)) return st;
-            HIPCHK(cp_drop(ctx, ctx->cp_idx));
-            ctx->cp_idx = nullptr;
-            ctx->cp_idx_n = 0;
-            HIPCHK(hipMalloc(&ctx->cp_idx, 8 * need_idx));
-            ctx->cp_idx_n = need_idx;
-        }
-        if (need > ctx->cp_bytes) {
-            if (int st = no_growth_in_capture(s)) return st;
-            HIPCHK(cp_drop(ctx, ctx->cp_buf));
-            ctx->cp_buf = nullptr;
-            ctx->cp_bytes = 0;
-            HIPCHK(hipMalloc(&ctx->cp_buf, need));
-            ctx->cp_bytes = need;
-        }
+        if (int st = ensure_cp(ctx, 4ull * n_msgs + 2, 2 * total_bytes + (uint64_t)n_msgs * (28 + 4 * wmax), s, true))
+            return st;
         buf = ctx->cp_buf, buf_bytes = ctx->cp_bytes, idx = ctx->cp_idx;
     }
     uint64_t *slot = idx, *ptr = idx + n_msgs + 1, *cap = ptr + n_msgs, *len = cap + n_msgs;
@@ -2538,9 +2537,7 @@ int tdt_encode_batch_vp(tdt_ctx *ctx, const uint8_t *const *d_msgs, const uint64
     HIPCHK((hipError_t)psy::launch_pack_slots(slot, buf, buf_bytes, ptr, cap, n_msgs, s));
     const Scatter v{reinterpret_cast<const uint64_t *>(d_msgs), d_sizes, ptr, cap};
     const int st = d_word_size ? encode_mixed(ctx, v, d_word_size, width_mask, n_msgs, len, d_status, s)
-                               : encode_common(ctx, psy::MODE_ENCODE, nullptr, nullptr, n_msgs, nullptr, nullptr, 0, nullptr,
-                                               d_status, nullptr, nullptr, nullptr, stream, nullptr, len, nullptr, nullptr,
-                                               -1, &v);
+                               : encode_scattered(ctx, v, n_msgs, len, d_status, stream);
     if (st) return st;
     return pack_common(ctx, ptr, len, n_msgs, d_out, out_cap, d_out_off, d_status, true, s);
 }
@@ -2548,17 +2545,25 @@ int tdt_encode_batch_vp(tdt_ctx *ctx, const uint8_t *const *d_msgs, const uint64
 int tdt_decode_batch_v(tdt_ctx *ctx, const uint8_t *const *d_blobs, const uint64_t *d_blob_len, uint32_t n_msgs,
                        uint8_t *const *d_outs, const uint64_t *d_out_cap, uint64_t *d_out_len, int32_t *d_status,
                        void *stream) {
-    const Scatter v{reinterpret_cast<const uint64_t *>(d_blobs), d_blob_len, reinterpret_cast<const uint64_t *>(d_outs),
-                    d_out_cap};
-    return decode_common(ctx, false, nullptr, v.ptr, n_msgs, nullptr, 0, nullptr, nullptr, d_status, stream, nullptr,
-                         d_out_len, d_blob_len, nullptr, nullptr, &v);
+    const Scatter v = scatter_of(d_blobs, d_blob_len, d_outs, d_out_cap);
+    psy::DecodeArgs a{};  // (the blobs through in_off / in_len as they are)
+    a.in_off = v.ptr;
+    a.in_len = d_blob_len;
+    a.n_msgs = n_msgs;
+    a.status = d_status;
+    a.out_len = d_out_len;
+    Where w(stream);
+    w.v = &v;
+    return decode_common(ctx, false, a, w);
 }
 
 int tdt_decoded_sizes_v(tdt_ctx *ctx, const uint8_t *const *d_blobs, const uint64_t *d_blob_len, uint32_t n_msgs,
                         uint64_t *d_sizes, int32_t *d_status, void *stream) {
     if (n_msgs && !d_blob_len) return set_err(TDT_E_ARG, "null blob lengths");
-    return decode_common(ctx, true, nullptr, reinterpret_cast<const uint64_t *>(d_blobs), n_msgs, nullptr, 0, nullptr,
-                         d_sizes, d_status, stream, nullptr, nullptr, d_blob_len);
+    auto a = batch_args<psy::DecodeArgs>(nullptr, reinterpret_cast<const uint64_t *>(d_blobs), n_msgs, nullptr, d_status);
+    a.in_len = d_blob_len;
+    a.sizes_out = d_sizes;
+    return decode_common(ctx, true, a, Where(stream));
 }
 
 int tdt_encode_slots(tdt_ctx *ctx, const uint64_t *d_in_off, uint32_t n_msgs, uint64_t *d_slot_off, void *stream) {
@@ -2580,9 +2585,10 @@ int tdt_decode_slots(tdt_ctx *ctx, const uint8_t *d_in, const uint64_t *d_in_off
     if (!ctx) return set_err(TDT_E_ARG, "null context");
     if (!d_slot_off) return set_err(TDT_E_ARG, "null offsets");
     if (n_msgs) {
-        int st = decode_common(ctx, true, d_in, d_in_off, n_msgs, nullptr, 0, nullptr, d_slot_off, d_status, stream,
-                               nullptr, nullptr, d_in_len);
-        if (st) return st;
+        auto a = batch_args<psy::DecodeArgs>(d_in, d_in_off, n_msgs, nullptr, d_status);
+        a.in_len = d_in_len;
+        a.sizes_out = d_slot_off;
+        if (int st = decode_common(ctx, true, a, Where(stream))) return st;
     }
     HIPCHK(hipSetDevice(ctx->device));
     return scan_sizes(ctx, d_slot_off, n_msgs, (hipStream_t)stream);
@@ -2613,15 +2619,7 @@ int tdt_encode_host_v(tdt_ctx *ctx, const uint8_t *const *msgs, const uint64_t *
     }
     std::vector<uint64_t> voff(n_msgs + 1, 0);
     for (uint32_t i = 0; i < n_msgs; ++i) voff[i + 1] = voff[i] + sizes[i];
-    HIPCHK(hipSetDevice(ctx->device));
-    std::lock_guard<std::mutex> lk(ctx->hmu);
-    if (!ctx->pool) ctx->pool.reset(new CopyPool(ctx->copy_threads));
-    const int st = host_encode(ctx, nullptr, voff.data(), n_msgs, h_out, out_cap, h_out_off, h_status, msgs, sizes);
-    if (st != TDT_OK) {
-        drain_host(ctx);
-        (void)hipGetLastError();
-    }
-    return st;
+    return host_path(ctx, true, nullptr, voff.data(), n_msgs, h_out, out_cap, h_out_off, h_status, msgs, sizes);
 }
 
 int tdt_host_alloc(uint64_t bytes, void **ptr) {
@@ -2687,10 +2685,13 @@ int tdt_analyze_host(tdt_ctx *ctx, const uint8_t *h_in, const uint64_t *h_in_off
     hipStream_t s = ctx->astream;
     HIPCHK(hipMemcpyAsync(d, h_in + h_in_off[0], in_bytes, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(d + o_off, tmp.data(), 8ull * (n_msgs + 1), hipMemcpyHostToDevice, s));
-    st = encode_common(ctx, psy::MODE_ANALYZE, d, reinterpret_cast<uint64_t *>(d + o_off), n_msgs, nullptr, nullptr,
-                       0, nullptr, reinterpret_cast<int32_t *>(d + o_st), nullptr,
-                       reinterpret_cast<double *>(d + o_ent), reinterpret_cast<int32_t *>(d + o_map), s, nullptr,
-                       nullptr, nullptr, nullptr, in_bytes <= kSmallMax * n_msgs ? 1 : 0);
+    auto a = batch_args<psy::EncodeArgs>(d, reinterpret_cast<uint64_t *>(d + o_off), n_msgs, nullptr,
+                                         reinterpret_cast<int32_t *>(d + o_st));
+    a.ent_out = reinterpret_cast<double *>(d + o_ent);
+    a.map_out = reinterpret_cast<int32_t *>(d + o_map);
+    Where w(s);
+    w.small_teams = in_bytes <= kSmallMax * n_msgs ? 1 : 0;
+    st = encode_common(ctx, psy::MODE_ANALYZE, a, w);
     if (st) return st;
     if (h_entropy) HIPCHK(hipMemcpyAsync(h_entropy, d + o_ent, 8ull * n_msgs * ws, hipMemcpyDeviceToHost, s));
     if (h_mapping) HIPCHK(hipMemcpyAsync(h_mapping, d + o_map, 4ull * n_msgs * ws, hipMemcpyDeviceToHost, s));
@@ -2735,13 +2736,9 @@ static int scan_sizes(tdt_ctx *ctx, uint64_t *d_slot_off, uint32_t n_msgs, hipSt
     const uint32_t nb = (n_msgs + psy::kSlotChunk - 1) / psy::kSlotChunk;
     if (nb > 1) {
         std::lock_guard<std::mutex> lk(ctx->mu);
-        if (nb > ctx->slot_sums_n) {
-            if (int st = no_growth_in_capture(stream)) return st;
-            if (ctx->slot_sums) ctx->retired.push_back(ctx->slot_sums);  // (a captured graph may use it)
-            ctx->slot_sums = nullptr;
-            HIPCHK(hipMalloc(&ctx->slot_sums, 8ull * nb));
-            ctx->slot_sums_n = nb;
-        }
+        if (int st = grow_retiring(ctx->slot_sums, ctx->slot_sums_n, nb, psy::cap_exact(nb, ctx->slot_sums_n), ctx->retired,
+                                   stream, 8))
+            return st;
         hipLaunchKernelGGL(psy::tdt_slot_sums_kernel, dim3(nb - 1), dim3(psy::kSlotThreads), 0, (hipStream_t)stream,
                            d_slot_off, ctx->slot_sums, n_msgs);
         HIPCHK(hipGetLastError());
