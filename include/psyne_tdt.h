@@ -30,6 +30,8 @@
  *                                     :206-222, :434-525 (full-sample histograms, entropies,
  *                                     mapping per message)
  *   tdt_encode_bound                  worst-case blob size (sizing out buffers)
+ *   tdt_encoded_sizes_batch /         transformation_ratio (encoded size / original size) of each
+ *   tdt_encoded_sizes_v               message BEFORE it is encoded: the exact blob length, no blob written
  *   tdt_last_error                    the reference's exception text (:128, :275)
  *
  * Wire format: identical bytes to the reference: UNCP marker
@@ -253,12 +255,42 @@ int tdt_pack_v(tdt_ctx *ctx, const uint8_t *const *d_blobs, const uint64_t *d_bl
  *     once one eager call with the same n_msgs, the same mask and a total_bytes at least as large
  *     has run (TDT_E_CAPTURE otherwise) — tdt_encode_batch, the compacted call for contiguous
  *     input, is not at generic widths.
+ *   Sizes first: with TDT_OPT_PACK_SIZES_FIRST set, the call instead sizes every blob (the pass of
+ *     tdt_encoded_sizes_v) into d_out_off, scans it in place, and encodes every blob once, straight
+ *     into d_out[d_out_off[i] .. d_out_off[i+1]) — a blob that would end past out_cap gets a slot of
+ *     capacity 0.  The scratch is not used and total_bytes is ignored; every line of the contract
+ *     above holds unchanged (the same bytes, the same d_out_off with the full need at [n_msgs], the
+ *     same statuses, nothing written outside d_out[0 .. min(total, out_cap)), capturable once warm).
  * Replaces a loop of TDTCompressionProtocol::encode (:227-266) followed by a framed send of each
  * vector. */
 int tdt_encode_batch_vp(tdt_ctx *ctx, const uint8_t *const *d_msgs, const uint64_t *d_sizes,
                         const int32_t *d_word_size, uint64_t width_mask, uint32_t n_msgs, uint64_t total_bytes,
                         uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_off, int32_t *d_status,
                         void *hip_stream);
+/* EXACT ENCODED SIZES — how long blob i will be, before a byte of it is written.  The size pass runs
+ * the encode pipeline (the UNCP routing, the histograms, the mapping decision with its exact chains
+ * on near ties, the run and 255-cap counts) and stops at the pair counts: it reads what the encode
+ * reads and writes 8 bytes per message.  A caller sizes its output exactly (scan d_enc_sizes into
+ * offsets) instead of by tdt_encode_bound, or decides from d_enc_sizes[i] / size[i] — the message's
+ * transformation ratio — whether compressing it pays.
+ *   tdt_encoded_sizes_batch: message i = d_in[d_in_off[i] .. d_in_off[i+1]), at the context's width.
+ *   tdt_encoded_sizes_v: message i = d_msgs[i][0 .. d_sizes[i]).  d_word_size == NULL: every message
+ *     at the context's width, width_mask ignored.  Otherwise d_word_size[i] is message i's width and
+ *     width_mask, the rejected widths and the call-level mask errors are those of tdt_encode_batch_vw.
+ *   Contract: d_enc_sizes[i] and d_status[i] are exactly the d_out_len[i] and d_status[i] that
+ *     tdt_encode_batch_v / _vw give for the same bytes, context and metrics with a capacity of the
+ *     encode bound: TDT_OK for every accepted message, a rejected width's status with size 0.
+ *   Context rules: those of the scattered calls — asynchronous, nothing read back, pointers of any
+ *     alignment and order, the pointer of a size-0 message never dereferenced, one stream at a time
+ *     per context, n_msgs == 0 touches nothing; capturable once one eager call of the same n_msgs
+ *     (and mask) has grown the workspaces (TDT_E_CAPTURE otherwise).  The calls share the encode's
+ *     plan workspace, so an eager size call also warms the context for a captured encode of that
+ *     batch size, and the other way round. */
+int tdt_encoded_sizes_batch(tdt_ctx *ctx, const uint8_t *d_in, const uint64_t *d_in_off, uint32_t n_msgs,
+                            uint64_t *d_enc_sizes, int32_t *d_status, void *hip_stream);
+int tdt_encoded_sizes_v(tdt_ctx *ctx, const uint8_t *const *d_msgs, const uint64_t *d_sizes,
+                        const int32_t *d_word_size, uint64_t width_mask, uint32_t n_msgs,
+                        uint64_t *d_enc_sizes, int32_t *d_status, void *hip_stream);
 /* Decoded size of each scattered blob (0 with an error status), as tdt_decoded_sizes_batch. */
 int tdt_decoded_sizes_v(tdt_ctx *ctx, const uint8_t *const *d_blobs, const uint64_t *d_blob_len, uint32_t n_msgs,
                         uint64_t *d_sizes, int32_t *d_status, void *hip_stream);
@@ -331,6 +363,8 @@ int tdt_ctx_error_flags(tdt_ctx *ctx, void *hip_stream, uint32_t *flags);
 #define TDT_OPT_SMALL_ON_CALLER_STREAM 4  /* 1: small-message lists stay on the caller's stream */
 #define TDT_OPT_NO_TWO_PHASE 5            /* 1: compacted calls always take the one-pass kernels */
 #define TDT_OPT_COPY_THREADS 6            /* host threads staging pageable buffers (default <= 16) */
+#define TDT_OPT_PACK_SIZES_FIRST 7        /* 1: tdt_encode_batch_vp sizes the blobs first and encodes them in
+                                             place, without the scratch (default 0: the two phases) */
 int tdt_ctx_set_option(tdt_ctx *ctx, int option, uint64_t value);
 
 /* Host-memory analyze (analyze_data :206-222): h_entropy n*ws doubles, h_mapping n*ws int32

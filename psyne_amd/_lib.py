@@ -16,6 +16,7 @@ TDT_E_CAPACITY, TDT_E_UNSUPPORTED, TDT_E_BAD_HEADER, TDT_E_CONFIG = 5, 6, 7, 8
 TDT_E_HIP, TDT_E_ARG, TDT_E_CAPTURE = 10, 11, 12
 TDT_OPT_LARGE_MIN, TDT_OPT_TILE_CAP, TDT_OPT_NO_SIDE_STREAM = 1, 2, 3
 TDT_OPT_SMALL_ON_CALLER_STREAM, TDT_OPT_NO_TWO_PHASE, TDT_OPT_COPY_THREADS = 4, 5, 6
+TDT_OPT_PACK_SIZES_FIRST = 7
 
 
 class TdtConfigC(C.Structure):
@@ -50,6 +51,8 @@ SIGNATURES = {
     "tdt_pack_v": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _vp, C.c_uint64, _vp, _vp, _vp]),
     "tdt_encode_batch_vp": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint64, C.c_uint32, C.c_uint64, _vp, C.c_uint64, _vp, _vp,
                                       _vp]),
+    "tdt_encoded_sizes_batch": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp]),
+    "tdt_encoded_sizes_v": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint64, C.c_uint32, _vp, _vp, _vp]),
     "tdt_decode_batch_v": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp]),
     "tdt_decoded_sizes_v": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp]),
     "tdt_encode_slots": (C.c_int, [_vp, _vp, C.c_uint32, _vp, _vp]),

@@ -19,13 +19,14 @@ ARCH = os.environ.get("PSYNE_ARCH", "gfx950")
 
 SOURCES = [CSRC / "tdt_api.hip"]  # (diagnostic single-TU builds compile this file alone)
 ENC_WS_SRC = CSRC / "tdt_enc_ws.hip"  # the encode kernels of one word size
+ENC_SIZES_WS_SRC = CSRC / "tdt_enc_sizes_ws.hip"  # the size-pass kernels (tdt_encoded_sizes_*) of one word size
 WORD_SIZES = (1, 2, 4, 8, 16)
 ANYWS_SRC = CSRC / "tdt_anyws.hip"  # encode and decode of every other word size up to 64
 SOURCES.append(ANYWS_SRC)
 PACK_SRC = CSRC / "tdt_pack.hip"  # the pack kernel of tdt_pack_v / tdt_encode_batch_vp
 SOURCES.append(PACK_SRC)
 # every source and header under csrc/ (tdt_api.hip includes the headers, directly or not)
-DEPS = SOURCES + [ENC_WS_SRC] + sorted(CSRC.glob("*.h")) + [ROOT / "include" / "psyne_tdt.h"]
+DEPS = SOURCES + [ENC_WS_SRC, ENC_SIZES_WS_SRC] + sorted(CSRC.glob("*.h")) + [ROOT / "include" / "psyne_tdt.h"]
 OBJ_DIR = PKG / "build"
 
 
@@ -47,6 +48,8 @@ def build(force: bool = False, verbose: bool = False) -> pathlib.Path:
         for ws in WORD_SIZES:
             o = OBJ_DIR / f"tdt_enc_ws{ws}.o"
             jobs.append((base + [f"-DPSY_INST_WS={ws}", "-c", str(ENC_WS_SRC), "-o", str(o)], o))
+            o = OBJ_DIR / f"tdt_enc_sizes_ws{ws}.o"
+            jobs.append((base + [f"-DPSY_INST_WS={ws}", "-c", str(ENC_SIZES_WS_SRC), "-o", str(o)], o))
         procs = []
         for cmd, _ in jobs:
             if verbose:

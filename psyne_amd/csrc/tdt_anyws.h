@@ -37,7 +37,9 @@ inline bool anyws_generic(int ws) { return ws >= 1 && ws <= kAnyWsMax && !anyws_
 // Encode (mode MODE_ENCODE / MODE_MAPPED: slotted output, a.slot_off set; MODE_ANALYZE:
 // histograms, entropies and mapping, no blob) of a.n_msgs messages at word size ws.
 // pair (MODE_ENCODE only): a.in_off and a.slot_off are the (begin, end) pair tables of a scattered
-// batch (table_at, tdt_plan.h).  Returns a hipError_t as int (0: launched).
+// batch (table_at, tdt_plan.h); or, pair with MODE_SIZES, the size pass: a.in_off alone is a pair
+// table, the blob lengths go to a.out_len and nothing else is written.  Returns a hipError_t as
+// int (0: launched).
 int launch_encode_any(const EncodeArgs &a, int ws, int mode, hipStream_t s, bool pair = false);
 
 // Decode the blobs listed in a.dlist[0 .. *a.dcount) (slotted: a.slot_off; compacted: the

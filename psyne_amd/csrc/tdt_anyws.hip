@@ -52,6 +52,9 @@ __device__ __forceinline__ uint32_t byte_of(const uint32_t (&w)[4], int i) { ret
 
 // ---------------------------------------------------------------------------------------
 // Encode.  HP: histogram positions held in LDS (>= ws; 1 for MODE_MAPPED, which has none).
+// MODE_SIZES: the size pass — the same analysis, mapping and split + RLE loop of both streams with
+// every store to the blob compiled out (stream 0's pair count places stream 1, so there is no
+// separate count to stop at); the length goes to out_len, and there is no slot.
 template <int MODE, int HP, bool PAIR = false>
 __global__ __launch_bounds__(kAnyTeam) void tdt_encode_any_kernel(EncodeArgs a, uint32_t ws) {
     __shared__ uint32_t s_hist[HP * 256];
@@ -85,7 +88,15 @@ __global__ __launch_bounds__(kAnyTeam) void tdt_encode_any_kernel(EncodeArgs a, 
                    n < (1ull << 32);
     }
     uint64_t slot_b = 0, cap = 0;
-    if constexpr (MODE != MODE_ANALYZE) {
+    if constexpr (MODE == MODE_SIZES) {
+        if (!compress) {
+            if (tid == 0) {
+                if (a.status) a.status[msg] = ST_OK;
+                if (a.out_len) a.out_len[msg] = n + 4;
+            }
+            return;
+        }
+    } else if constexpr (MODE != MODE_ANALYZE) {
         slot_b = a.slot_off[table_at<PAIR>(msg, 0)];
         cap = a.slot_off[table_at<PAIR>(msg, 1)] - slot_b;
         if (!compress) {
@@ -207,6 +218,7 @@ __global__ __launch_bounds__(kAnyTeam) void tdt_encode_any_kernel(EncodeArgs a, 
         uint8_t *dst = a.out + slot_b;
         // every store is bounded by the slot: a blob that does not fit is reported, not written past it
         auto put8 = [&](uint64_t o, uint32_t v) __attribute__((always_inline)) {
+            if constexpr (MODE == MODE_SIZES) return;  // (the size pass writes no blob byte)
             if (o < cap) dst[o] = (uint8_t)v;
         };
         auto put32 = [&](uint64_t o, uint32_t v) __attribute__((always_inline)) {
@@ -343,7 +355,7 @@ __global__ __launch_bounds__(kAnyTeam) void tdt_encode_any_kernel(EncodeArgs a, 
             if (tid == 0) put32(o, 2u * cpairs);
             o = dpos + 2ull * cpairs;
         }
-        const bool fits = o <= cap;
+        const bool fits = MODE == MODE_SIZES || o <= cap;
         if (tid == 0) {
             if (a.status) a.status[msg] = fits ? ST_OK : ST_CAPACITY;
             if (a.out_len) a.out_len[msg] = fits ? o : 0;
@@ -476,25 +488,20 @@ __global__ __launch_bounds__(kAnyTeam) void tdt_decode_any_kernel(DecodeArgs a) 
 
 int launch_encode_any(const EncodeArgs &a, int ws, int mode, hipStream_t s, bool pair) {
     if (a.n_msgs == 0) return 0;
-    if (pair && mode != MODE_ENCODE) return (int)hipErrorInvalidValue;
+    if (pair ? mode != MODE_ENCODE && mode != MODE_SIZES : mode == MODE_SIZES) return (int)hipErrorInvalidValue;
     const dim3 g(a.n_msgs), t(kAnyTeam);
     const uint32_t w = (uint32_t)ws;
-#define PSY_ANY_HP(MODE_)                                                                              \
-    do {                                                                                               \
-        if (ws <= 8) hipLaunchKernelGGL((tdt_encode_any_kernel<MODE_, 8>), g, t, 0, s, a, w);          \
-        else if (ws <= 16) hipLaunchKernelGGL((tdt_encode_any_kernel<MODE_, 16>), g, t, 0, s, a, w);   \
-        else if (ws <= 32) hipLaunchKernelGGL((tdt_encode_any_kernel<MODE_, 32>), g, t, 0, s, a, w);   \
-        else hipLaunchKernelGGL((tdt_encode_any_kernel<MODE_, 64>), g, t, 0, s, a, w);                 \
+#define PSY_ANY_HP(MODE_, PAIR_)                                                                              \
+    do {                                                                                                      \
+        if (ws <= 8) hipLaunchKernelGGL((tdt_encode_any_kernel<MODE_, 8, PAIR_>), g, t, 0, s, a, w);          \
+        else if (ws <= 16) hipLaunchKernelGGL((tdt_encode_any_kernel<MODE_, 16, PAIR_>), g, t, 0, s, a, w);   \
+        else if (ws <= 32) hipLaunchKernelGGL((tdt_encode_any_kernel<MODE_, 32, PAIR_>), g, t, 0, s, a, w);   \
+        else hipLaunchKernelGGL((tdt_encode_any_kernel<MODE_, 64, PAIR_>), g, t, 0, s, a, w);                 \
     } while (0)
-    if (pair) {
-#define PSY_ANY_PAIR(HP_) hipLaunchKernelGGL((tdt_encode_any_kernel<MODE_ENCODE, HP_, true>), g, t, 0, s, a, w)
-        if (ws <= 8) PSY_ANY_PAIR(8);
-        else if (ws <= 16) PSY_ANY_PAIR(16);
-        else if (ws <= 32) PSY_ANY_PAIR(32);
-        else PSY_ANY_PAIR(64);
-#undef PSY_ANY_PAIR
-    } else if (mode == MODE_ENCODE) PSY_ANY_HP(MODE_ENCODE);
-    else if (mode == MODE_ANALYZE) PSY_ANY_HP(MODE_ANALYZE);
+    if (pair && mode == MODE_SIZES) PSY_ANY_HP(MODE_SIZES, true);
+    else if (pair) PSY_ANY_HP(MODE_ENCODE, true);
+    else if (mode == MODE_ENCODE) PSY_ANY_HP(MODE_ENCODE, false);
+    else if (mode == MODE_ANALYZE) PSY_ANY_HP(MODE_ANALYZE, false);
     else hipLaunchKernelGGL((tdt_encode_any_kernel<MODE_MAPPED, 1>), g, t, 0, s, a, w);
 #undef PSY_ANY_HP
     return (int)hipGetLastError();

@@ -40,7 +40,12 @@
     PSY_ENC_INSTANCES(PSY_ENC_EXT, WS)                                                                              \
     extern template __global__ void psy::tdt_encode_lscan_kernel<WS>(psy::EncodeArgs, const uint32_t *, uint32_t);  \
     PSY_ENC_PAIR_INSTANCES(PSY_ENC_PAIR_EXT, WS)                                                                    \
-    extern template __global__ void psy::tdt_encode_lscan_kernel<WS, true>(psy::EncodeArgs, const uint32_t *, uint32_t);
+    extern template __global__ void psy::tdt_encode_lscan_kernel<WS, true>(psy::EncodeArgs, const uint32_t *, uint32_t); \
+    PSY_ENC_SIZES_INSTANCES(PSY_ENC_SIZES_EXT, WS)                                                                   \
+    extern template __global__ void psy::tdt_encode_lscan_sizes_kernel<WS>(psy::EncodeArgs, const uint32_t *, uint32_t);
+// (the size pass, MODE_SIZES: tdt_enc_sizes_ws.hip)
+#define PSY_ENC_SIZES_EXT(WS, T, G, TL, PS, PA) \
+    extern template __global__ void psy::tdt_encode_kernel<WS, T, G, psy::MODE_SIZES, 0, TL, PS, PA, true>(psy::EncodeArgs);
 PSY_ENC_EXT_WS(1)
 PSY_ENC_EXT_WS(2)
 PSY_ENC_EXT_WS(4)
@@ -265,9 +270,13 @@ struct tdt_ctx {
     uint64_t *cp_idx = nullptr;  // slots (n + 1) | lengths (n) | flag
     size_t cp_idx_n = 0;
     // packed scattered encode (tdt_encode_batch_vp) keeps its slots in cp_buf and its tables in
-    // cp_idx: slots (n + 1) | blob addresses (n) | capacities (n) | lengths (n).  That call may be
+    // cp_idx: slots (n + 1) | blob addresses (n) | capacities (n) | lengths (n) — or, sizes first, no
+    // slots at all and blob addresses (n) | capacities (n).  That call may be
     // captured, so from its first capture on a buffer replaced by a larger one is retired, not freed
     bool cp_in_graph = false;
+    // TDT_OPT_PACK_SIZES_FIRST: tdt_encode_batch_vp sizes the blobs first (the size pass), scans, and
+    // encodes straight into the caller's buffer — cp_buf is not used, cp_idx holds addresses (n) | capacities (n)
+    bool pack_sizes_first = false;
     // the pack kernel's knobs (PSYNE_TDT_PACK_CUT, PSYNE_TDT_PACK_GRID: tools/pack_bench.py)
     uint32_t pack_cut = psy::kPackCut, pack_grid = psy::kPackGridCap;
     uint64_t large_min = 256 * 1024;  // messages (decode: decoded blobs) above this take the tiled path
@@ -398,6 +407,18 @@ __global__ __launch_bounds__(256) void tdt_encode_copy_kernel(psy::EncodeArgs a)
     }
 }
 
+// the size pass (MODE_SIZES) over the copy list: the marker and the payload, nothing is copied (one
+// thread per entry; the batch is read through its pair table)
+__global__ __launch_bounds__(256) void tdt_encode_copy_sizes_kernel(psy::EncodeArgs a) {
+    const uint32_t n = *a.list_count;
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) {
+        const uint32_t msg = a.list[i];
+        const uint64_t len = a.in_off[psy::table_at<true>(msg, 1)] - a.in_off[psy::table_at<true>(msg, 0)];
+        if (a.status) a.status[msg] = psy::ST_OK;
+        if (a.out_len) a.out_len[msg] = len + 4;
+    }
+}
+
 // decode: payload of a UNCP blob into its slot
 template <bool PAIR = false>
 __global__ __launch_bounds__(256) void tdt_decode_copy_kernel(psy::DecodeArgs a) {
@@ -513,6 +534,32 @@ int launch_table(PlanWS &pw, const Scatter &v, uint32_t n, bool in_table, unsign
     HIPCHK(hipGetLastError());
     in_pair = reinterpret_cast<const uint64_t *>(t.in_pair);
     out_pair = reinterpret_cast<const uint64_t *>(t.out_pair);
+    return TDT_OK;
+}
+
+// A contiguous batch read through the PAIR instances (tdt_encoded_sizes_batch: the size pass has no
+// instances of its own for offset tables): message i is [base + off[i], base + off[i + 1]), and the
+// batch's bytes, off[n] - off[0], go to the plan counter the scattered table kernel sums them into.
+struct Contig {
+    const uint8_t *base;
+    const uint64_t *off;  // n + 1 entries
+};
+__global__ __launch_bounds__(256) void tdt_offsets_table_kernel(Contig g, uint32_t n, ulonglong2 *in_pair,
+                                                                unsigned long long *bytes) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t b = (uint64_t)(uintptr_t)g.base;
+    in_pair[i] = make_ulonglong2(b + g.off[i], b + g.off[i + 1]);
+    if (i == 0 && bytes) atomicAdd(bytes, (unsigned long long)(g.off[n] - g.off[0]));
+}
+int launch_offsets_table(PlanWS &pw, const Contig &g, uint32_t n, unsigned long long *bytes, const uint64_t *&in_pair,
+                         hipStream_t s) {
+    const psy::PlanLayout PL = psy::plan_layout(n, true);
+    if (pw.bytes < PL.bytes) return set_err(TDT_E_ARG, "plan buffer without room for the pair tables");
+    auto *tab = reinterpret_cast<ulonglong2 *>(pw.buf + PL.pair[psy::PT_IN]);
+    hipLaunchKernelGGL(tdt_offsets_table_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, g, n, tab, bytes);
+    HIPCHK(hipGetLastError());
+    in_pair = reinterpret_cast<const uint64_t *>(tab);
     return TDT_OK;
 }
 
@@ -665,17 +712,25 @@ struct Routed {
 };
 
 // PAIR: a scattered batch (`v`): its pair tables first, then the same classes through the PAIR
-// instances; or one width of a mixed-width batch (`r`), whose tables are there already
-template <int WS, bool PAIR = false>
+// instances; or one width of a mixed-width batch (`r`), whose tables are there already.
+// MODE_SIZES (PAIR only): the size pass — the same plan, lists, grids and count history, through
+// the size-pass instances of every class; the emit pass of the tiles is not launched, the copy
+// list is sized by its own kernel, and the batch has no outputs: a scattered one's out_ptr / out_cap
+// are any readable arrays of n entries (the table kernel reads them, nothing reads what it writes
+// from them), a contiguous one (`g`) gets its input table from its offsets.
+template <int WS, bool PAIR = false, int MODE = psy::MODE_ENCODE>
 int launch_slotted(tdt_ctx *c, PlanWS &pw, psy::EncodeArgs a, hipStream_t s, const Scatter *v = nullptr,
-                   const Routed *r = nullptr) {
+                   const Routed *r = nullptr, const Contig *g = nullptr) {
+    static_assert(MODE == psy::MODE_ENCODE || (MODE == psy::MODE_SIZES && PAIR), "slotted encode, or its size pass");
+    constexpr bool SIZES = MODE == psy::MODE_SIZES;
     using namespace psy;  // (counter, list and kernel names)
     const uint32_t n = a.n_msgs;
     // the list-entry prefetch of the slotted kernels (EncodeArgs::list) reads entry
     // min(i, n - 1) of a class list before its count: n >= 1, and every list holds n entries
     // (ensure_plan: five lists of n entries behind the counters)
     if (n == 0) return set_err(TDT_E_ARG, "slotted encode launch without messages");
-    if (PAIR != (v != nullptr || r != nullptr)) return set_err(TDT_E_ARG, "scattered launch without its arrays");
+    if (PAIR != (v != nullptr || r != nullptr || g != nullptr)) return set_err(TDT_E_ARG, "scattered launch without its arrays");
+    if (g && !SIZES) return set_err(TDT_E_ARG, "a contiguous batch runs the PAIR instances in the size pass only");
     int st = ensure_plan(pw, n, s, PAIR && !r);
     if (st) return st;
     const PlanLayout PL = plan_layout(n);
@@ -709,8 +764,15 @@ int launch_slotted(tdt_ctx *c, PlanWS &pw, psy::EncodeArgs a, hipStream_t s, con
         if (r) {
             a.in_off = r->in_pair;
             a.slot_off = r->out_pair;
+        } else if (g) {
+            if ((st = launch_offsets_table(pw, *g, n, cnt64 + EC_BYTES, a.in_off, s))) return st;
         } else if ((st = launch_table(pw, *v, n, true, cnt64 + EC_BYTES, a.in_off, a.slot_off, s))) {
             return st;
+        }
+        if constexpr (SIZES) {  // the table holds addresses; there are no slots, and nothing may read any
+            a.in = nullptr;
+            a.out = nullptr;
+            a.slot_off = nullptr;
         }
     }
     PlanArgs p{a.in, a.in_off, n, cnt64, list(EL_SMALL), list(EL_MEDIUM), list(EL_MID), list(EL_BIG), list(EL_COPY),
@@ -748,16 +810,21 @@ int launch_slotted(tdt_ctx *c, PlanWS &pw, psy::EncodeArgs a, hipStream_t s, con
         a.tcap = tcap;
         auto tile_pass = [&](auto TL, EncCount k, uint32_t bound) {  // (no main launch before any count is known)
             cls(nullptr, k, guess(H, k, bound, 0), bound, 512, ovf512, ts,
-                tdt_encode_kernel<WS, 512, 8, MODE_ENCODE, 0, TL(), 0, PATH_BOTH, PAIR>,
-                tdt_encode_kernel<WS, 512, 8, MODE_ENCODE, 0, TL(), 1, PATH_BOTH, PAIR>);
+                tdt_encode_kernel<WS, 512, 8, MODE, 0, TL(), 0, PATH_BOTH, PAIR>,
+                tdt_encode_kernel<WS, 512, 8, MODE, 0, TL(), 1, PATH_BOTH, PAIR>);
         };
         tile_pass(Int<1>{}, EC_SPANS, scap);  // span histograms (and counts under the speculated mapping)
         tile_pass(Int<4>{}, EC_LARGE, lcap);  // mapping per large message; lists the tiles to count again
         if (!capturing && (st = record_counts(H, cnt, n, ts))) return st;
         tile_pass(Int<2>{}, EC_RECOUNT, tcap);  // per-tile counts of the listed tiles
-        hipLaunchKernelGGL((tdt_encode_lscan_kernel<WS, PAIR>), dim3(std::max(1u, std::min(lcap, 1024u))), dim3(64), 0, ts, a,
-                           cnt + lo32(EC_LARGE), lcap);
-        tile_pass(Int<3>{}, EC_TILES, tcap);  // emit
+        if constexpr (SIZES) {  // the scan alone: it has the pair counts, and there is nothing to emit
+            hipLaunchKernelGGL((tdt_encode_lscan_sizes_kernel<WS>), dim3(std::max(1u, std::min(lcap, 1024u))), dim3(64), 0, ts,
+                               a, cnt + lo32(EC_LARGE), lcap);
+        } else {
+            hipLaunchKernelGGL((tdt_encode_lscan_kernel<WS, PAIR>), dim3(std::max(1u, std::min(lcap, 1024u))), dim3(64), 0, ts, a,
+                               cnt + lo32(EC_LARGE), lcap);
+            tile_pass(Int<3>{}, EC_TILES, tcap);  // emit
+        }
     }
     // medium messages: one workgroup per list entry — the big list first (longer or unaligned
     // messages: the streaming-only kernel; a long team started last would run alone in the
@@ -766,28 +833,32 @@ int launch_slotted(tdt_ctx *c, PlanWS &pw, psy::EncodeArgs a, hipStream_t s, con
     // is empty); the big list has no main launch when the history says it is empty
     a.list2 = nullptr;
     cls(list(EL_BIG), EC_BIG, H.valid && !H[EC_BIG] ? 0u : guess(H, EC_BIG, n, n), n, 512, ovf512, s,
-        tdt_encode_kernel<WS, 512, 8, MODE_ENCODE, 0, 0, 0, PATH_STREAM, PAIR>,
-        tdt_encode_kernel<WS, 512, 8, MODE_ENCODE, 0, 0, 1, PATH_STREAM, PAIR>);
+        tdt_encode_kernel<WS, 512, 8, MODE, 0, 0, 0, PATH_STREAM, PAIR>,
+        tdt_encode_kernel<WS, 512, 8, MODE, 0, 0, 1, PATH_STREAM, PAIR>);
     cls(list(EL_MEDIUM), EC_MEDIUM, guess(H, EC_MEDIUM, n, n), n, 512, ovf512, s,
-        tdt_encode_kernel<WS, 512, 8, MODE_ENCODE, 0, 0, 0, PATH_RES, PAIR>,
-        tdt_encode_kernel<WS, 512, 8, MODE_ENCODE, 0, 0, 1, PATH_RES, PAIR>);
+        tdt_encode_kernel<WS, 512, 8, MODE, 0, 0, 0, PATH_RES, PAIR>,
+        tdt_encode_kernel<WS, 512, 8, MODE, 0, 0, 1, PATH_RES, PAIR>);
     // the small, copy and mid-sized lists behind the tile pipeline on the side stream (the two
     // streams' loads balance better: C4's tile pipeline is shorter than its medium list)
     const hipStream_t ss = forked && !c->small_main ? pw.side : s;
     if (small_on)  // one-wave teams
         cls(list(EL_SMALL), EC_SMALL, guess(H, EC_SMALL, n, n), n, 64, ovf64, ss,
-            tdt_encode_kernel<WS, 64, 4, MODE_ENCODE, 0, 0, 0, PATH_BOTH, PAIR>,
-            tdt_encode_kernel<WS, 64, 4, MODE_ENCODE, 0, 0, 1, PATH_BOTH, PAIR>);
+            tdt_encode_kernel<WS, 64, 4, MODE, 0, 0, 0, PATH_BOTH, PAIR>,
+            tdt_encode_kernel<WS, 64, 4, MODE, 0, 0, 1, PATH_BOTH, PAIR>);
     if (copy_on) {  // passthrough copies
         a.list = list(EL_COPY);
         a.list_count = cnt + lo32(EC_UNCP);
-        hipLaunchKernelGGL(tdt_encode_copy_kernel<PAIR>, dim3(std::max(1u, std::min((uint32_t)c->cus * c->copy_wgs, (n + 15) / 16))),
-                           dim3(256), 0, ss, a);
+        if constexpr (SIZES)
+            hipLaunchKernelGGL(tdt_encode_copy_sizes_kernel, dim3(std::max(1u, std::min((uint32_t)c->cus, (n + 255) / 256))),
+                               dim3(256), 0, ss, a);
+        else
+            hipLaunchKernelGGL(tdt_encode_copy_kernel<PAIR>,
+                               dim3(std::max(1u, std::min((uint32_t)c->cus * c->copy_wgs, (n + 15) / 16))), dim3(256), 0, ss, a);
     }
     if (mid_on)  // 256-lane teams
         cls(list(EL_MID), EC_MID, guess(H, EC_MID, n, n), n, 256, ovf256, ss,
-            tdt_encode_kernel<WS, 256, 8, MODE_ENCODE, 0, 0, 0, PATH_BOTH, PAIR>,
-            tdt_encode_kernel<WS, 256, 8, MODE_ENCODE, 0, 0, 1, PATH_BOTH, PAIR>);
+            tdt_encode_kernel<WS, 256, 8, MODE, 0, 0, 0, PATH_BOTH, PAIR>,
+            tdt_encode_kernel<WS, 256, 8, MODE, 0, 0, 1, PATH_BOTH, PAIR>);
     if (forked) return join_side(pw, s);
     return TDT_OK;
 }
@@ -907,8 +978,10 @@ void wire_decode(psy::DecodeArgs &a, uint8_t *wsp, bool lookback) {
 int tuned_index(int ws) { return ws == 1 ? 0 : ws == 2 ? 1 : ws == 4 ? 2 : ws == 8 ? 3 : 4; }
 int prep(tdt_ctx *c, uint32_t n_msgs, hipStream_t s, uint8_t *&wsp, bool lookback);  // (below)
 
+// mode: MODE_ENCODE, or MODE_SIZES — the size pass of every width over the same routes and plan
+// workspaces (v.out_ptr / v.out_cap: any readable arrays of n entries, see launch_slotted)
 int encode_mixed(tdt_ctx *c, const Scatter &v, const int32_t *d_word_size, uint64_t width_mask, uint32_t n,
-                 uint64_t *d_out_len, int32_t *d_status, hipStream_t s) {
+                 uint64_t *d_out_len, int32_t *d_status, hipStream_t s, int mode = psy::MODE_ENCODE) {
     if (!c) return set_err(TDT_E_ARG, "null context");
     if (n == 0) return TDT_OK;
     if (!(v.ptr && v.size && v.out_ptr && v.out_cap && d_word_size))
@@ -962,12 +1035,15 @@ int encode_mixed(tdt_ctx *c, const Scatter &v, const int32_t *d_word_size, uint6
         const Routed r{reinterpret_cast<const uint64_t *>(t.in_pair[k]), reinterpret_cast<const uint64_t *>(t.out_pair[k])};
         if (q.tuned) {
             PlanWS &pw = *c->mx_pw[tuned_index(q.ws)];
-            with_word_size(q.ws, [&](auto W) { st = launch_slotted<W(), true>(c, pw, a, s, nullptr, &r); });
+            with_word_size(q.ws, [&](auto W) {
+                st = mode == psy::MODE_SIZES ? launch_slotted<W(), true, psy::MODE_SIZES>(c, pw, a, s, nullptr, &r)
+                                             : launch_slotted<W(), true>(c, pw, a, s, nullptr, &r);
+            });
         } else {
             psy::EncodeArgs g = a;
             g.in_off = r.in_pair;
-            g.slot_off = r.out_pair;
-            st = launch_any_encode(g, q.ws, psy::MODE_ENCODE, s, true);
+            g.slot_off = mode == psy::MODE_SIZES ? nullptr : r.out_pair;
+            st = launch_any_encode(g, q.ws, mode, s, true);
         }
         if (st) return st;
     }
@@ -1064,6 +1140,42 @@ int encode_common(tdt_ctx *c, int mode, psy::EncodeArgs a, const Where &w) {
         st = launch_encode<psy::MODE_MAPPED, 1>(c, a, s, w.small_teams);
     } else {
         st = launch_encode<psy::MODE_ANALYZE, 1>(c, a, s, w.small_teams);
+    }
+    if (st) return st;
+    HIPCHK(hipGetLastError());
+    return TDT_OK;
+}
+
+// The size pass at the context's width (tdt_encoded_sizes_batch / _v): d_enc[i] and d_status[i] are
+// what the scattered encode reports for a slot of the encode bound.  One of `v` (scattered: ptr and
+// size; there are no outputs, and out_ptr / out_cap name the size array, see launch_slotted) and `g`
+// (contiguous) names the batch.  The plan workspace and count history are the encode's own: both
+// passes plan the same batch into the same lists.
+int encoded_sizes_one(tdt_ctx *c, const Scatter *v, const Contig *g, uint32_t n, uint64_t *d_enc, int32_t *d_status,
+                      hipStream_t s) {
+    if (!c) return set_err(TDT_E_ARG, "null context");
+    if (n == 0) return TDT_OK;
+    if (!d_enc || (v && !(v->ptr && v->size)) || (g && !g->off)) return set_err(TDT_E_ARG, "null pointer, size or output array");
+    std::lock_guard<std::mutex> lk(c->mu);
+    uint8_t *wsp = nullptr;
+    int st = prep(c, n, s, wsp, false);
+    if (st) return st;
+    psy::EncodeArgs a{};
+    a.n_msgs = n;
+    a.status = d_status;
+    a.out_len = d_enc;
+    wire_encode(c, a, wsp);
+    if (!with_word_size(c->cfg.word_size, [&](auto W) {
+            st = launch_slotted<W(), true, psy::MODE_SIZES>(c, c->pw, a, s, v, nullptr, g);
+        })) {
+        // generic widths: one workgroup per message, no plan (the plan buffer holds the input table alone)
+        if (!psy::anyws_generic(c->cfg.word_size)) return set_err(TDT_E_UNSUPPORTED, "word_size not supported on the GPU path");
+        if ((st = ensure_plan(c->pw, n, s, true))) return st;
+        st = g ? launch_offsets_table(c->pw, *g, n, nullptr, a.in_off, s)
+               : launch_table(c->pw, *v, n, true, nullptr, a.in_off, a.slot_off, s);
+        if (st) return st;
+        a.slot_off = nullptr;
+        st = launch_any_encode(a, c->cfg.word_size, psy::MODE_SIZES, s, true);
     }
     if (st) return st;
     HIPCHK(hipGetLastError());
@@ -2273,6 +2385,7 @@ int tdt_ctx_set_option(tdt_ctx *ctx, int option, uint64_t value) {
         case TDT_OPT_NO_SIDE_STREAM: ctx->no_side = value != 0; return TDT_OK;
         case TDT_OPT_SMALL_ON_CALLER_STREAM: ctx->small_main = value != 0; return TDT_OK;
         case TDT_OPT_NO_TWO_PHASE: ctx->no_two_phase = value != 0; return TDT_OK;
+        case TDT_OPT_PACK_SIZES_FIRST: ctx->pack_sizes_first = value != 0; return TDT_OK;
     }
     return set_err(TDT_E_ARG, "unknown option");
 }
@@ -2519,6 +2632,31 @@ int tdt_encode_batch_vp(tdt_ctx *ctx, const uint8_t *const *d_msgs, const uint64
     if (total_bytes > (1ull << 62)) return set_err(TDT_E_ARG, "total_bytes too large");
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(hipSetDevice(ctx->device));
+    uint64_t *sf_idx = nullptr;  // sizes first: blob addresses (n) | capacities (n)
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        if (ctx->pack_sizes_first) {
+            if (int st = ensure_cp(ctx, 2ull * n_msgs, 0, s, true)) return st;
+            sf_idx = ctx->cp_idx;
+        }
+    }
+    if (sf_idx) {
+        // Sizes first: the exact lengths into d_out_off (the size pass), scanned in place into the
+        // offsets, each blob's slot [off[i], off[i+1]) of d_out — capacity 0 where it would end past
+        // out_cap — and the scattered / mixed encode straight into those slots.  No scratch: total_bytes
+        // plays no part, cp_buf is not touched.
+        uint64_t *ptr = sf_idx, *cap = sf_idx + n_msgs;
+        const uint64_t *msgs = reinterpret_cast<const uint64_t *>(d_msgs);
+        const Scatter vs{msgs, d_sizes, d_sizes, d_sizes};  // (the size pass has no outputs: launch_slotted)
+        int st = d_word_size ? encode_mixed(ctx, vs, d_word_size, width_mask, n_msgs, d_out_off, d_status, s, psy::MODE_SIZES)
+                             : encoded_sizes_one(ctx, &vs, nullptr, n_msgs, d_out_off, d_status, s);
+        if (st) return st;
+        if ((st = scan_sizes(ctx, d_out_off, n_msgs, s))) return st;
+        HIPCHK((hipError_t)psy::launch_pack_exact_slots(d_out_off, d_out, out_cap, ptr, cap, n_msgs, s));
+        const Scatter v{msgs, d_sizes, ptr, cap};
+        return d_word_size ? encode_mixed(ctx, v, d_word_size, width_mask, n_msgs, nullptr, d_status, s)
+                           : encode_scattered(ctx, v, n_msgs, nullptr, d_status, stream);
+    }
     // the scratch: every blob in a slot of its encode bound, Σ bounds <= 2·total_bytes + n·(28 + 4·wmax);
     // the tables: slots (n + 1) | blob addresses (n) | capacities (n) | lengths (n)
     uint8_t *buf;
@@ -2540,6 +2678,22 @@ int tdt_encode_batch_vp(tdt_ctx *ctx, const uint8_t *const *d_msgs, const uint64
                                : encode_scattered(ctx, v, n_msgs, len, d_status, stream);
     if (st) return st;
     return pack_common(ctx, ptr, len, n_msgs, d_out, out_cap, d_out_off, d_status, true, s);
+}
+
+int tdt_encoded_sizes_batch(tdt_ctx *ctx, const uint8_t *d_in, const uint64_t *d_in_off, uint32_t n_msgs,
+                            uint64_t *d_enc_sizes, int32_t *d_status, void *stream) {
+    const Contig g{d_in, d_in_off};
+    return encoded_sizes_one(ctx, nullptr, &g, n_msgs, d_enc_sizes, d_status, (hipStream_t)stream);
+}
+
+int tdt_encoded_sizes_v(tdt_ctx *ctx, const uint8_t *const *d_msgs, const uint64_t *d_sizes, const int32_t *d_word_size,
+                        uint64_t width_mask, uint32_t n_msgs, uint64_t *d_enc_sizes, int32_t *d_status, void *stream) {
+    const uint64_t *msgs = reinterpret_cast<const uint64_t *>(d_msgs);
+    const Scatter v{msgs, d_sizes, d_sizes, d_sizes};  // (the size pass has no outputs: launch_slotted)
+    if (!d_word_size) return encoded_sizes_one(ctx, &v, nullptr, n_msgs, d_enc_sizes, d_status, (hipStream_t)stream);
+    if (ctx && n_msgs && !d_enc_sizes) return set_err(TDT_E_ARG, "null output array");
+    return encode_mixed(ctx, v, d_word_size, width_mask, n_msgs, d_enc_sizes, d_status, (hipStream_t)stream,
+                        psy::MODE_SIZES);
 }
 
 int tdt_decode_batch_v(tdt_ctx *ctx, const uint8_t *const *d_blobs, const uint64_t *d_blob_len, uint32_t n_msgs,

@@ -49,7 +49,10 @@ namespace psy {
 static __constant__ __attribute__((aligned(16))) double c_log2_tab[128] = PSY_LOG2_TAB_INIT;
 static __constant__ __attribute__((aligned(16))) double c_log2_tab2[128] = PSY_LOG2_TAB2_INIT;
 
-enum { MODE_ENCODE = 0, MODE_MAPPED = 1, MODE_ANALYZE = 2 };
+// MODE_SIZES: the encode pipeline up to the pair counts — the length tdt_encode_batch_v would report
+// for a slot of the encode bound goes to out_len, and no blob byte is written (a.out and a.slot_off
+// are null: every site that would touch them is compiled out under `if constexpr` on the mode)
+enum { MODE_ENCODE = 0, MODE_MAPPED = 1, MODE_ANALYZE = 2, MODE_SIZES = 3 };
 
 // status codes (include/psyne_tdt.h)
 enum { ST_OK = 0, ST_SHORT = 1, ST_MAGIC = 2, ST_TRUNCATED = 3, ST_BAD_MAPPING = 4, ST_CAPACITY = 5,
@@ -386,7 +389,7 @@ enum { PATH_BOTH = 0, PATH_RES = 1, PATH_STREAM = 2 };
 template <int WS, int TEAM, int G, int MODE, int LB, int TL, int PATH = PATH_BOTH, bool CARM = false, bool PAIR = false>
 __device__ __forceinline__ void encode_one(const EncodeArgs &a, uint8_t *smem, uint32_t msg, uint32_t lj,
                                            uint32_t tile) {
-    static_assert(TL == 0 || (TEAM * G == (int)kTileGroups && MODE == MODE_ENCODE && !LB), "tile shape");
+    static_assert(TL == 0 || (TEAM * G == (int)kTileGroups && (MODE == MODE_ENCODE || MODE == MODE_SIZES) && !LB), "tile shape");
     constexpr uint32_t kTG = TL == 1 ? kTileGroups * kSpanTiles : kTileGroups;  // groups per team
     using Lay = EncLayout<WS, TEAM, LB>;
     constexpr int W = Lay::W;
@@ -410,7 +413,7 @@ __device__ __forceinline__ void encode_one(const EncodeArgs &a, uint8_t *smem, u
     // critical path between the count pass and the emit pass (round 6: loaded at its first use
     // instead, the C3 encode took 8.2-8.7 ms against 7.26)
     uint64_t slot_b = 0, slot_e = 0;
-    if constexpr (!LB) {
+    if constexpr (!LB && MODE != MODE_SIZES) {
         slot_b = a.slot_off[table_at<PAIR>(msg, 0)];
         slot_e = a.slot_off[table_at<PAIR>(msg, 1)];
     }
@@ -458,7 +461,13 @@ __device__ __forceinline__ void encode_one(const EncodeArgs &a, uint8_t *smem, u
 
     // ---------------------------------------------------------------- UNCP passthrough
     if (!compress) {
-        if constexpr (TL == 1) {
+        if constexpr (MODE == MODE_SIZES) {
+            // size pass: the marker and the payload (the span pass reports it once, as it does below)
+            if ((TL == 0 || (TL == 1 && tile == 0)) && tid == 0) {
+                if (a.status) a.status[msg] = ST_OK;
+                if (a.out_len) a.out_len[msg] = n + 4;
+            }
+        } else if constexpr (TL == 1) {
             const uint64_t E = n + 4;
             const bool fits = E <= slot_e - slot_b;
             if (tile == 0 && tid == 0) {
@@ -488,7 +497,7 @@ __device__ __forceinline__ void encode_one(const EncodeArgs &a, uint8_t *smem, u
     constexpr uint32_t kSpec = spec_mapbits<WS>();
     // the histogram pass counts run starts under the speculated mapping: tiled messages (TL 1,
     // one wave per tile) and streaming whole messages (TL 0)
-    constexpr bool SPECA1 = kSpec != 0xffffffffu && MODE == MODE_ENCODE && (TL == 0 || TL == 1);
+    constexpr bool SPECA1 = kSpec != 0xffffffffu && (MODE == MODE_ENCODE || MODE == MODE_SIZES) && (TL == 0 || TL == 1);
     // streaming rounds in flight per wave: the streaming-only kernel and the span pass have the
     // registers (37 / 30 VGPRs with one); kernels holding the resident body too keep one
     constexpr int PF = PATH == PATH_STREAM || TL == 1 ? 4 : 1;
@@ -1604,6 +1613,15 @@ __device__ __forceinline__ void encode_one(const EncodeArgs &a, uint8_t *smem, u
         } else {
             const uint64_t E = hdr + (4 + 2ull * P0) + (ns2 ? 4 + 2ull * P1 : 0);
             Eblob = E;
+            if constexpr (MODE == MODE_SIZES) {
+                // size pass: the pair counts are the answer — no slot, so no capacity test, and
+                // neither the header nor pass B below runs
+                if (tid == 0) {
+                    if (a.status) a.status[msg] = ST_OK;
+                    if (a.out_len) a.out_len[msg] = E;
+                }
+                return;
+            }
             bool fits = true;
             if constexpr (DEFER) {
                 // compacted, resident: publish the blob size now and take the offset only at the
@@ -2182,7 +2200,8 @@ __device__ __forceinline__ uint32_t entry_count(const EncodeArgs &a) {
 
 template <int WS, int TEAM, int G, int MODE, int LB, int TL = 0, int PS = 0, int PATH = PATH_BOTH, bool PAIR = false>
 __global__ __launch_bounds__(TEAM, PSY_ENC_WAVES(TEAM, LB)) void tdt_encode_kernel(EncodeArgs a) {
-    static_assert(!PAIR || (!LB && MODE == MODE_ENCODE), "scattered batches are slotted encodes");
+    static_assert(!PAIR || (!LB && (MODE == MODE_ENCODE || MODE == MODE_SIZES)), "scattered batches are slotted encodes");
+    static_assert(MODE != MODE_SIZES || (PAIR && TL != 3), "the size pass reads pair tables and never emits");
     using Lay = EncLayout<WS, TEAM, LB>;
     constexpr int W = Lay::W;
     __shared__ __attribute__((aligned(16))) uint8_t smem[Lay::BYTES];
@@ -2367,8 +2386,10 @@ __global__ __launch_bounds__(kPlanThreads) void tdt_encode_plan_kernel(PlanArgs 
 // the 255-cap chunk starts that carried run makes inside the tile before its first own run
 // start, prefix sums of the chunk starts — rewrites the records for the emit pass, and writes
 // the blob's size, status and header.
-template <int WS, bool PAIR = false>
-__global__ __launch_bounds__(64) void tdt_encode_lscan_kernel(EncodeArgs a, const uint32_t *lcnt, uint32_t lmax) {
+// SIZES: the size pass (MODE_SIZES) — the blob's size alone: no slot, no header, and the emit pass
+// that would read the rewritten records is never launched.
+template <int WS, bool PAIR, bool SIZES>
+__device__ __forceinline__ void encode_lscan(const EncodeArgs &a, const uint32_t *lcnt, uint32_t lmax) {
     const uint32_t nl = umin(*lcnt, lmax);
     const int lane = lane_id();
     for (uint32_t j = blockIdx.x; j < nl; j += gridDim.x) {
@@ -2421,6 +2442,13 @@ __global__ __launch_bounds__(64) void tdt_encode_lscan_kernel(EncodeArgs a, cons
         }
         const uint32_t hdr = 20 + 4 * WS;
         const uint64_t E = hdr + (4 + 2ull * Pt[0]) + (ns2 ? 4 + 2ull * Pt[1] : 0);
+        if constexpr (SIZES) {
+            if (lane == 0) {
+                if (a.status) a.status[msg] = ST_OK;
+                if (a.out_len) a.out_len[msg] = E;
+            }
+            continue;
+        }
         const uint64_t ob = a.slot_off[table_at<PAIR>(msg, 0)];
         const bool fits = E <= a.slot_off[table_at<PAIR>(msg, 1)] - ob;
         if (lane == 0) {
@@ -2448,6 +2476,14 @@ __global__ __launch_bounds__(64) void tdt_encode_lscan_kernel(EncodeArgs a, cons
         }
     }
 }
+template <int WS, bool PAIR = false>
+__global__ __launch_bounds__(64) void tdt_encode_lscan_kernel(EncodeArgs a, const uint32_t *lcnt, uint32_t lmax) {
+    encode_lscan<WS, PAIR, false>(a, lcnt, lmax);
+}
+template <int WS>
+__global__ __launch_bounds__(64) void tdt_encode_lscan_sizes_kernel(EncodeArgs a, const uint32_t *lcnt, uint32_t lmax) {
+    encode_lscan<WS, true, true>(a, lcnt, lmax);
+}
 
 // The kernel instances of one word size.  The product library instantiates them in
 // tdt_enc_ws.hip, one translation unit per word size (compiled in parallel), and tdt_api.hip
@@ -2469,5 +2505,14 @@ __global__ __launch_bounds__(64) void tdt_encode_lscan_kernel(EncodeArgs a, cons
     X(WS, 512, 8, 2, 0, 0) X(WS, 512, 8, 3, 0, 0) X(WS, 512, 8, 4, 0, 0) X(WS, 64, 4, 0, 0, 0) X(WS, 512, 8, 1, 1, 0)  \
     X(WS, 512, 8, 2, 1, 0) X(WS, 512, 8, 3, 1, 0) X(WS, 512, 8, 4, 1, 0) X(WS, 64, 4, 0, 1, 0) X(WS, 256, 8, 0, 0, 0)  \
     X(WS, 256, 8, 0, 1, 0)
+
+
+// The size pass (MODE_SIZES): the PAIR instances of every class and of the tile passes that write no
+// blob byte (TL 1 span, 4 map, 2 count; 3, the emit, has no size-pass form).  tdt_enc_sizes_ws.hip
+// instantiates them, one translation unit per word size.
+#define PSY_ENC_SIZES_INSTANCES(X, WS)                                                                            \
+    X(WS, 512, 8, 0, 0, 1) X(WS, 512, 8, 0, 1, 1) X(WS, 512, 8, 0, 0, 2) X(WS, 512, 8, 0, 1, 2) X(WS, 512, 8, 1, 0, 0) \
+    X(WS, 512, 8, 2, 0, 0) X(WS, 512, 8, 4, 0, 0) X(WS, 64, 4, 0, 0, 0) X(WS, 512, 8, 1, 1, 0) X(WS, 512, 8, 2, 1, 0)  \
+    X(WS, 512, 8, 4, 1, 0) X(WS, 64, 4, 0, 1, 0) X(WS, 256, 8, 0, 0, 0) X(WS, 256, 8, 0, 1, 0)
 
 }  // namespace psy

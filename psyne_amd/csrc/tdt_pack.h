@@ -102,6 +102,19 @@ PSY_PACK_HD PackSeg pack_segment(uint64_t o0, uint64_t o1, PackPiece pc) {
     return PackSeg{b - o0, b, e - b};
 }
 
+// ---- sizes-first slots (tdt_encode_batch_vp with TDT_OPT_PACK_SIZES_FIRST) -------------------------
+// The blobs' exact sizes are known before a byte is written (the size pass), so blob i is encoded
+// straight into the packed output: its slot is [o0, o1) = [off[i], off[i+1]) of it when that ends
+// inside out_cap, and a slot of capacity 0 — TDT_E_CAPACITY, no byte written — when it does not.
+// The offsets ascend, so the accepted slots tile [0, min(total, out_cap)) up to the first blob
+// that ends past out_cap, and every slot from that blob on has capacity 0.
+struct PackSlot {
+    uint64_t off, cap;  // blob i at out + off, `cap` bytes
+};
+PSY_PACK_HD PackSlot pack_exact_slot(uint64_t o0, uint64_t o1, uint64_t out_cap) {
+    return PackSlot{o0, o1 <= out_cap ? o1 - o0 : 0u};
+}
+
 // ---- launchers (tdt_pack.hip; `stream` is a hipStream_t; the result a hipError_t as int) ----
 // off[0..n] holds the scanned lengths.  status (may be null): TDT_E_CAPACITY for blob i with
 // off[i+1] > out_cap, else TDT_OK — or, with keep_errors, left as it is unless it was TDT_OK.
@@ -114,5 +127,9 @@ int launch_pack_bounds(const uint64_t *size, const int32_t *ws, int32_t ws_all, 
 // slot i = buf + off[i], its capacity off[i+1] - off[i], or 0 where the slot would end past buf_bytes
 int launch_pack_slots(const uint64_t *off, uint8_t *buf, uint64_t buf_bytes, uint64_t *ptr, uint64_t *cap,
                       uint32_t n, void *stream);
+
+// ptr[i] = out + off[i] and cap[i] as pack_exact_slot gives it for out_cap
+int launch_pack_exact_slots(const uint64_t *off, uint8_t *out, uint64_t out_cap, uint64_t *ptr, uint64_t *cap,
+                            uint32_t n, void *stream);
 
 }  // namespace psy

@@ -134,6 +134,15 @@ __global__ __launch_bounds__(256) void tdt_pack_slots_kernel(const uint64_t *off
     cap[i] = o1 <= buf_bytes ? o1 - o0 : 0;
 }
 
+__global__ __launch_bounds__(256) void tdt_pack_exact_slots_kernel(const uint64_t *off, uint8_t *out, uint64_t out_cap,
+                                                                   uint64_t *ptr, uint64_t *cap, uint32_t n) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const PackSlot sl = pack_exact_slot(off[i], off[i + 1], out_cap);
+    ptr[i] = (uint64_t)(uintptr_t)out + sl.off;
+    cap[i] = sl.cap;
+}
+
 }  // namespace
 
 int launch_pack(const uint64_t *blobs, const uint64_t *off, uint32_t n, uint8_t *out, uint64_t out_cap, int32_t *status,
@@ -156,6 +165,13 @@ int launch_pack_slots(const uint64_t *off, uint8_t *buf, uint64_t buf_bytes, uin
                       void *stream) {
     hipLaunchKernelGGL(tdt_pack_slots_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, off, buf,
                        buf_bytes, ptr, cap, n);
+    return (int)hipGetLastError();
+}
+
+int launch_pack_exact_slots(const uint64_t *off, uint8_t *out, uint64_t out_cap, uint64_t *ptr, uint64_t *cap, uint32_t n,
+                            void *stream) {
+    hipLaunchKernelGGL(tdt_pack_exact_slots_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, off, out,
+                       out_cap, ptr, cap, n);
     return (int)hipGetLastError();
 }
 

@@ -20,6 +20,7 @@ torch is used only for device memory and streams; all codec work is in the HIP k
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import time
 from dataclasses import dataclass
@@ -301,6 +302,39 @@ class TdtCodec:
                                             self._stream(stream)))
         return sizes[:n], status[:n]
 
+    # ---- exact encoded sizes (how long blob i will be, before it is written) -----------------
+    def encoded_sizes(self, data, offsets, stream=None, enc_sizes=None, status=None):
+        """The exact length of the blob of message i = data[offsets[i]:offsets[i+1]] at this codec's
+        word_size, without encoding it: (sizes, status), int64 / int32 tensors on the GPU.  sizes[i]
+        is what encode_v reports for a capacity of the encode bound, and sizes[i] / message size the
+        message's transformation ratio.  enc_sizes / status: the caller's result tensors (n entries;
+        pass them when the call is captured into a graph, so that nothing is allocated in the capture
+        and every replay writes where the caller reads)."""
+        import torch
+        n = offsets.numel() - 1
+        sizes = enc_sizes if enc_sizes is not None else torch.empty(max(n, 1), dtype=torch.int64, device=offsets.device)
+        if status is None:
+            status = torch.empty(max(n, 1), dtype=torch.int32, device=offsets.device)
+        check(self._lib.tdt_encoded_sizes_batch(self._h, _ptr(data), _ptr(offsets), n, _ptr(sizes), _ptr(status),
+                                                self._stream(stream)))
+        return sizes[:n], status[:n]
+
+    def encoded_sizes_v(self, ptrs, sizes, word_sizes=None, width_mask=0, stream=None, enc_sizes=None, status=None):
+        """encoded_sizes for scattered messages (sizes[i] bytes at address ptrs[i], int64 tensors on the
+        GPU): at this codec's word_size (word_sizes None), or at word_sizes[i] per message with
+        width_mask as encode_vw takes them — a rejected width gets its status and size 0.  Returns
+        (enc_sizes, status); enc_sizes / status may be the caller's tensors, as for encoded_sizes."""
+        import torch
+        n = sizes.numel()
+        if n and word_sizes is not None and word_sizes.dtype != torch.int32:
+            raise ValueError("word_sizes must be an int32 tensor")
+        enc = enc_sizes if enc_sizes is not None else torch.empty(max(n, 1), dtype=torch.int64, device=sizes.device)
+        if status is None:
+            status = torch.empty(max(n, 1), dtype=torch.int32, device=sizes.device)
+        check(self._lib.tdt_encoded_sizes_v(self._h, _ptr(ptrs), _ptr(sizes), _ptr(word_sizes), int(width_mask), n,
+                                            _ptr(enc), _ptr(status), self._stream(stream)))
+        return enc[:n], status[:n]
+
     # ---- packed wire buffer (blobs back to back, one copy or send per batch) ----------------
     def pack_v(self, ptrs, lengths, out, out_offsets=None, status=None, stream=None):
         """Pack blob i = lengths[i] bytes at address ptrs[i] (int64 tensors on the GPU: the slots and
@@ -350,7 +384,7 @@ class TdtCodec:
         ptrs = np.array([t.data_ptr() if s else 0 for t, s in zip(tensors, sizes)], dtype=np.uint64).view(np.int64)
         return ptrs, sizes
 
-    def encode_tensors(self, tensors, out=None, stream=None, word_sizes=None, packed=False):
+    def encode_tensors(self, tensors, out=None, stream=None, word_sizes=None, packed=False, exact=False):
         """Encode a list of contiguous GPU tensors (message i = the bytes of tensors[i]) without
         packing them: blob i goes to out[slots[i]:slots[i+1]], the slots being the prefix sum of the
         encode bounds.  Returns (out, slots, lengths, status).
@@ -373,7 +407,14 @@ class TdtCodec:
         `out` defaults to the sum of the encode bounds, as in the slotted form: TDT does not fall back
         to the raw bytes when its run-length streams grow, so a blob of incompressible records reaches
         28 + 4*ws + 2*size and a buffer of the sizes plus a margin would not hold it.  A smaller `out`
-        may be passed: a blob that ends past it gets status 5 and offsets[n] still reports the need."""
+        may be passed: a blob that ends past it gets status 5 and offsets[n] still reports the need.
+
+        packed=True, exact=True allocates exactly what the blobs need instead: the tensors are sized
+        on the GPU (encoded_sizes_v), the sizes summed there, and the total is read back — ONE
+        synchronisation of the stream with the host, which the other forms do not have — then `out`
+        is allocated with that many bytes (a caller's `out` is ignored) and every blob is encoded
+        straight to its offset.  Returns (out, offsets, status) as packed=True does, with
+        out.numel() == offsets[n]."""
         import torch
         ptrs, sizes = self._tensor_table(tensors)
         n = len(tensors)
@@ -394,6 +435,30 @@ class TdtCodec:
             if bin(mask).count("1") > 8:
                 raise ValueError("more than 8 different word sizes in one call")
             ws = widths.astype(np.int64)
+        if exact and not packed:
+            raise ValueError("exact=True sizes the packed form: pass packed=True")
+        if packed and exact:
+            parts = [ptrs, sizes]  # one upload: addresses | sizes (| widths, two per word)
+            if widths is not None:
+                parts.append(np.concatenate([widths, np.zeros(n % 2, np.int32)]).view(np.int64))
+            d = torch.from_numpy(np.concatenate(parts)).to(dev, non_blocking=False)
+            dw = d[2 * n:].view(torch.int32)[:n] if widths is not None and n else None
+            enc, status = self.encoded_sizes_v(d[:n], d[n:2 * n], word_sizes=dw, width_mask=mask if dw is not None else 0,
+                                               stream=stream)
+            offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+            with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+                torch.cumsum(enc, 0, out=offsets[1:])
+                total = int(offsets[n].item()) if n else 0  # (the one read-back)
+                out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)[:total]
+                optrs = offsets[:n] + out.data_ptr()
+                caps = offsets[1:] - offsets[:n]
+            if n == 0:
+                return out, offsets, status
+            if dw is None:
+                _, status = self.encode_v(d[:n], d[n:2 * n], optrs, caps, stream=stream)
+            else:
+                _, status = self.encode_vw(d[:n], d[n:2 * n], dw, mask, optrs, caps, stream=stream)
+            return out, offsets, status[:n]
         slots = np.zeros(n + 1, np.int64)
         np.cumsum(np.maximum(sizes + 4, 28 + 4 * ws + 2 * sizes), out=slots[1:])
         if packed:
