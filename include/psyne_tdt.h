@@ -32,6 +32,8 @@
  *   tdt_encode_bound                  worst-case blob size (sizing out buffers)
  *   tdt_encoded_sizes_batch /         transformation_ratio (encoded size / original size) of each
  *   tdt_encoded_sizes_v               message BEFORE it is encoded: the exact blob length, no blob written
+ *   tdt_mappings_v /                  analyze_data's clustering kept between encodes: the mapping of each
+ *   tdt_encode_mapped_v / _vp         message as one word, and the scattered encodes with such mappings given
  *   tdt_last_error                    the reference's exception text (:128, :275)
  *
  * Wire format: identical bytes to the reference: UNCP marker
@@ -261,6 +263,10 @@ int tdt_pack_v(tdt_ctx *ctx, const uint8_t *const *d_blobs, const uint64_t *d_bl
  *     capacity 0.  The scratch is not used and total_bytes is ignored; every line of the contract
  *     above holds unchanged (the same bytes, the same d_out_off with the full need at [n_msgs], the
  *     same statuses, nothing written outside d_out[0 .. min(total, out_cap)), capturable once warm).
+ *     With the option at 2 the size pass also keeps every message's mapping (n more words of the
+ *     context's tables) and the second pass runs as the known-mapping encode (below) with them: the
+ *     analysis runs once per message instead of twice.  Bytes, offsets, statuses and the capture
+ *     rules are exactly those of value 1.
  * Replaces a loop of TDTCompressionProtocol::encode (:227-266) followed by a framed send of each
  * vector. */
 int tdt_encode_batch_vp(tdt_ctx *ctx, const uint8_t *const *d_msgs, const uint64_t *d_sizes,
@@ -291,6 +297,57 @@ int tdt_encoded_sizes_batch(tdt_ctx *ctx, const uint8_t *d_in, const uint64_t *d
 int tdt_encoded_sizes_v(tdt_ctx *ctx, const uint8_t *const *d_msgs, const uint64_t *d_sizes,
                         const int32_t *d_word_size, uint64_t width_mask, uint32_t n_msgs,
                         uint64_t *d_enc_sizes, int32_t *d_status, void *hip_stream);
+/* KNOWN MAPPINGS — the scattered encodes without the analysis.  A training process encodes the same
+ * tensors step after step, and the byte-plane mapping of an fp32 or bf16 gradient does not change
+ * between steps: tdt_mappings_v decides every message's mapping once (every K steps), and the mapped
+ * encodes between run neither histograms nor entropies nor the decision.
+ *   Mapping bits: one uint64_t per message; bit p is the stream (0 or 1) of byte position p, for
+ *     p < word_size — the int32 mapping of tdt_encode_with_mapping_batch (which stays as it is) with
+ *     mapping[p] at bit p.  One word per message, so a mixed-width list needs no layout of its own.
+ *
+ * tdt_mappings_v: tdt_encoded_sizes_v plus d_mapbits (n_msgs entries, device memory).  d_enc_sizes and
+ * d_status are exactly tdt_encoded_sizes_v's; d_mapbits[i] is the mapping the encode of message i
+ * decides (the margin-checked fast decision and the exact chains on near ties are the encode's own
+ * lines), and 0 for a message that takes the UNCP route or whose width is rejected.  Context rules,
+ * capture and the shared plan workspace as for tdt_encoded_sizes_v.
+ *
+ * tdt_encode_mapped_v: tdt_encode_batch_v (d_word_size == NULL: every message at the context's
+ * width, width_mask ignored) or tdt_encode_batch_vw with the caller's mapping d_mapbits[i] per message.
+ *   UNCP first: the UNCP routing (the policy, min_tensor_size, n % 4, n >= 64, n % word_size) is
+ *     evaluated first and is unchanged; the mapping of a message that takes it is ignored.
+ *   Same bytes: otherwise blob i, d_out_len[i] and d_status[i] are byte for byte what the reference
+ *     gives for that message at that width with mapping[p] = (d_mapbits[i] >> p) & 1 — what
+ *     tdt_encode_with_mapping_batch gives for the same bytes on a context of that width.  With
+ *     d_mapbits from tdt_mappings_v over the same bytes, context and metrics the result equals
+ *     tdt_encode_batch_v / _vw's in every byte, length and status.
+ *   Any mapping is valid: every mapping gives a blob that decodes to the message; a stale one costs
+ *     compression ratio, never correctness.
+ *   Statuses: a mapping with a bit at or above word_size set gives TDT_E_BAD_MAPPING, length 0 and
+ *     no byte of the output written.  TDT_E_CAPACITY, the rejected widths (TDT_E_CONFIG /
+ *     TDT_E_UNSUPPORTED / TDT_E_ARG) and the call-level mask errors are those of _v / _vw; a null
+ *     d_mapbits with n_msgs > 0 returns TDT_E_ARG.
+ *   Everything else — addressing, aliasing, size-0 messages, one stream per context, asynchronous,
+ *     nothing read back — is as for tdt_encode_batch_v.  The call plans into the encode's plan
+ *     workspace, classes, side stream and count history, so an ordinary encode warms the context for
+ *     a captured mapped call of that n_msgs (and mask), and the other way round (TDT_E_CAPTURE
+ *     otherwise).  d_mapbits is read on the device at run time: a replayed graph encodes with
+ *     whatever the array holds then.
+ *
+ * tdt_encode_mapped_vp: the packed contract of tdt_encode_batch_vp over those blobs; a
+ * TDT_E_BAD_MAPPING message occupies no bytes.  It always takes the two phases, whatever
+ * TDT_OPT_PACK_SIZES_FIRST says: the sizes-first form would need the sizes under the caller's mapping,
+ * and the size pass decides its mapping itself. */
+int tdt_mappings_v(tdt_ctx *ctx, const uint8_t *const *d_msgs, const uint64_t *d_sizes,
+                   const int32_t *d_word_size, uint64_t width_mask, uint32_t n_msgs,
+                   uint64_t *d_enc_sizes, uint64_t *d_mapbits, int32_t *d_status, void *hip_stream);
+int tdt_encode_mapped_v(tdt_ctx *ctx, const uint8_t *const *d_msgs, const uint64_t *d_sizes,
+                        const int32_t *d_word_size, uint64_t width_mask, uint32_t n_msgs,
+                        const uint64_t *d_mapbits, uint8_t *const *d_blobs, const uint64_t *d_blob_cap,
+                        uint64_t *d_out_len, int32_t *d_status, void *hip_stream);
+int tdt_encode_mapped_vp(tdt_ctx *ctx, const uint8_t *const *d_msgs, const uint64_t *d_sizes,
+                         const int32_t *d_word_size, uint64_t width_mask, uint32_t n_msgs,
+                         uint64_t total_bytes, const uint64_t *d_mapbits, uint8_t *d_out, uint64_t out_cap,
+                         uint64_t *d_out_off, int32_t *d_status, void *hip_stream);
 /* Decoded size of each scattered blob (0 with an error status), as tdt_decoded_sizes_batch. */
 int tdt_decoded_sizes_v(tdt_ctx *ctx, const uint8_t *const *d_blobs, const uint64_t *d_blob_len, uint32_t n_msgs,
                         uint64_t *d_sizes, int32_t *d_status, void *hip_stream);
@@ -364,7 +421,9 @@ int tdt_ctx_error_flags(tdt_ctx *ctx, void *hip_stream, uint32_t *flags);
 #define TDT_OPT_NO_TWO_PHASE 5            /* 1: compacted calls always take the one-pass kernels */
 #define TDT_OPT_COPY_THREADS 6            /* host threads staging pageable buffers (default <= 16) */
 #define TDT_OPT_PACK_SIZES_FIRST 7        /* 1: tdt_encode_batch_vp sizes the blobs first and encodes them in
-                                             place, without the scratch (default 0: the two phases) */
+                                             place, without the scratch (default 0: the two phases);
+                                             2: as 1, and the second pass reuses the mappings the size
+                                             pass decided (the known-mapping encode) */
 int tdt_ctx_set_option(tdt_ctx *ctx, int option, uint64_t value);
 
 /* Host-memory analyze (analyze_data :206-222): h_entropy n*ws doubles, h_mapping n*ws int32

@@ -2,6 +2,6 @@
 
 The product is libpsyne_tdt.so (C ABI: include/psyne_tdt.h) built from psyne_amd/csrc/;
 this package is its Python host mirror (psyne_amd.tdt)."""
-from .tdt import TDTConfig, TdtCodec, TDTCompressionProtocol, encode_bound  # noqa: F401
+from .tdt import TDTConfig, TdtCodec, TDTCompressionProtocol, encode_bound, mapbits_of, mapping_of  # noqa: F401
 
-__all__ = ["TDTConfig", "TdtCodec", "TDTCompressionProtocol", "encode_bound"]
+__all__ = ["TDTConfig", "TdtCodec", "TDTCompressionProtocol", "encode_bound", "mapbits_of", "mapping_of"]

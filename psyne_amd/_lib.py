@@ -53,6 +53,10 @@ SIGNATURES = {
                                       _vp]),
     "tdt_encoded_sizes_batch": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp]),
     "tdt_encoded_sizes_v": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint64, C.c_uint32, _vp, _vp, _vp]),
+    "tdt_mappings_v": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint64, C.c_uint32, _vp, _vp, _vp, _vp]),
+    "tdt_encode_mapped_v": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint64, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tdt_encode_mapped_vp": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint64, C.c_uint32, C.c_uint64, _vp, _vp, C.c_uint64, _vp,
+                                       _vp, _vp]),
     "tdt_decode_batch_v": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp]),
     "tdt_decoded_sizes_v": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp]),
     "tdt_encode_slots": (C.c_int, [_vp, _vp, C.c_uint32, _vp, _vp]),

@@ -20,13 +20,14 @@ ARCH = os.environ.get("PSYNE_ARCH", "gfx950")
 SOURCES = [CSRC / "tdt_api.hip"]  # (diagnostic single-TU builds compile this file alone)
 ENC_WS_SRC = CSRC / "tdt_enc_ws.hip"  # the encode kernels of one word size
 ENC_SIZES_WS_SRC = CSRC / "tdt_enc_sizes_ws.hip"  # the size-pass kernels (tdt_encoded_sizes_*) of one word size
+ENC_MAPPED_WS_SRC = CSRC / "tdt_enc_mapped_ws.hip"  # the known-mapping scattered encode (tdt_encode_mapped_v) of one word size
 WORD_SIZES = (1, 2, 4, 8, 16)
 ANYWS_SRC = CSRC / "tdt_anyws.hip"  # encode and decode of every other word size up to 64
 SOURCES.append(ANYWS_SRC)
 PACK_SRC = CSRC / "tdt_pack.hip"  # the pack kernel of tdt_pack_v / tdt_encode_batch_vp
 SOURCES.append(PACK_SRC)
 # every source and header under csrc/ (tdt_api.hip includes the headers, directly or not)
-DEPS = SOURCES + [ENC_WS_SRC, ENC_SIZES_WS_SRC] + sorted(CSRC.glob("*.h")) + [ROOT / "include" / "psyne_tdt.h"]
+DEPS = SOURCES + [ENC_WS_SRC, ENC_SIZES_WS_SRC, ENC_MAPPED_WS_SRC] + sorted(CSRC.glob("*.h")) + [ROOT / "include" / "psyne_tdt.h"]
 OBJ_DIR = PKG / "build"
 
 
@@ -38,8 +39,9 @@ def needs_build() -> bool:
 
 
 def build(force: bool = False, verbose: bool = False) -> pathlib.Path:
-    """Compile tdt_api.hip, tdt_anyws.hip, tdt_pack.hip and one tdt_enc_ws.hip object per word size in parallel
-    (the encode kernels dominate the compile time), then link libpsyne_tdt.so."""
+    """Compile tdt_api.hip, tdt_anyws.hip, tdt_pack.hip and one tdt_enc_ws.hip, tdt_enc_sizes_ws.hip and
+    tdt_enc_mapped_ws.hip object per word size in parallel (the encode kernels dominate the compile time), then
+    link libpsyne_tdt.so."""
     if force or needs_build():
         OBJ_DIR.mkdir(exist_ok=True)
         base = [HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-I", str(ROOT / "include")]
@@ -50,6 +52,8 @@ def build(force: bool = False, verbose: bool = False) -> pathlib.Path:
             jobs.append((base + [f"-DPSY_INST_WS={ws}", "-c", str(ENC_WS_SRC), "-o", str(o)], o))
             o = OBJ_DIR / f"tdt_enc_sizes_ws{ws}.o"
             jobs.append((base + [f"-DPSY_INST_WS={ws}", "-c", str(ENC_SIZES_WS_SRC), "-o", str(o)], o))
+            o = OBJ_DIR / f"tdt_enc_mapped_ws{ws}.o"
+            jobs.append((base + [f"-DPSY_INST_WS={ws}", "-c", str(ENC_MAPPED_WS_SRC), "-o", str(o)], o))
         procs = []
         for cmd, _ in jobs:
             if verbose:

@@ -36,9 +36,11 @@ inline bool anyws_generic(int ws) { return ws >= 1 && ws <= kAnyWsMax && !anyws_
 
 // Encode (mode MODE_ENCODE / MODE_MAPPED: slotted output, a.slot_off set; MODE_ANALYZE:
 // histograms, entropies and mapping, no blob) of a.n_msgs messages at word size ws.
-// pair (MODE_ENCODE only): a.in_off and a.slot_off are the (begin, end) pair tables of a scattered
-// batch (table_at, tdt_plan.h); or, pair with MODE_SIZES, the size pass: a.in_off alone is a pair
-// table, the blob lengths go to a.out_len and nothing else is written.  Returns a hipError_t as
+// pair (MODE_ENCODE / MODE_MAPPED): a.in_off and a.slot_off are the (begin, end) pair tables of a
+// scattered batch (table_at, tdt_plan.h), and a MODE_MAPPED batch's a.mapping_in holds one u64 of
+// mapping bits per message (tdt_mapbits.h); or, pair with MODE_SIZES, the size pass: a.in_off alone
+// is a pair table, the blob lengths go to a.out_len (and, a.map_out set, the mapping bits of every
+// compressed message there, one u64 each) and nothing else is written.  Returns a hipError_t as
 // int (0: launched).
 int launch_encode_any(const EncodeArgs &a, int ws, int mode, hipStream_t s, bool pair = false);
 

@@ -119,7 +119,12 @@ __global__ __launch_bounds__(kAnyTeam) void tdt_encode_any_kernel(EncodeArgs a, 
     if constexpr (MODE == MODE_MAPPED) {
         if (tid == 0) s_bad = 0u;
         __syncthreads();
-        if (tid < ws) {
+        if constexpr (PAIR) {
+            // scattered batches: one u64 of mapping bits per message; a bit at or above ws is a bad mapping
+            const uint64_t bits = reinterpret_cast<const uint64_t *>(a.mapping_in)[msg];
+            if (tid == 0 && !mapbits_ok(bits, (int)ws)) s_bad = 1u;
+            if (tid < ws) s_map[tid] = mapbits_at(bits, (int)tid);
+        } else if (tid < ws) {
             const int32_t m = a.mapping_in[(uint64_t)msg * ws + tid];
             if (m < 0 || m > 1) s_bad = 1u;
             s_map[tid] = (uint32_t)(m & 1);
@@ -359,6 +364,13 @@ __global__ __launch_bounds__(kAnyTeam) void tdt_encode_any_kernel(EncodeArgs a, 
         if (tid == 0) {
             if (a.status) a.status[msg] = fits ? ST_OK : ST_CAPACITY;
             if (a.out_len) a.out_len[msg] = fits ? o : 0;
+            if constexpr (MODE == MODE_SIZES) {
+                if (a.map_out) {  // (tdt_mappings_v: the mapping bits beside the size)
+                    uint64_t bits = 0;
+                    for (uint32_t p = 0; p < ws; ++p) bits |= (uint64_t)s_map[p] << p;
+                    reinterpret_cast<uint64_t *>(a.map_out)[msg] = bits;
+                }
+            }
         }
     }
 }
@@ -488,7 +500,8 @@ __global__ __launch_bounds__(kAnyTeam) void tdt_decode_any_kernel(DecodeArgs a) 
 
 int launch_encode_any(const EncodeArgs &a, int ws, int mode, hipStream_t s, bool pair) {
     if (a.n_msgs == 0) return 0;
-    if (pair ? mode != MODE_ENCODE && mode != MODE_SIZES : mode == MODE_SIZES) return (int)hipErrorInvalidValue;
+    if (pair ? mode != MODE_ENCODE && mode != MODE_SIZES && mode != MODE_MAPPED : mode == MODE_SIZES)
+        return (int)hipErrorInvalidValue;
     const dim3 g(a.n_msgs), t(kAnyTeam);
     const uint32_t w = (uint32_t)ws;
 #define PSY_ANY_HP(MODE_, PAIR_)                                                                              \
@@ -499,6 +512,7 @@ int launch_encode_any(const EncodeArgs &a, int ws, int mode, hipStream_t s, bool
         else hipLaunchKernelGGL((tdt_encode_any_kernel<MODE_, 64, PAIR_>), g, t, 0, s, a, w);                 \
     } while (0)
     if (pair && mode == MODE_SIZES) PSY_ANY_HP(MODE_SIZES, true);
+    else if (pair && mode == MODE_MAPPED) hipLaunchKernelGGL((tdt_encode_any_kernel<MODE_MAPPED, 1, true>), g, t, 0, s, a, w);
     else if (pair) PSY_ANY_HP(MODE_ENCODE, true);
     else if (mode == MODE_ENCODE) PSY_ANY_HP(MODE_ENCODE, false);
     else if (mode == MODE_ANALYZE) PSY_ANY_HP(MODE_ANALYZE, false);

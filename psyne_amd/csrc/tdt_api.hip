@@ -24,6 +24,7 @@
 #include "tdt_copypool.h"
 #include "tdt_decode.h"
 #include "tdt_encode.h"
+#include "tdt_enc_lmap.h"
 #include "tdt_grow.h"
 #include "tdt_pack.h"
 #include "tdt_plan.h"
@@ -42,7 +43,11 @@
     PSY_ENC_PAIR_INSTANCES(PSY_ENC_PAIR_EXT, WS)                                                                    \
     extern template __global__ void psy::tdt_encode_lscan_kernel<WS, true>(psy::EncodeArgs, const uint32_t *, uint32_t); \
     PSY_ENC_SIZES_INSTANCES(PSY_ENC_SIZES_EXT, WS)                                                                   \
-    extern template __global__ void psy::tdt_encode_lscan_sizes_kernel<WS>(psy::EncodeArgs, const uint32_t *, uint32_t);
+    extern template __global__ void psy::tdt_encode_lscan_sizes_kernel<WS>(psy::EncodeArgs, const uint32_t *, uint32_t); \
+    PSY_ENC_MAPPED_INSTANCES(PSY_ENC_MAPPED_EXT, WS)
+// (the known-mapping scattered encode, MODE_MAPPED with PAIR: tdt_enc_mapped_ws.hip)
+#define PSY_ENC_MAPPED_EXT(WS, T, G, TL, PS, PA) \
+    extern template __global__ void psy::tdt_encode_kernel<WS, T, G, psy::MODE_MAPPED, 0, TL, PS, PA, true>(psy::EncodeArgs);
 // (the size pass, MODE_SIZES: tdt_enc_sizes_ws.hip)
 #define PSY_ENC_SIZES_EXT(WS, T, G, TL, PS, PA) \
     extern template __global__ void psy::tdt_encode_kernel<WS, T, G, psy::MODE_SIZES, 0, TL, PS, PA, true>(psy::EncodeArgs);
@@ -275,8 +280,10 @@ struct tdt_ctx {
     // captured, so from its first capture on a buffer replaced by a larger one is retired, not freed
     bool cp_in_graph = false;
     // TDT_OPT_PACK_SIZES_FIRST: tdt_encode_batch_vp sizes the blobs first (the size pass), scans, and
-    // encodes straight into the caller's buffer — cp_buf is not used, cp_idx holds addresses (n) | capacities (n)
-    bool pack_sizes_first = false;
+    // encodes straight into the caller's buffer — cp_buf is not used, cp_idx holds addresses (n) | capacities (n).
+    // 2: the size pass also exports every message's mapping bits (cp_idx: n more u64) and the second
+    // pass runs as the known-mapping encode with them — no histogram, no entropies, no decision again
+    int pack_sizes_first = 0;
     // the pack kernel's knobs (PSYNE_TDT_PACK_CUT, PSYNE_TDT_PACK_GRID: tools/pack_bench.py)
     uint32_t pack_cut = psy::kPackCut, pack_grid = psy::kPackGridCap;
     uint64_t large_min = 256 * 1024;  // messages (decode: decoded blobs) above this take the tiled path
@@ -718,11 +725,17 @@ struct Routed {
 // list is sized by its own kernel, and the batch has no outputs: a scattered one's out_ptr / out_cap
 // are any readable arrays of n entries (the table kernel reads them, nothing reads what it writes
 // from them), a contiguous one (`g`) gets its input table from its offsets.
+// MODE_MAPPED (PAIR only): the known-mapping encode (a.mapping_in: one u64 of mapping bits per
+// message) — the same plan, lists, grids, side stream and count history through the mapped
+// instances of every whole-message class.  In the tile pipeline two small kernels (tdt_enc_lmap.h)
+// stand in for the span and map passes, which have nothing to compute; the count pass, the scan and
+// the emit pass are the ordinary encode's own instances (they read the mapping from LMeta).
 template <int WS, bool PAIR = false, int MODE = psy::MODE_ENCODE>
 int launch_slotted(tdt_ctx *c, PlanWS &pw, psy::EncodeArgs a, hipStream_t s, const Scatter *v = nullptr,
                    const Routed *r = nullptr, const Contig *g = nullptr) {
-    static_assert(MODE == psy::MODE_ENCODE || (MODE == psy::MODE_SIZES && PAIR), "slotted encode, or its size pass");
-    constexpr bool SIZES = MODE == psy::MODE_SIZES;
+    static_assert(MODE == psy::MODE_ENCODE || ((MODE == psy::MODE_SIZES || MODE == psy::MODE_MAPPED) && PAIR),
+                  "slotted encode, its size pass, or its known-mapping form");
+    constexpr bool SIZES = MODE == psy::MODE_SIZES, MAPPED = MODE == psy::MODE_MAPPED;
     using namespace psy;  // (counter, list and kernel names)
     const uint32_t n = a.n_msgs;
     // the list-entry prefetch of the slotted kernels (EncodeArgs::list) reads entry
@@ -808,13 +821,23 @@ int launch_slotted(tdt_ctx *c, PlanWS &pw, psy::EncodeArgs a, hipStream_t s, con
         a.rcount = cnt64 + EC_RECOUNT;
         a.lcap = lcap;
         a.tcap = tcap;
+        // (a known-mapping batch counts and emits with the ordinary encode's tile instances)
+        constexpr int TMODE = MAPPED ? (int)MODE_ENCODE : MODE;
         auto tile_pass = [&](auto TL, EncCount k, uint32_t bound) {  // (no main launch before any count is known)
             cls(nullptr, k, guess(H, k, bound, 0), bound, 512, ovf512, ts,
-                tdt_encode_kernel<WS, 512, 8, MODE, 0, TL(), 0, PATH_BOTH, PAIR>,
-                tdt_encode_kernel<WS, 512, 8, MODE, 0, TL(), 1, PATH_BOTH, PAIR>);
+                tdt_encode_kernel<WS, 512, 8, TMODE, 0, TL(), 0, PATH_BOTH, PAIR>,
+                tdt_encode_kernel<WS, 512, 8, TMODE, 0, TL(), 1, PATH_BOTH, PAIR>);
         };
-        tile_pass(Int<1>{}, EC_SPANS, scap);  // span histograms (and counts under the speculated mapping)
-        tile_pass(Int<4>{}, EC_LARGE, lcap);  // mapping per large message; lists the tiles to count again
+        if constexpr (MAPPED) {
+            // the caller's mappings into the records, every tile on the count list; large passthrough copies
+            hipLaunchKernelGGL(tdt_encode_lcopy_kernel, dim3(std::max(1u, std::min(scap, ovf512))), dim3(512), 0, ts, a,
+                               (uint32_t)WS);
+            hipLaunchKernelGGL(tdt_encode_lmap_kernel, dim3(std::max(1u, std::min(lcap, 1024u))), dim3(64), 0, ts, a,
+                               (uint32_t)WS);
+        } else {
+            tile_pass(Int<1>{}, EC_SPANS, scap);  // span histograms (and counts under the speculated mapping)
+            tile_pass(Int<4>{}, EC_LARGE, lcap);  // mapping per large message; lists the tiles to count again
+        }
         if (!capturing && (st = record_counts(H, cnt, n, ts))) return st;
         tile_pass(Int<2>{}, EC_RECOUNT, tcap);  // per-tile counts of the listed tiles
         if constexpr (SIZES) {  // the scan alone: it has the pair counts, and there is nothing to emit
@@ -863,10 +886,15 @@ int launch_slotted(tdt_ctx *c, PlanWS &pw, psy::EncodeArgs a, hipStream_t s, con
     return TDT_OK;
 }
 
-int launch_slotted_any(tdt_ctx *c, PlanWS &pw, psy::EncodeArgs a, hipStream_t s, const Scatter *v = nullptr) {
+// mapped: the known-mapping form of a scattered batch (a.mapping_in: mapping bits, tdt_mapbits.h)
+int launch_slotted_any(tdt_ctx *c, PlanWS &pw, psy::EncodeArgs a, hipStream_t s, const Scatter *v = nullptr,
+                       bool mapped = false) {
     int st = TDT_OK;
+    if (mapped && !v) return set_err(TDT_E_ARG, "the known-mapping slotted encode is a scattered call");
     if (with_word_size(c->cfg.word_size, [&](auto W) {
-            st = v ? launch_slotted<W(), true>(c, pw, a, s, v) : launch_slotted<W()>(c, pw, a, s);
+            st = mapped ? launch_slotted<W(), true, psy::MODE_MAPPED>(c, pw, a, s, v)
+                 : v    ? launch_slotted<W(), true>(c, pw, a, s, v)
+                        : launch_slotted<W()>(c, pw, a, s);
         }))
         return st;
     // generic widths: one workgroup per message, message id = block index, no plan
@@ -874,7 +902,7 @@ int launch_slotted_any(tdt_ctx *c, PlanWS &pw, psy::EncodeArgs a, hipStream_t s,
         if ((st = ensure_plan(pw, a.n_msgs, s, true))) return st;
         if ((st = launch_table(pw, *v, a.n_msgs, true, nullptr, a.in_off, a.slot_off, s))) return st;
     }
-    return launch_any_encode(a, c->cfg.word_size, psy::MODE_ENCODE, s, v != nullptr);
+    return launch_any_encode(a, c->cfg.word_size, mapped ? psy::MODE_MAPPED : psy::MODE_ENCODE, s, v != nullptr);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -979,13 +1007,17 @@ int tuned_index(int ws) { return ws == 1 ? 0 : ws == 2 ? 1 : ws == 4 ? 2 : ws ==
 int prep(tdt_ctx *c, uint32_t n_msgs, hipStream_t s, uint8_t *&wsp, bool lookback);  // (below)
 
 // mode: MODE_ENCODE, or MODE_SIZES — the size pass of every width over the same routes and plan
-// workspaces (v.out_ptr / v.out_cap: any readable arrays of n entries, see launch_slotted)
+// workspaces (v.out_ptr / v.out_cap: any readable arrays of n entries, see launch_slotted), which
+// also writes the mapping bits of every compressed message to d_mapbits when that is set — or
+// MODE_MAPPED, the known-mapping encode of every width, which reads d_mapbits (n u64, tdt_mapbits.h)
 int encode_mixed(tdt_ctx *c, const Scatter &v, const int32_t *d_word_size, uint64_t width_mask, uint32_t n,
-                 uint64_t *d_out_len, int32_t *d_status, hipStream_t s, int mode = psy::MODE_ENCODE) {
+                 uint64_t *d_out_len, int32_t *d_status, hipStream_t s, int mode = psy::MODE_ENCODE,
+                 uint64_t *d_mapbits = nullptr) {
     if (!c) return set_err(TDT_E_ARG, "null context");
     if (n == 0) return TDT_OK;
     if (!(v.ptr && v.size && v.out_ptr && v.out_cap && d_word_size))
         return set_err(TDT_E_ARG, "null pointer, size or word-size array");
+    if (mode == psy::MODE_MAPPED && !d_mapbits) return set_err(TDT_E_ARG, "null mapping");
     psy::MixedRoutes R{};
     if (!psy::mixed_routes(width_mask, n, R))
         return set_err(TDT_E_ARG, "width_mask must name between 1 and 8 word sizes");
@@ -1028,6 +1060,8 @@ int encode_mixed(tdt_ctx *c, const Scatter &v, const int32_t *d_word_size, uint6
     a.n_msgs = n;
     a.status = d_status;
     a.out_len = d_out_len;
+    if (mode == psy::MODE_MAPPED) a.mapping_in = reinterpret_cast<const int32_t *>(d_mapbits);
+    if (mode == psy::MODE_SIZES) a.map_out = reinterpret_cast<int32_t *>(d_mapbits);
     wire_encode(c, a, wsp);
     // one width after another on the caller's stream, each tuned one forking its own side stream
     for (int k = 0; k < R.n_routes; ++k) {
@@ -1036,8 +1070,9 @@ int encode_mixed(tdt_ctx *c, const Scatter &v, const int32_t *d_word_size, uint6
         if (q.tuned) {
             PlanWS &pw = *c->mx_pw[tuned_index(q.ws)];
             with_word_size(q.ws, [&](auto W) {
-                st = mode == psy::MODE_SIZES ? launch_slotted<W(), true, psy::MODE_SIZES>(c, pw, a, s, nullptr, &r)
-                                             : launch_slotted<W(), true>(c, pw, a, s, nullptr, &r);
+                st = mode == psy::MODE_SIZES    ? launch_slotted<W(), true, psy::MODE_SIZES>(c, pw, a, s, nullptr, &r)
+                     : mode == psy::MODE_MAPPED ? launch_slotted<W(), true, psy::MODE_MAPPED>(c, pw, a, s, nullptr, &r)
+                                                : launch_slotted<W(), true>(c, pw, a, s, nullptr, &r);
             });
         } else {
             psy::EncodeArgs g = a;
@@ -1137,7 +1172,8 @@ int encode_common(tdt_ctx *c, int mode, psy::EncodeArgs a, const Where &w) {
         st = slotted ? launch_slotted_any(c, w.pws ? *w.pws : c->pw, a, s, v)
                      : launch_encode<psy::MODE_ENCODE, 1>(c, a, s, w.small_teams);
     } else if (mode == psy::MODE_MAPPED) {
-        st = launch_encode<psy::MODE_MAPPED, 1>(c, a, s, w.small_teams);
+        st = v ? launch_slotted_any(c, w.pws ? *w.pws : c->pw, a, s, v, true)
+               : launch_encode<psy::MODE_MAPPED, 1>(c, a, s, w.small_teams);
     } else {
         st = launch_encode<psy::MODE_ANALYZE, 1>(c, a, s, w.small_teams);
     }
@@ -1151,8 +1187,9 @@ int encode_common(tdt_ctx *c, int mode, psy::EncodeArgs a, const Where &w) {
 // size; there are no outputs, and out_ptr / out_cap name the size array, see launch_slotted) and `g`
 // (contiguous) names the batch.  The plan workspace and count history are the encode's own: both
 // passes plan the same batch into the same lists.
+// d_mapbits (optional, n u64): the mapping bits of every compressed message (tdt_mappings_v).
 int encoded_sizes_one(tdt_ctx *c, const Scatter *v, const Contig *g, uint32_t n, uint64_t *d_enc, int32_t *d_status,
-                      hipStream_t s) {
+                      hipStream_t s, uint64_t *d_mapbits = nullptr) {
     if (!c) return set_err(TDT_E_ARG, "null context");
     if (n == 0) return TDT_OK;
     if (!d_enc || (v && !(v->ptr && v->size)) || (g && !g->off)) return set_err(TDT_E_ARG, "null pointer, size or output array");
@@ -1164,6 +1201,7 @@ int encoded_sizes_one(tdt_ctx *c, const Scatter *v, const Contig *g, uint32_t n,
     a.n_msgs = n;
     a.status = d_status;
     a.out_len = d_enc;
+    a.map_out = reinterpret_cast<int32_t *>(d_mapbits);
     wire_encode(c, a, wsp);
     if (!with_word_size(c->cfg.word_size, [&](auto W) {
             st = launch_slotted<W(), true, psy::MODE_SIZES>(c, c->pw, a, s, v, nullptr, g);
@@ -2385,7 +2423,7 @@ int tdt_ctx_set_option(tdt_ctx *ctx, int option, uint64_t value) {
         case TDT_OPT_NO_SIDE_STREAM: ctx->no_side = value != 0; return TDT_OK;
         case TDT_OPT_SMALL_ON_CALLER_STREAM: ctx->small_main = value != 0; return TDT_OK;
         case TDT_OPT_NO_TWO_PHASE: ctx->no_two_phase = value != 0; return TDT_OK;
-        case TDT_OPT_PACK_SIZES_FIRST: ctx->pack_sizes_first = value != 0; return TDT_OK;
+        case TDT_OPT_PACK_SIZES_FIRST: ctx->pack_sizes_first = value == 2 ? 2 : value != 0 ? 1 : 0; return TDT_OK;
     }
     return set_err(TDT_E_ARG, "unknown option");
 }
@@ -2615,11 +2653,25 @@ int tdt_pack_v(tdt_ctx *ctx, const uint8_t *const *d_blobs, const uint64_t *d_bl
                        d_status, false, (hipStream_t)stream);
 }
 
-int tdt_encode_batch_vp(tdt_ctx *ctx, const uint8_t *const *d_msgs, const uint64_t *d_sizes, const int32_t *d_word_size,
-                        uint64_t width_mask, uint32_t n_msgs, uint64_t total_bytes, uint8_t *d_out, uint64_t out_cap,
-                        uint64_t *d_out_off, int32_t *d_status, void *stream) {
-    if (!ctx) return set_err(TDT_E_ARG, "null context");
-    if (n_msgs == 0) return TDT_OK;
+// A scattered known-mapping encode: `v` and the caller's mapping bits (n u64)
+static int encode_scattered_mapped(tdt_ctx *ctx, const Scatter &v, uint32_t n_msgs, const uint64_t *d_mapbits,
+                                   uint64_t *d_out_len, int32_t *d_status, void *stream) {
+    psy::EncodeArgs a{};
+    a.n_msgs = n_msgs;
+    a.status = d_status;
+    a.out_len = d_out_len;
+    a.mapping_in = reinterpret_cast<const int32_t *>(d_mapbits);
+    Where w(stream);
+    w.v = &v;
+    return encode_common(ctx, psy::MODE_MAPPED, a, w);
+}
+
+// tdt_encode_batch_vp (d_mapbits null) and tdt_encode_mapped_vp (the caller's mapping bits: always the
+// two phases — the sizes-first form would need the sizes under the caller's mapping, a size pass
+// that takes the mapping instead of deciding it, which the mode parameters do not hold)
+static int encode_packed(tdt_ctx *ctx, const uint8_t *const *d_msgs, const uint64_t *d_sizes, const int32_t *d_word_size,
+                         uint64_t width_mask, uint32_t n_msgs, uint64_t total_bytes, const uint64_t *d_mapbits,
+                         uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_off, int32_t *d_status, void *stream) {
     if (!d_msgs || !d_sizes || !d_out_off) return set_err(TDT_E_ARG, "null pointer, size or offset array");
     if (!d_out && out_cap) return set_err(TDT_E_ARG, "null output");
     uint64_t wmax = (uint64_t)ctx->cfg.word_size;
@@ -2632,11 +2684,13 @@ int tdt_encode_batch_vp(tdt_ctx *ctx, const uint8_t *const *d_msgs, const uint64
     if (total_bytes > (1ull << 62)) return set_err(TDT_E_ARG, "total_bytes too large");
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(hipSetDevice(ctx->device));
-    uint64_t *sf_idx = nullptr;  // sizes first: blob addresses (n) | capacities (n)
+    uint64_t *sf_idx = nullptr;  // sizes first: blob addresses (n) | capacities (n) | option value 2: mapping bits (n)
+    bool sf_map = false;
     {
         std::lock_guard<std::mutex> lk(ctx->mu);
-        if (ctx->pack_sizes_first) {
-            if (int st = ensure_cp(ctx, 2ull * n_msgs, 0, s, true)) return st;
+        if (ctx->pack_sizes_first && !d_mapbits) {
+            sf_map = ctx->pack_sizes_first == 2;
+            if (int st = ensure_cp(ctx, (sf_map ? 3ull : 2ull) * n_msgs, 0, s, true)) return st;
             sf_idx = ctx->cp_idx;
         }
     }
@@ -2645,15 +2699,22 @@ int tdt_encode_batch_vp(tdt_ctx *ctx, const uint8_t *const *d_msgs, const uint64
         // offsets, each blob's slot [off[i], off[i+1]) of d_out — capacity 0 where it would end past
         // out_cap — and the scattered / mixed encode straight into those slots.  No scratch: total_bytes
         // plays no part, cp_buf is not touched.
-        uint64_t *ptr = sf_idx, *cap = sf_idx + n_msgs;
+        // Option value 2: the size pass leaves every message's mapping bits behind the two tables (0 for
+        // a passthrough or rejected message: the words are zeroed first), and the second pass is the
+        // known-mapping encode with them — the same bytes, the analysis run once.
+        uint64_t *ptr = sf_idx, *cap = sf_idx + n_msgs, *bits = sf_map ? sf_idx + 2ull * n_msgs : nullptr;
         const uint64_t *msgs = reinterpret_cast<const uint64_t *>(d_msgs);
         const Scatter vs{msgs, d_sizes, d_sizes, d_sizes};  // (the size pass has no outputs: launch_slotted)
-        int st = d_word_size ? encode_mixed(ctx, vs, d_word_size, width_mask, n_msgs, d_out_off, d_status, s, psy::MODE_SIZES)
-                             : encoded_sizes_one(ctx, &vs, nullptr, n_msgs, d_out_off, d_status, s);
+        if (bits) HIPCHK(hipMemsetAsync(bits, 0, 8ull * n_msgs, s));
+        int st = d_word_size ? encode_mixed(ctx, vs, d_word_size, width_mask, n_msgs, d_out_off, d_status, s, psy::MODE_SIZES, bits)
+                             : encoded_sizes_one(ctx, &vs, nullptr, n_msgs, d_out_off, d_status, s, bits);
         if (st) return st;
         if ((st = scan_sizes(ctx, d_out_off, n_msgs, s))) return st;
         HIPCHK((hipError_t)psy::launch_pack_exact_slots(d_out_off, d_out, out_cap, ptr, cap, n_msgs, s));
         const Scatter v{msgs, d_sizes, ptr, cap};
+        if (bits)
+            return d_word_size ? encode_mixed(ctx, v, d_word_size, width_mask, n_msgs, nullptr, d_status, s, psy::MODE_MAPPED, bits)
+                               : encode_scattered_mapped(ctx, v, n_msgs, bits, nullptr, d_status, stream);
         return d_word_size ? encode_mixed(ctx, v, d_word_size, width_mask, n_msgs, nullptr, d_status, s)
                            : encode_scattered(ctx, v, n_msgs, nullptr, d_status, stream);
     }
@@ -2674,10 +2735,69 @@ int tdt_encode_batch_vp(tdt_ctx *ctx, const uint8_t *const *d_msgs, const uint64
     // TDT_E_CAPACITY for that message, never a write outside the scratch)
     HIPCHK((hipError_t)psy::launch_pack_slots(slot, buf, buf_bytes, ptr, cap, n_msgs, s));
     const Scatter v{reinterpret_cast<const uint64_t *>(d_msgs), d_sizes, ptr, cap};
-    const int st = d_word_size ? encode_mixed(ctx, v, d_word_size, width_mask, n_msgs, len, d_status, s)
-                               : encode_scattered(ctx, v, n_msgs, len, d_status, stream);
+    int st;
+    if (d_mapbits)
+        st = d_word_size ? encode_mixed(ctx, v, d_word_size, width_mask, n_msgs, len, d_status, s, psy::MODE_MAPPED,
+                                        const_cast<uint64_t *>(d_mapbits))
+                         : encode_scattered_mapped(ctx, v, n_msgs, d_mapbits, len, d_status, stream);
+    else
+        st = d_word_size ? encode_mixed(ctx, v, d_word_size, width_mask, n_msgs, len, d_status, s)
+                         : encode_scattered(ctx, v, n_msgs, len, d_status, stream);
     if (st) return st;
     return pack_common(ctx, ptr, len, n_msgs, d_out, out_cap, d_out_off, d_status, true, s);
+}
+
+int tdt_encode_batch_vp(tdt_ctx *ctx, const uint8_t *const *d_msgs, const uint64_t *d_sizes, const int32_t *d_word_size,
+                        uint64_t width_mask, uint32_t n_msgs, uint64_t total_bytes, uint8_t *d_out, uint64_t out_cap,
+                        uint64_t *d_out_off, int32_t *d_status, void *stream) {
+    if (!ctx) return set_err(TDT_E_ARG, "null context");
+    if (n_msgs == 0) return TDT_OK;
+    return encode_packed(ctx, d_msgs, d_sizes, d_word_size, width_mask, n_msgs, total_bytes, nullptr, d_out, out_cap,
+                         d_out_off, d_status, stream);
+}
+
+int tdt_encode_mapped_vp(tdt_ctx *ctx, const uint8_t *const *d_msgs, const uint64_t *d_sizes, const int32_t *d_word_size,
+                         uint64_t width_mask, uint32_t n_msgs, uint64_t total_bytes, const uint64_t *d_mapbits,
+                         uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_off, int32_t *d_status, void *stream) {
+    if (!ctx) return set_err(TDT_E_ARG, "null context");
+    if (n_msgs == 0) return TDT_OK;
+    if (!d_mapbits) return set_err(TDT_E_ARG, "null mapping");
+    return encode_packed(ctx, d_msgs, d_sizes, d_word_size, width_mask, n_msgs, total_bytes, d_mapbits, d_out, out_cap,
+                         d_out_off, d_status, stream);
+}
+
+int tdt_encode_mapped_v(tdt_ctx *ctx, const uint8_t *const *d_msgs, const uint64_t *d_sizes, const int32_t *d_word_size,
+                        uint64_t width_mask, uint32_t n_msgs, const uint64_t *d_mapbits, uint8_t *const *d_blobs,
+                        const uint64_t *d_blob_cap, uint64_t *d_out_len, int32_t *d_status, void *stream) {
+    if (!ctx) return set_err(TDT_E_ARG, "null context");
+    if (n_msgs == 0) return TDT_OK;
+    if (!d_mapbits) return set_err(TDT_E_ARG, "null mapping");
+    const Scatter v = scatter_of(d_msgs, d_sizes, d_blobs, d_blob_cap);
+    if (!d_word_size) return encode_scattered_mapped(ctx, v, n_msgs, d_mapbits, d_out_len, d_status, stream);
+    return encode_mixed(ctx, v, d_word_size, width_mask, n_msgs, d_out_len, d_status, (hipStream_t)stream, psy::MODE_MAPPED,
+                        const_cast<uint64_t *>(d_mapbits));
+}
+
+int tdt_mappings_v(tdt_ctx *ctx, const uint8_t *const *d_msgs, const uint64_t *d_sizes, const int32_t *d_word_size,
+                   uint64_t width_mask, uint32_t n_msgs, uint64_t *d_enc_sizes, uint64_t *d_mapbits, int32_t *d_status,
+                   void *stream) {
+    if (!ctx) return set_err(TDT_E_ARG, "null context");
+    if (n_msgs == 0) return TDT_OK;
+    if (!d_enc_sizes || !d_mapbits) return set_err(TDT_E_ARG, "null output array");
+    if (d_word_size) {  // (the call-level mask errors before anything is written)
+        psy::MixedRoutes R{};
+        if (!psy::mixed_routes(width_mask, n_msgs, R))
+            return set_err(TDT_E_ARG, "width_mask must name between 1 and 8 word sizes");
+    }
+    if (!d_msgs || !d_sizes) return set_err(TDT_E_ARG, "null pointer, size or output array");
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(hipSetDevice(ctx->device));
+    // the size pass stores the bits of the messages it compresses; every other one (UNCP, a rejected width) keeps 0
+    HIPCHK(hipMemsetAsync(d_mapbits, 0, 8ull * n_msgs, s));
+    const uint64_t *msgs = reinterpret_cast<const uint64_t *>(d_msgs);
+    const Scatter v{msgs, d_sizes, d_sizes, d_sizes};  // (the size pass has no outputs: launch_slotted)
+    if (!d_word_size) return encoded_sizes_one(ctx, &v, nullptr, n_msgs, d_enc_sizes, d_status, s, d_mapbits);
+    return encode_mixed(ctx, v, d_word_size, width_mask, n_msgs, d_enc_sizes, d_status, s, psy::MODE_SIZES, d_mapbits);
 }
 
 int tdt_encoded_sizes_batch(tdt_ctx *ctx, const uint8_t *d_in, const uint64_t *d_in_off, uint32_t n_msgs,

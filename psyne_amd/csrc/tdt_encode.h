@@ -40,6 +40,7 @@
 #pragma once
 #include "tdt_device.h"
 #include "tdt_log2.h"
+#include "tdt_mapbits.h"
 #include "tdt_plan.h"
 
 #include <type_traits>
@@ -95,10 +96,10 @@ struct EncodeArgs {
     uint64_t out_cap;
     uint64_t *out_off;
     int32_t *status;
-    const int32_t *mapping_in;  // MODE_MAPPED
+    const int32_t *mapping_in;  // MODE_MAPPED (PAIR instances: one u64 of mapping bits per message, tdt_mapbits.h)
     uint32_t *hist_out;         // MODE_ANALYZE
     double *ent_out;
-    int32_t *map_out;
+    int32_t *map_out;           // (MODE_SIZES, when set: one u64 of mapping bits per compressed message)
     uint64_t *lookback;
     uint32_t *ticket;
     uint32_t *errflags;  // bit0 look-back timeout, bit2 flush bound, bit3 a resident-only kernel got a streaming message
@@ -724,7 +725,16 @@ __device__ __forceinline__ void encode_one(const EncodeArgs &a, uint8_t *smem, u
     // ------------------------------------------------------------ mapping (analysis)
     if constexpr (MODE == MODE_MAPPED || TL == 2 || TL == 3) {
         uint32_t bad = 0, mbit = 0;
-        if (lane < WS) {
+        if constexpr (MODE == MODE_MAPPED && PAIR) {
+            // scattered batches: the message's mapping bits, one u64 (a uniform load); a bit at or
+            // above the width is a bad mapping
+            const uint64_t bits = reinterpret_cast<const uint64_t *>(a.mapping_in)[msg];
+            bad = mapbits_ok(bits, WS) ? 0u : 1u;
+            if (lane < WS) {
+                mbit = mapbits_at(bits, lane);
+                wm[M_MAP + lane] = mbit;
+            }
+        } else if (lane < WS) {
             int32_t m;
             if constexpr (TL == 2 || TL == 3) m = (int32_t)((a.lmeta[lj].mapbits >> lane) & 1u);
             else m = a.mapping_in[(uint64_t)msg * WS + lane];
@@ -1619,6 +1629,7 @@ __device__ __forceinline__ void encode_one(const EncodeArgs &a, uint8_t *smem, u
                 if (tid == 0) {
                     if (a.status) a.status[msg] = ST_OK;
                     if (a.out_len) a.out_len[msg] = E;
+                    if (a.map_out) reinterpret_cast<uint64_t *>(a.map_out)[msg] = mapbits;  // (tdt_mappings_v)
                 }
                 return;
             }
@@ -2200,7 +2211,9 @@ __device__ __forceinline__ uint32_t entry_count(const EncodeArgs &a) {
 
 template <int WS, int TEAM, int G, int MODE, int LB, int TL = 0, int PS = 0, int PATH = PATH_BOTH, bool PAIR = false>
 __global__ __launch_bounds__(TEAM, PSY_ENC_WAVES(TEAM, LB)) void tdt_encode_kernel(EncodeArgs a) {
-    static_assert(!PAIR || (!LB && (MODE == MODE_ENCODE || MODE == MODE_SIZES)), "scattered batches are slotted encodes");
+    static_assert(!PAIR || (!LB && (MODE == MODE_ENCODE || MODE == MODE_SIZES || MODE == MODE_MAPPED)),
+                  "scattered batches are slotted encodes");
+    static_assert(MODE != MODE_MAPPED || LB || (PAIR && TL == 0), "slotted known-mapping encodes are scattered, whole messages");
     static_assert(MODE != MODE_SIZES || (PAIR && TL != 3), "the size pass reads pair tables and never emits");
     using Lay = EncLayout<WS, TEAM, LB>;
     constexpr int W = Lay::W;
@@ -2446,6 +2459,7 @@ __device__ __forceinline__ void encode_lscan(const EncodeArgs &a, const uint32_t
             if (lane == 0) {
                 if (a.status) a.status[msg] = ST_OK;
                 if (a.out_len) a.out_len[msg] = E;
+                if (a.map_out) reinterpret_cast<uint64_t *>(a.map_out)[msg] = mapbits & ((1u << WS) - 1u);
             }
             continue;
         }
@@ -2514,5 +2528,15 @@ __global__ __launch_bounds__(64) void tdt_encode_lscan_sizes_kernel(EncodeArgs a
     X(WS, 512, 8, 0, 0, 1) X(WS, 512, 8, 0, 1, 1) X(WS, 512, 8, 0, 0, 2) X(WS, 512, 8, 0, 1, 2) X(WS, 512, 8, 1, 0, 0) \
     X(WS, 512, 8, 2, 0, 0) X(WS, 512, 8, 4, 0, 0) X(WS, 64, 4, 0, 0, 0) X(WS, 512, 8, 1, 1, 0) X(WS, 512, 8, 2, 1, 0)  \
     X(WS, 512, 8, 4, 1, 0) X(WS, 64, 4, 0, 1, 0) X(WS, 256, 8, 0, 0, 0) X(WS, 256, 8, 0, 1, 0)
+
+// The known-mapping encode of the scattered batches (MODE_MAPPED, PAIR: tdt_encode_mapped_v / _vp):
+// every whole-message class — resident and streaming 512-lane teams, one-wave and 256-lane teams —
+// each with its overflow instance.  tdt_enc_mapped_ws.hip instantiates them, one translation unit
+// per word size.  (There are no mapped tile instances: tdt_enc_lmap.h writes the caller's mappings
+// into the large-message records, and the count, scan and emit passes are the ordinary encode's,
+// DESIGN.md §4 "Known mappings".)
+#define PSY_ENC_MAPPED_INSTANCES(X, WS)                                                                           \
+    X(WS, 512, 8, 0, 0, 1) X(WS, 512, 8, 0, 1, 1) X(WS, 512, 8, 0, 0, 2) X(WS, 512, 8, 0, 1, 2) X(WS, 64, 4, 0, 0, 0) \
+    X(WS, 64, 4, 0, 1, 0) X(WS, 256, 8, 0, 0, 0) X(WS, 256, 8, 0, 1, 0)
 
 }  // namespace psy

@@ -73,6 +73,31 @@ def encode_bound(n: int, word_size: int = 4) -> int:
     return int(_lib.load().tdt_encode_bound(n, word_size))
 
 
+def mapbits_of(mapping) -> int:
+    """The mapping bits (one word per message: mappings_v, the mapbits= arguments) of a mapping given
+    as one stream number in {0, 1} per byte position: bit p = mapping[p]."""
+    mapping = [int(m) for m in mapping]
+    if not 1 <= len(mapping) <= 64:
+        raise ValueError("a mapping holds 1..64 positions")
+    bits = 0
+    for p, m in enumerate(mapping):
+        if m not in (0, 1):
+            raise ValueError("mapping[%d] = %d is neither 0 nor 1" % (p, m))
+        bits |= m << p
+    return bits
+
+
+def mapping_of(bits: int, ws: int) -> list[int]:
+    """The mapping (one stream number per byte position, as blobs carry it at bytes 20 ..) of mapping
+    bits at word size ws; a bit at or above ws is TDT_E_BAD_MAPPING's case and raises here."""
+    bits = int(bits) & 0xFFFFFFFFFFFFFFFF  # (an int64 tensor's entry with bit 63 set reads negative)
+    if not 1 <= ws <= 64:
+        raise ValueError("word size %d is outside 1..64" % ws)
+    if bits >> ws:
+        raise ValueError("mapping bits 0x%x have a bit at or above word size %d" % (bits, ws))
+    return [(bits >> p) & 1 for p in range(ws)]
+
+
 def _ptr(t) -> int:
     return 0 if t is None else int(t.data_ptr())
 
@@ -238,15 +263,29 @@ class TdtCodec:
         return sizes[:n], status[:n]
 
     # ---- scattered batches (one buffer per message: tensors of a training process) ------
-    def encode_v(self, ptrs, sizes, out_ptrs, out_caps, lengths=None, status=None, stream=None):
+    @staticmethod
+    def _check_mapbits(mapbits, n):
+        import torch
+        if mapbits.dtype != torch.int64 or mapbits.numel() < n:
+            raise ValueError("mapbits must be an int64 tensor of one word per message")
+
+    def encode_v(self, ptrs, sizes, out_ptrs, out_caps, lengths=None, status=None, stream=None, mapbits=None):
         """Encode message i = sizes[i] bytes at address ptrs[i] into out_caps[i] bytes at address
-        out_ptrs[i] (int64 tensors on the GPU); returns (lengths, status)."""
+        out_ptrs[i] (int64 tensors on the GPU); returns (lengths, status).  mapbits (an int64 tensor on
+        the GPU, one word per message: mappings_v's, or mapbits_of) encodes with those mappings instead
+        of analysing the messages; a word with a bit at or above the word size gives status 4."""
         import torch
         n = sizes.numel()
         if lengths is None:
             lengths = torch.empty(max(n, 1), dtype=torch.int64, device=sizes.device)
         if status is None:
             status = torch.empty(max(n, 1), dtype=torch.int32, device=sizes.device)
+        if mapbits is not None:
+            self._check_mapbits(mapbits, n)
+            check(self._lib.tdt_encode_mapped_v(self._h, _ptr(ptrs), _ptr(sizes), None, 0, n, _ptr(mapbits),
+                                                _ptr(out_ptrs), _ptr(out_caps), _ptr(lengths), _ptr(status),
+                                                self._stream(stream)))
+            return lengths, status
         check(self._lib.tdt_encode_batch_v(self._h, _ptr(ptrs), _ptr(sizes), n, _ptr(out_ptrs), _ptr(out_caps),
                                            _ptr(lengths), _ptr(status), self._stream(stream)))
         return lengths, status
@@ -262,11 +301,11 @@ class TdtCodec:
         return mask
 
     def encode_vw(self, ptrs, sizes, word_sizes, width_mask, out_ptrs, out_caps, lengths=None, status=None,
-                  stream=None):
+                  stream=None, mapbits=None):
         """encode_v with one record width per message: word_sizes[i] (int32 tensor on the GPU) is
         message i's, whatever this codec's own word_size; width_mask (a host int, bit w - 1 per width
         that may occur, at most 8 of them) tells the host which pipelines to launch.  Blob i is what
-        a codec of word_size word_sizes[i] gives; returns (lengths, status)."""
+        a codec of word_size word_sizes[i] gives; returns (lengths, status).  mapbits: as for encode_v."""
         import torch
         n = sizes.numel()
         if n and word_sizes.dtype != torch.int32:
@@ -275,6 +314,12 @@ class TdtCodec:
             lengths = torch.empty(max(n, 1), dtype=torch.int64, device=sizes.device)
         if status is None:
             status = torch.empty(max(n, 1), dtype=torch.int32, device=sizes.device)
+        if mapbits is not None:
+            self._check_mapbits(mapbits, n)
+            check(self._lib.tdt_encode_mapped_v(self._h, _ptr(ptrs), _ptr(sizes), _ptr(word_sizes), int(width_mask), n,
+                                                _ptr(mapbits), _ptr(out_ptrs), _ptr(out_caps), _ptr(lengths),
+                                                _ptr(status), self._stream(stream)))
+            return lengths, status
         check(self._lib.tdt_encode_batch_vw(self._h, _ptr(ptrs), _ptr(sizes), _ptr(word_sizes), int(width_mask), n,
                                             _ptr(out_ptrs), _ptr(out_caps), _ptr(lengths), _ptr(status),
                                             self._stream(stream)))
@@ -335,6 +380,26 @@ class TdtCodec:
                                             _ptr(enc), _ptr(status), self._stream(stream)))
         return enc[:n], status[:n]
 
+    def mappings_v(self, ptrs, sizes, word_sizes=None, width_mask=0, stream=None, enc_sizes=None, mapbits=None,
+                   status=None):
+        """encoded_sizes_v plus the mapping the encode decides for every message: (enc_sizes, mapbits,
+        status), mapbits an int64 tensor of one word per message (bit p = the stream of byte position
+        p; 0 for a message that goes through uncompressed or whose width is rejected).  Passed back as
+        encode_v / encode_vw / encode_vp / encode_tensors(mapbits=...) it gives the bytes of the
+        ordinary encode without the analysis: size and map every K steps, encode mapped between."""
+        import torch
+        n = sizes.numel()
+        if n and word_sizes is not None and word_sizes.dtype != torch.int32:
+            raise ValueError("word_sizes must be an int32 tensor")
+        enc = enc_sizes if enc_sizes is not None else torch.empty(max(n, 1), dtype=torch.int64, device=sizes.device)
+        bits = mapbits if mapbits is not None else torch.empty(max(n, 1), dtype=torch.int64, device=sizes.device)
+        self._check_mapbits(bits, n)
+        if status is None:
+            status = torch.empty(max(n, 1), dtype=torch.int32, device=sizes.device)
+        check(self._lib.tdt_mappings_v(self._h, _ptr(ptrs), _ptr(sizes), _ptr(word_sizes), int(width_mask), n,
+                                       _ptr(enc), _ptr(bits), _ptr(status), self._stream(stream)))
+        return enc[:n], bits[:n], status[:n]
+
     # ---- packed wire buffer (blobs back to back, one copy or send per batch) ----------------
     def pack_v(self, ptrs, lengths, out, out_offsets=None, status=None, stream=None):
         """Pack blob i = lengths[i] bytes at address ptrs[i] (int64 tensors on the GPU: the slots and
@@ -353,12 +418,13 @@ class TdtCodec:
         return out_offsets, status
 
     def encode_vp(self, ptrs, sizes, total_bytes, out, word_sizes=None, width_mask=0, out_offsets=None, status=None,
-                  stream=None):
+                  stream=None, mapbits=None):
         """encode_v (word_sizes None) or encode_vw (word_sizes an int32 tensor on the GPU, width_mask
         as there) into the packed buffer `out`: blob i at out[offsets[i]:offsets[i+1]].  total_bytes
         (a host int) is an upper bound of sizes.sum(): it sizes the codec's scratch, and the host
         reads nothing back.  A blob that ends past out.numel() gets status 5 (TDT_E_CAPACITY);
-        offsets[n] is the full need either way.  Returns (out_offsets, status)."""
+        offsets[n] is the full need either way.  Returns (out_offsets, status).  mapbits: as for
+        encode_v (the mapped packed call always takes the two phases)."""
         import torch
         n = sizes.numel()
         if n and word_sizes is not None and word_sizes.dtype != torch.int32:
@@ -367,6 +433,12 @@ class TdtCodec:
             out_offsets = torch.zeros(n + 1, dtype=torch.int64, device=sizes.device)
         if status is None:
             status = torch.zeros(max(n, 1), dtype=torch.int32, device=sizes.device)
+        if mapbits is not None:
+            self._check_mapbits(mapbits, n)
+            check(self._lib.tdt_encode_mapped_vp(self._h, _ptr(ptrs), _ptr(sizes), _ptr(word_sizes), int(width_mask), n,
+                                                 int(total_bytes), _ptr(mapbits), _ptr(out), out.numel(),
+                                                 _ptr(out_offsets), _ptr(status), self._stream(stream)))
+            return out_offsets, status
         check(self._lib.tdt_encode_batch_vp(self._h, _ptr(ptrs), _ptr(sizes), _ptr(word_sizes), int(width_mask), n,
                                             int(total_bytes), _ptr(out), out.numel(), _ptr(out_offsets), _ptr(status),
                                             self._stream(stream)))
@@ -384,7 +456,8 @@ class TdtCodec:
         ptrs = np.array([t.data_ptr() if s else 0 for t, s in zip(tensors, sizes)], dtype=np.uint64).view(np.int64)
         return ptrs, sizes
 
-    def encode_tensors(self, tensors, out=None, stream=None, word_sizes=None, packed=False, exact=False):
+    def encode_tensors(self, tensors, out=None, stream=None, word_sizes=None, packed=False, exact=False, mapbits=None,
+                       return_mappings=False):
         """Encode a list of contiguous GPU tensors (message i = the bytes of tensors[i]) without
         packing them: blob i goes to out[slots[i]:slots[i+1]], the slots being the prefix sum of the
         encode bounds.  Returns (out, slots, lengths, status).
@@ -414,10 +487,27 @@ class TdtCodec:
         synchronisation of the stream with the host, which the other forms do not have — then `out`
         is allocated with that many bytes (a caller's `out` is ignored) and every blob is encoded
         straight to its offset.  Returns (out, offsets, status) as packed=True does, with
-        out.numel() == offsets[n]."""
+        out.numel() == offsets[n].
+
+        Known mappings: mapbits (an int64 tensor on the GPU, one word per tensor) encodes every tensor
+        with that mapping instead of analysing it; return_mappings=True first decides the mappings
+        (mappings_v), encodes with them, and appends the mapping tensor to the returned tuple — keep
+        it and pass it as mapbits for the following steps:
+            out, slots, lengths, status, bits = codec.encode_tensors(grads, return_mappings=True)
+            out, slots, lengths, status = codec.encode_tensors(grads, mapbits=bits)   # steps 2 .. K
+        (exact=True sizes the blobs under the mappings the codec decides, so with it mapbits must be
+        those of the same bytes, as return_mappings=True makes them: a stale mapping's longer blob
+        gets status 5 there.)"""
         import torch
         ptrs, sizes = self._tensor_table(tensors)
         n = len(tensors)
+        if return_mappings and mapbits is not None:
+            raise ValueError("return_mappings=True decides the mappings itself: pass no mapbits")
+        if return_mappings:
+            res = self._encode_tensors_mapped(tensors, ptrs, sizes, out, stream, word_sizes, packed, exact)
+            return res
+        if mapbits is not None:
+            self._check_mapbits(mapbits, n)
         dev = tensors[0].device if n else torch.device("cuda", self.device)
         if word_sizes is None:
             widths = None
@@ -455,9 +545,9 @@ class TdtCodec:
             if n == 0:
                 return out, offsets, status
             if dw is None:
-                _, status = self.encode_v(d[:n], d[n:2 * n], optrs, caps, stream=stream)
+                _, status = self.encode_v(d[:n], d[n:2 * n], optrs, caps, stream=stream, mapbits=mapbits)
             else:
-                _, status = self.encode_vw(d[:n], d[n:2 * n], dw, mask, optrs, caps, stream=stream)
+                _, status = self.encode_vw(d[:n], d[n:2 * n], dw, mask, optrs, caps, stream=stream, mapbits=mapbits)
             return out, offsets, status[:n]
         slots = np.zeros(n + 1, np.int64)
         np.cumsum(np.maximum(sizes + 4, 28 + 4 * ws + 2 * sizes), out=slots[1:])
@@ -470,7 +560,7 @@ class TdtCodec:
             d = torch.from_numpy(np.concatenate(parts)).to(dev, non_blocking=False)
             dw = d[2 * n:].view(torch.int32)[:n] if widths is not None and n else None
             offsets, status = self.encode_vp(d[:n], d[n:2 * n], int(sizes.sum()), out, word_sizes=dw,
-                                             width_mask=mask if dw is not None else 0, stream=stream)
+                                             width_mask=mask if dw is not None else 0, stream=stream, mapbits=mapbits)
             return out, offsets, status
         if out is None:
             out = torch.empty(max(int(slots[-1]), 1), dtype=torch.uint8, device=dev)
@@ -482,12 +572,39 @@ class TdtCodec:
             parts.append(np.concatenate([widths, np.zeros(n % 2, np.int32)]).view(np.int64))
         d = torch.from_numpy(np.concatenate(parts)).to(dev, non_blocking=False)
         if widths is None or n == 0:
-            lengths, status = self.encode_v(d[:n], d[n:2 * n], d[2 * n:3 * n], d[3 * n:4 * n], stream=stream)
+            lengths, status = self.encode_v(d[:n], d[n:2 * n], d[2 * n:3 * n], d[3 * n:4 * n], stream=stream,
+                                            mapbits=mapbits if n else None)
         else:
             dw = d[5 * n + 1:].view(torch.int32)[:n]
             lengths, status = self.encode_vw(d[:n], d[n:2 * n], dw, mask, d[2 * n:3 * n], d[3 * n:4 * n],
-                                             stream=stream)
+                                             stream=stream, mapbits=mapbits)
         return out, d[4 * n:5 * n + 1], lengths, status
+
+    def _encode_tensors_mapped(self, tensors, ptrs, sizes, out, stream, word_sizes, packed, exact):
+        """encode_tensors(return_mappings=True): the mappings by mappings_v, then the mapped encode."""
+        import torch
+        n = len(tensors)
+        dev = tensors[0].device if n else torch.device("cuda", self.device)
+        dw, mask = None, 0
+        parts = [ptrs, sizes]
+        if word_sizes is not None and n:
+            if isinstance(word_sizes, str):
+                if word_sizes != "dtype":
+                    raise ValueError('word_sizes is None, "dtype" or one width per tensor')
+                widths = np.array([t.element_size() for t in tensors], dtype=np.int32)
+            else:
+                widths = np.array([int(w) for w in word_sizes], dtype=np.int32)
+            if widths.size != n:
+                raise ValueError("%d word sizes for %d tensors" % (widths.size, n))
+            mask = self.width_mask(widths)
+            parts.append(np.concatenate([widths, np.zeros(n % 2, np.int32)]).view(np.int64))
+        d = torch.from_numpy(np.concatenate(parts)).to(dev, non_blocking=False)
+        if len(parts) == 3:
+            dw = d[2 * n:].view(torch.int32)[:n]
+        _, bits, _ = self.mappings_v(d[:n], d[n:2 * n], word_sizes=dw, width_mask=mask, stream=stream)
+        res = self.encode_tensors(tensors, out=out, stream=stream, word_sizes=word_sizes, packed=packed, exact=exact,
+                                  mapbits=bits if n else None)
+        return (*res, bits)
 
     def decode_tensors(self, blobs, offsets, in_lengths, outs, stream=None):
         """Decode blob i = blobs[offsets[i]:offsets[i]+in_lengths[i]] into the preallocated

@@ -1,7 +1,8 @@
 """Per-kernel resource usage of the library (one line per kernel: VGPRs, spills, scratch, occupancy,
 LDS), from hipcc's kernel-resource-usage remarks over the translation units psyne_amd/build.py
-compiles: tdt_api.hip, tdt_anyws.hip (the generic-word-size kernels), tdt_pack.hip, and tdt_enc_ws.hip and
-tdt_enc_sizes_ws.hip once per word size (the tuned encode kernels and their size-pass instances live there).
+compiles: tdt_api.hip, tdt_anyws.hip (the generic-word-size kernels), tdt_pack.hip, and tdt_enc_ws.hip,
+tdt_enc_sizes_ws.hip and tdt_enc_mapped_ws.hip once per word size (the tuned encode kernels, their size-pass
+instances and their known-mapping instances live there).
 Usage: python tools/kres.py [--ws 4[,8...]] [--grep SUBSTRING] [-DFLAG ...]   (device code only)"""
 import concurrent.futures
 import pathlib
@@ -51,6 +52,9 @@ def main(argv):
                 (csrc / "tdt_pack.hip", flags, tmp + "/pack.o")]
         jobs += [(csrc / "tdt_enc_ws.hip", flags + ["-DPSY_INST_WS=%d" % ws], tmp + "/ws%d.o" % ws) for ws in ws_list]
         jobs += [(csrc / "tdt_enc_sizes_ws.hip", flags + ["-DPSY_INST_WS=%d" % ws], tmp + "/sws%d.o" % ws) for ws in ws_list]
+        if (csrc / "tdt_enc_mapped_ws.hip").exists():  # (absent in a parent tree this file is copied into for an A/B)
+            jobs += [(csrc / "tdt_enc_mapped_ws.hip", flags + ["-DPSY_INST_WS=%d" % ws], tmp + "/mws%d.o" % ws)
+                     for ws in ws_list]
         with concurrent.futures.ThreadPoolExecutor(len(jobs)) as ex:
             rows = [r for rs in ex.map(lambda j: remarks(*j), jobs) for r in rs]
     names = subprocess.run(["c++filt"], input="\n".join(r["name"] for r in rows), capture_output=True,
