@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "tdt_anyws.h"
+#include "tdt_copy.h"
 #include "tdt_copypool.h"
 #include "tdt_decode.h"
 #include "tdt_encode.h"
@@ -368,29 +369,10 @@ int launch_encode_t(psy::EncodeArgs a, hipStream_t s) {
 // policy off, or a size that is not a whole number of words) and UNCP blobs (decode :271-304) get
 // a copy list of their own.  Sixteen lanes per entry, 16 entries per 256-lane workgroup,
 // grid-stride over the list (its length is device data); a one-wave team per 64-byte message
-// cost a whole wave's launch, LDS and header work.
-template <int GL>
-__device__ __forceinline__ void lanes_copy_any(uint8_t *dst, const uint8_t *src, uint64_t len, uint32_t l) {
-    // 16-byte aligned stores on dst; each 16-byte chunk read as aligned dwords and funnel-shifted
-    // by the source misalignment
-    uint64_t head = (16 - ((uintptr_t)dst & 15)) & 15;
-    if (head > len) head = len;
-    if (l < head) dst[l] = src[l];
-    const uint64_t nb = (len - head) / 16;
-    const uint8_t *s0 = src + head;
-    const uint32_t sh = (uint32_t)((uintptr_t)s0 & 3) * 8;
-    const uint32_t *sw = reinterpret_cast<const uint32_t *>((uintptr_t)s0 & ~(uintptr_t)3);
-    uint4 *dv = reinterpret_cast<uint4 *>(dst + head);
-    for (uint64_t k = l; k < nb; k += GL) {
-        const uint32_t *q = sw + 4 * k;
-        const uint32_t w0 = psy::gload<uint32_t>(q), w1 = psy::gload<uint32_t>(q + 1), w2 = psy::gload<uint32_t>(q + 2),
-                       w3 = psy::gload<uint32_t>(q + 3);
-        const uint32_t w4 = sh ? psy::gload<uint32_t>(q + 4) : 0u;  // (only when misaligned: inside src)
-        dv[k] = make_uint4((uint32_t)((((uint64_t)w1 << 32) | w0) >> sh), (uint32_t)((((uint64_t)w2 << 32) | w1) >> sh),
-                           (uint32_t)((((uint64_t)w3 << 32) | w2) >> sh), (uint32_t)((((uint64_t)w4 << 32) | w3) >> sh));
-    }
-    for (uint64_t k = head + 16 * nb + l; k < len; k += GL) dst[k] = src[k];
-}
+// cost a whole wave's launch, LDS and header work.  The sixteen lanes run the shared copy
+// (psy::copy_shifted, tdt_copy.h); its sources here are the batch's device buffers.
+constexpr uint32_t kCopyListLanes = 16;  // (q and l of the kernels below: threadIdx.x >> 4, & 15)
+static_assert(kCopyListLanes >= psy::kCopyMinT, "copy_shifted: one byte store per lane covers the head and the tail");
 
 // encode: blob = "UNCP" + payload in the message's slot (slotted batches; PAIR: a scattered batch's
 // pair tables, psy::table_at)
@@ -410,7 +392,7 @@ __global__ __launch_bounds__(256) void tdt_encode_copy_kernel(psy::EncodeArgs a)
         if (!fits) continue;
         uint8_t *dst = a.out + sb;
         if (l < 4) dst[l] = (uint8_t)(psy::kMagicUNCP >> (8 * l));
-        lanes_copy_any<16>(dst + 4, a.in + off0, len, l);
+        psy::copy_shifted<1, false>(dst + 4, a.in + off0, len, l, kCopyListLanes);
     }
 }
 
@@ -441,7 +423,7 @@ __global__ __launch_bounds__(256) void tdt_decode_copy_kernel(psy::DecodeArgs a)
             if (a.out_len) a.out_len[msg] = fits ? osize : 0;
             if (a.status) a.status[msg] = fits ? psy::ST_OK : psy::ST_CAPACITY;
         }
-        if (fits) lanes_copy_any<16>(a.out + ob, a.in + boff + 4, osize, l);
+        if (fits) psy::copy_shifted<1, false>(a.out + ob, a.in + boff + 4, osize, l, kCopyListLanes);
     }
 }
 
@@ -1513,7 +1495,7 @@ Chunk plan_chunk(const uint64_t *h_in_off, uint32_t m0, uint32_t n_msgs, bool en
     k.o_ws = align_up(k.o_st + 4ull * k.n, 256);
     k.o_len = align_up(k.o_ws + kCounterBytes + 8ull * (k.n + 1), 256);
     k.o_sbuf = align_up(k.o_len + 8ull * k.n, 256);
-    k.end = k.o_sbuf + (k.scap ? k.scap + 16 : 0);  // (+16: the gather's funnel reads past a blob)
+    k.end = k.o_sbuf + (k.scap ? k.scap + 16 : 0);  // (+16: more than the gather's copy needs — the over-read rule, tdt_copy.h)
     return k;
 }
 
@@ -1537,58 +1519,18 @@ uint64_t host_decoded_size(const uint8_t *b, uint64_t len) {
     return orig;
 }
 
-// One wave copies `len` bytes: 16-byte aligned stores; each 16-byte chunk read as five aligned
-// dwords and funnel-shifted by the (constant) source misalignment — compacted offsets have any
-// alignment, so a byte loop would be the common case otherwise.
-__device__ __forceinline__ void wave_copy_any(uint8_t *dst, const uint8_t *src, uint64_t len) {
-    const uint32_t lane = (uint32_t)psy::lane_id();
-    uint64_t head = (16 - ((uintptr_t)dst & 15)) & 15;
-    if (head > len) head = len;
-    if (lane < head) dst[lane] = src[lane];
-    const uint64_t nb = (len - head) / 16;
-    const uint8_t *s0 = src + head;
-    const uint32_t sh = (uint32_t)((uintptr_t)s0 & 3) * 8;
-    const uint32_t *sw = reinterpret_cast<const uint32_t *>((uintptr_t)s0 & ~(uintptr_t)3);
-    uint4 *dv = reinterpret_cast<uint4 *>(dst + head);
-    for (uint64_t k = lane; k < nb; k += 64) {
-        const uint32_t *q = sw + 4 * k;
-        const uint32_t w0 = psy::gload<uint32_t>(q), w1 = psy::gload<uint32_t>(q + 1), w2 = psy::gload<uint32_t>(q + 2),
-                       w3 = psy::gload<uint32_t>(q + 3);
-        // (the fifth dword only when misaligned: it may lie past the source's end otherwise)
-        const uint32_t w4 = sh ? psy::gload<uint32_t>(q + 4) : 0u;
-        dv[k] = make_uint4((uint32_t)((((uint64_t)w1 << 32) | w0) >> sh), (uint32_t)((((uint64_t)w2 << 32) | w1) >> sh),
-                           (uint32_t)((((uint64_t)w3 << 32) | w2) >> sh), (uint32_t)((((uint64_t)w4 << 32) | w3) >> sh));
-    }
-    for (uint64_t k = head + 16 * nb + lane; k < len; k += 64) dst[k] = src[k];
-}
-
 // Chunk ci's compacted output → host memory, issued behind the encode kernel so that no host
 // wait sits between a chunk's kernel and its copy (the length is device-side: the chunk's last
 // offset).  dst: the slot's pinned staging (direct = 0), or the caller's pinned buffer at the
 // running base (direct = 1; bases[ci] = the totals of the chunks before, written by the previous
 // chunk's launch, which this one follows by an event).  Past out_cap nothing is copied (the host
-// reports TDT_E_CAPACITY).  Stores are 16-byte aligned on dst; the source is read as aligned
-// dwords and funnel-shifted.
-// total bytes src → d (host memory over PCIe, or device): 16-byte stores at d's alignment, the
-// source read as aligned dwords and shifted (src + total + 4 must be readable)
+// reports TDT_E_CAPACITY).
+// total bytes src → d (mapped host memory over PCIe, or device) by the whole grid of 256-lane
+// workgroups: the shared copy (tdt_copy.h) with generic stores.  src is a chunk's device buffer at
+// both call sites (d + k.o_out of host_encode and of host_decode), so its loads are global ones;
+// what it reads beyond src + total is the over-read rule's, inside the buffer's 256-byte alignment.
 __device__ __forceinline__ void grid_copy_out(uint8_t *d, const uint8_t *src, uint64_t total) {
-    const uint64_t gtid = (uint64_t)blockIdx.x * 256 + threadIdx.x, gsz = (uint64_t)gridDim.x * 256;
-    uint64_t head = (16 - ((uintptr_t)d & 15)) & 15;
-    if (head > total) head = total;
-    if (gtid < head) d[gtid] = src[gtid];
-    const uint64_t nb = (total - head) / 16;
-    const uint8_t *s0 = src + head;
-    const uint32_t sh = (uint32_t)((uintptr_t)s0 & 3) * 8;
-    const uint32_t *sw = reinterpret_cast<const uint32_t *>((uintptr_t)s0 & ~(uintptr_t)3);
-    uint4 *dv = reinterpret_cast<uint4 *>(d + head);
-    for (uint64_t k = gtid; k < nb; k += gsz) {
-        const uint32_t *q = sw + 4 * k;
-        const uint32_t w0 = q[0], w1 = q[1], w2 = q[2], w3 = q[3];
-        const uint32_t w4 = sh ? q[4] : 0u;  // (inside the chunk buffer's slack)
-        dv[k] = make_uint4((uint32_t)((((uint64_t)w1 << 32) | w0) >> sh), (uint32_t)((((uint64_t)w2 << 32) | w1) >> sh),
-                           (uint32_t)((((uint64_t)w3 << 32) | w2) >> sh), (uint32_t)((((uint64_t)w4 << 32) | w3) >> sh));
-    }
-    for (uint64_t k = head + 16 * nb + gtid; k < total; k += gsz) d[k] = src[k];
+    psy::copy_shifted<1, false>(d, src, total, (uint64_t)blockIdx.x * 256 + threadIdx.x, (uint64_t)gridDim.x * 256);
 }
 
 __global__ __launch_bounds__(256) void host_out_kernel(const uint8_t *src, const uint64_t *chunk_off, uint32_t n,
@@ -1650,7 +1592,9 @@ __global__ __launch_bounds__(1024) void host_scan_kernel(const uint64_t *len, ui
 
 // A slotted chunk's blobs → host memory at their compacted places (the output copy of
 // host_out_kernel, gathering from the slots): P waves per blob, each a contiguous part; the
-// running base is chained as there.
+// running base is chained as there.  A wave's part goes through the shared copy (tdt_copy.h): compacted
+// offsets have any alignment, so a byte loop would be the common case otherwise.  src is the chunk's
+// slot buffer on the device (d + k.o_sbuf).
 __global__ __launch_bounds__(256) void host_gather_kernel(const uint8_t *src, const uint64_t *slot, const uint64_t *len,
                                                           const uint64_t *out_off, uint32_t n, uint32_t P, uint8_t *dst,
                                                           uint64_t *bases, uint32_t ci, uint64_t cap, int direct) {
@@ -1663,7 +1607,7 @@ __global__ __launch_bounds__(256) void host_gather_kernel(const uint8_t *src, co
     for (uint64_t w = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); w < nw; w += (uint64_t)gridDim.x * 4) {
         const uint32_t i = (uint32_t)(w / P), p = (uint32_t)(w % P);
         const uint64_t l = len[i], a = l * p / P, e = l * (p + 1) / P;
-        if (e > a) wave_copy_any(d + out_off[i] + a, src + slot[i] + a, e - a);
+        if (e > a) psy::copy_shifted<1, false>(d + out_off[i] + a, src + slot[i] + a, e - a, threadIdx.x & 63u, 64);
     }
 }
 
@@ -2175,7 +2119,8 @@ __global__ __launch_bounds__(256) void cp_len_kernel(const uint64_t *len, uint64
     if (i < n) out_off[i] = len[i];
 }
 // blob i (one wave each, four per workgroup): slot → its compacted place (capacity: the
-// TDT_E_CAPACITY of the look-back path; out_off keeps the full prefix sum either way)
+// TDT_E_CAPACITY of the look-back path; out_off keeps the full prefix sum either way), by the
+// shared copy (tdt_copy.h).  src is the context's slot buffer on the device (cp_buf).
 __global__ __launch_bounds__(256) void cp_gather_kernel(const uint8_t *src, const uint64_t *slot, const uint64_t *len,
                                                       uint8_t *dst, const uint64_t *out_off, uint64_t cap,
                                                       int32_t *status, uint32_t n) {
@@ -2186,7 +2131,7 @@ __global__ __launch_bounds__(256) void cp_gather_kernel(const uint8_t *src, cons
         if ((threadIdx.x & 63) == 0 && status && status[i] == 0) status[i] = TDT_E_CAPACITY;
         return;
     }
-    wave_copy_any(dst + o, src + slot[i], l);
+    psy::copy_shifted<1, false>(dst + o, src + slot[i], l, threadIdx.x & 63u, 64);
 }
 }  // namespace
 

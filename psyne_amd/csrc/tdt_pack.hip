@@ -4,6 +4,7 @@
 #include "tdt_pack.h"
 
 #include "../../include/psyne_tdt.h"
+#include "tdt_copy.h"
 #include "tdt_device.h"
 
 // 16-byte chunks whose loads a lane issues before their stores (a build-time knob of the measurements)
@@ -14,53 +15,13 @@
 namespace psy {
 namespace {
 
-// 16 source bytes at the aligned dwords q[0..4], shifted by the source's misalignment (sh bits):
-// the fifth dword is read only when the source is misaligned, so every dword read holds a byte
-// of the chunk (none lies outside the aligned dwords that hold the blob).
-struct PackChunk {
-    uint32_t w0, w1, w2, w3, w4;
-};
-__device__ __forceinline__ PackChunk pack_load(const uint32_t *q, uint32_t sh) {
-    PackChunk c;
-    c.w0 = gload<uint32_t>(q);
-    c.w1 = gload<uint32_t>(q + 1);
-    c.w2 = gload<uint32_t>(q + 2);
-    c.w3 = gload<uint32_t>(q + 3);
-    c.w4 = sh ? gload<uint32_t>(q + 4) : 0u;
-    return c;
-}
-__device__ __forceinline__ void pack_store(uint4 *d, const PackChunk &c, uint32_t sh) {
-    st16_nt(d, make_uint4((uint32_t)((((uint64_t)c.w1 << 32) | c.w0) >> sh), (uint32_t)((((uint64_t)c.w2 << 32) | c.w1) >> sh),
-                          (uint32_t)((((uint64_t)c.w3 << 32) | c.w2) >> sh), (uint32_t)((((uint64_t)c.w4 << 32) | c.w3) >> sh)));
-}
-
-// Thread t of T copies its share of len bytes: a head of byte stores up to the destination's next
-// 16-byte boundary, 16-byte non-temporal stores (chunk k by thread k % T, the loads of U chunks
-// issued before their stores), a tail of byte stores.
+// Thread t of T copies its share of a segment: the shared copy (tdt_copy.h) with non-temporal
+// 16-byte stores, the loads of U chunks issued before their stores.  src is a blob in device memory
+// (tdt_pack_v's contract), out the packed device buffer.
 template <uint32_t T, int U>
 __device__ __forceinline__ void pack_copy(uint8_t *dst, const uint8_t *src, uint64_t len, uint32_t t) {
-    uint64_t head = (16 - ((uintptr_t)dst & 15)) & 15;
-    if (head > len) head = len;
-    if (t < head) dst[t] = src[t];
-    const uint64_t nb = (len - head) / 16;
-    const uint8_t *s0 = src + head;
-    const uint32_t sh = (uint32_t)((uintptr_t)s0 & 3) * 8;
-    const uint32_t *sw = reinterpret_cast<const uint32_t *>((uintptr_t)s0 & ~(uintptr_t)3);
-    uint4 *dv = reinterpret_cast<uint4 *>(dst + head);
-    uint64_t k = t;
-    for (; k + (uint64_t)(U - 1) * T < nb; k += (uint64_t)U * T) {
-        PackChunk c[U];
-#pragma unroll
-        for (int g = 0; g < U; ++g) c[g] = pack_load(sw + 4 * (k + (uint64_t)g * T), sh);
-#pragma unroll
-        for (int g = 0; g < U; ++g) pack_store(dv + k + (uint64_t)g * T, c[g], sh);
-    }
-    for (; k < nb; k += T) {
-        const PackChunk c = pack_load(sw + 4 * k, sh);
-        pack_store(dv + k, c, sh);
-    }
-    const uint64_t done = head + 16 * nb;
-    if (t < len - done) dst[done + t] = src[done + t];  // (fewer than 16 bytes)
+    static_assert(T >= kCopyMinT, "copy_shifted: one byte store per thread covers the head and the tail");
+    copy_shifted<U, true>(dst, src, len, t, T);
 }
 
 __device__ __forceinline__ uint64_t shfl_u64(uint64_t v, int src) {

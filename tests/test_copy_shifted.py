@@ -1,0 +1,25 @@
+"""The funnel-shift copy shared by the passthrough, gather, host-output and pack kernels
+(psyne_amd/csrc/tdt_copy.h: the split of a copy into head, 16-byte chunks and tail, the combine of
+five aligned dwords, and the loop over them): plain host C++, checked by
+tests/cpp/test_copy_shifted.cpp — a program of its own, built with AddressSanitizer and UBSan and
+run directly."""
+import pathlib
+import re
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = pathlib.Path(__file__).resolve().parent.parent
+SRC = ROOT / "tests" / "cpp" / "test_copy_shifted.cpp"
+CXX = shutil.which("g++") or shutil.which("clang++")
+
+
+@pytest.mark.skipif(CXX is None, reason="no host C++ compiler")
+def test_copy_shifted(tmp_path):
+    exe = tmp_path / "test_copy_shifted"
+    subprocess.check_call([CXX, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined",
+                           "-fno-sanitize-recover=undefined", str(SRC), "-o", str(exe)], timeout=600)
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert re.search(r"copy shifted: 0 failures", r.stdout), r.stdout
