@@ -412,10 +412,11 @@ int tdt_ctx_error_flags(tdt_ctx *ctx, void *hip_stream, uint32_t *flags);
 
 /* Tuning / diagnostic options (tdt_ctx_create reads the same from the environment once:
  * PSYNE_TDT_LARGE_MIN, PSYNE_TDT_TILE_CAP, PSYNE_TDT_NO_SIDE, PSYNE_TDT_SMALL_MAIN,
- * PSYNE_TDT_NO_TWO_PHASE, PSYNE_TDT_COPY_THREADS).  Not needed for correct results: every setting encodes and decodes
+ * PSYNE_TDT_NO_TWO_PHASE, PSYNE_TDT_COPY_THREADS, PSYNE_TDT_ANY_TILED).  Not needed for correct results: every setting encodes and decodes
  * the same bytes. */
-#define TDT_OPT_LARGE_MIN 1               /* messages above this many bytes take the tiled path */
-#define TDT_OPT_TILE_CAP 2                /* lower tile budget per batch (tests of the fallback) */
+#define TDT_OPT_LARGE_MIN 1               /* messages above this many bytes take the tiled path (every word size:
+                                             the tuned widths' tiles and the generic widths' alike) */
+#define TDT_OPT_TILE_CAP 2                /* lower tile budget per batch (tests of the fallback; every word size) */
 #define TDT_OPT_NO_SIDE_STREAM 3          /* 1: the tile pipeline runs on the caller's stream */
 #define TDT_OPT_SMALL_ON_CALLER_STREAM 4  /* 1: small-message lists stay on the caller's stream */
 #define TDT_OPT_NO_TWO_PHASE 5            /* 1: compacted calls always take the one-pass kernels */
@@ -424,6 +425,11 @@ int tdt_ctx_error_flags(tdt_ctx *ctx, void *hip_stream, uint32_t *flags);
                                              place, without the scratch (default 0: the two phases);
                                              2: as 1, and the second pass reuses the mappings the size
                                              pass decided (the known-mapping encode) */
+#define TDT_OPT_ANY_TILED 8               /* word sizes other than 1, 2, 4, 8, 16: messages above the tiled-path
+                                             threshold (max(TDT_OPT_LARGE_MIN, 1/4096 of the batch's bytes))
+                                             are encoded as 64 KiB tiles over the whole device (default 1);
+                                             0: every such message on one workgroup.  The A/B switch: the
+                                             same bytes, lengths and statuses either way */
 int tdt_ctx_set_option(tdt_ctx *ctx, int option, uint64_t value);
 
 /* Host-memory analyze (analyze_data :206-222): h_entropy n*ws doubles, h_mapping n*ws int32

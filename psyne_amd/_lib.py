@@ -17,6 +17,7 @@ TDT_E_HIP, TDT_E_ARG, TDT_E_CAPTURE = 10, 11, 12
 TDT_OPT_LARGE_MIN, TDT_OPT_TILE_CAP, TDT_OPT_NO_SIDE_STREAM = 1, 2, 3
 TDT_OPT_SMALL_ON_CALLER_STREAM, TDT_OPT_NO_TWO_PHASE, TDT_OPT_COPY_THREADS = 4, 5, 6
 TDT_OPT_PACK_SIZES_FIRST = 7
+TDT_OPT_ANY_TILED = 8  # generic word sizes: long messages as tiles (default 1); 0: one workgroup per message
 
 
 class TdtConfigC(C.Structure):

@@ -12,6 +12,10 @@
 #define PSY_DEC_INST_TU 1
 #include "tdt_anyws.h"
 
+#include <algorithm>
+
+#include "tdt_anyws_tiles.h"
+#include "tdt_copy.h"
 #include "tdt_decode.h"
 #include "tdt_encode.h"
 
@@ -51,12 +55,181 @@ __device__ __forceinline__ uint4 ld16_msg(const uint8_t *p, int valid, const uin
 __device__ __forceinline__ uint32_t byte_of(const uint32_t (&w)[4], int i) { return (w[i >> 2] >> (8 * (i & 3))) & 0xffu; }
 
 // ---------------------------------------------------------------------------------------
+// One chunk of one stream: split into LDS, SWAR run starts, the two team scans, pair stores.  The
+// one-workgroup kernel walks a whole message with it; the tile passes walk one tile each.
+//   CH_ENCODE  the one-workgroup kernel (put8 stores, or is empty in the size pass)
+//   CH_COUNT   a tile's count pass: the carries begin at zero, so the tile's first run start finds
+//              no start before it — it goes to *s_first (+ 1) and its run is not counted here
+//   CH_EMIT    a tile's emit pass: the carries come from the tile's record.  A closed run of more
+//              than 16 full pairs (longer than a chunk, so at most one per chunk) is handed to the
+//              whole workgroup through *s_big instead of one lane's loop
+enum : int { CH_ENCODE = 0, CH_COUNT = 1, CH_EMIT = 2 };
+struct AnyRunCarry {  // uniform, carried across chunks
+    uint32_t cstart;  // last run start + 1 (0: none yet)
+    uint32_t cpairs;  // pairs emitted
+    uint32_t lastb;   // the last stream byte so far
+};
+struct AnyBigRun {
+    uint64_t po;         // where its 255-count pairs go
+    uint32_t full, val;  // how many, of which value
+};
+constexpr uint32_t kAnyLaneFull = 16;  // full pairs one lane stores itself in the emit pass
+
+template <int KIND, class Put8>
+__device__ __forceinline__ void any_chunk(const uint8_t *base, const uint8_t *lim, uint64_t n, uint32_t ws, uint32_t s,
+                                          uint32_t ks, uint64_t dpos, uint64_t cb64, const uint32_t *s_map,
+                                          const uint32_t (*s_before)[kAnyWsMax + 1], uint8_t *s_buf,
+                                          uint32_t (*s_slots)[kAW], AnyRunCarry &c, Put8 put8, uint32_t *s_first,
+                                          AnyBigRun *s_big) {
+    const uint32_t tid = threadIdx.x, n32 = (uint32_t)n;
+    // this lane's 16 message bytes, their word and position
+    const uint32_t cb = (uint32_t)cb64;
+    const uint32_t j0 = cb + 16u * tid;
+    const int valid = cb64 + 16u * tid >= n ? 0 : (n32 - j0 >= 16u ? 16 : (int)(n32 - j0));
+    // the chunk's stream bytes [B, B + Lc): stream index of message byte j =
+    // (j / ws)·ks + s_before[s][j % ws]
+    const uint32_t ce = n32 - cb < kAnyChunk ? n32 : cb + kAnyChunk;
+    const uint32_t wcb = cb / ws, pcb = cb - wcb * ws;
+    const uint32_t wce = ce / ws, pce = ce - wce * ws;
+    const uint32_t B = wcb * ks + s_before[s][pcb];
+    const uint32_t Lc = wce * ks + s_before[s][pce] - B;
+    if (valid) {
+        const uint4 v = ld16_msg(base + j0, valid, base, lim);
+        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+        uint32_t wj = j0 / ws, p = j0 - wj * ws;
+        uint32_t rel = wj * ks - B;  // + s_before[s][p]: index in the chunk's stream bytes
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            if (i < valid && s_map[p] == s) s_buf[16u + rel + s_before[s][p]] = (uint8_t)byte_of(w, i);
+            if (++p == ws) {
+                p = 0u;
+                rel += ks;
+            }
+        }
+    }
+    __syncthreads();
+    if constexpr (KIND == CH_EMIT) {
+        if (tid == 0) s_big->full = 0u;  // (every lane has read the chunk before's; this chunk's is written behind two more barriers)
+    }
+    // ---- RLE (simple_rle_compress :557-582) of the chunk's stream bytes, 16 per
+    // lane.  A stream byte that differs from the one before it starts a run; every
+    // run start closes the run before it, which began at the last run start so far
+    // (a max-scan over the lanes, carried across chunks) and emits ceil(L / 255)
+    // pairs: 255, ..., 255, remainder.  An add-scan of the pair counts places them.
+    const uint32_t q0 = 16u * tid;
+    const uint32_t m = q0 >= Lc ? 0u : (Lc - q0 >= 16u ? 16u : Lc - q0);
+    const uint4 xv = *reinterpret_cast<const uint4 *>(s_buf + 16u + q0);
+    const uint32_t x[4] = {xv.x, xv.y, xv.z, xv.w};
+    const uint32_t prev = s_buf[15u + q0];
+    if (Lc) c.lastb = s_buf[15u + Lc];
+    uint32_t sm = neq_prev_mask4(x[0], prev << 24) | (neq_prev_mask4(x[1], x[0]) << 4) |
+                  (neq_prev_mask4(x[2], x[1]) << 8) | (neq_prev_mask4(x[3], x[2]) << 12);
+    if (B + q0 == 0u) sm |= 1u;  // the stream's first byte
+    sm &= (1u << m) - 1u;
+    uint32_t vmax[1] = {sm ? B + q0 + (31u - (uint32_t)__builtin_clz(sm)) + 1u : 0u}, tmax[1];
+    team_excl_scan<kAW, 1, OpMax>(vmax, tmax, s_slots[0]);
+    const uint32_t cur = vmax[0] > c.cstart ? vmax[0] : c.cstart;  // run start + 1 entering this lane
+    // only a lane's first run start can close a run longer than its 16 bytes
+    uint32_t first_full = 0u, first_rem = 0u, np = 0u;
+    if (sm) {
+        const uint32_t qf = B + q0 + (uint32_t)__builtin_ctz(sm);
+        np = (uint32_t)__builtin_popcount(sm);
+        if (KIND == CH_COUNT ? cur == 0u : qf == 0u) {
+            --np;  // nothing before the stream's first byte (the count pass: nothing known before the tile's first start)
+            if constexpr (KIND == CH_COUNT) *s_first = qf + 1u;
+        } else {
+            const uint32_t Lr = qf - (cur - 1u);
+            first_full = (Lr - 1u) / 255u;
+            first_rem = Lr - 255u * first_full;
+            np += first_full;
+        }
+    }
+    uint32_t vadd[1] = {np}, tadd[1];
+    team_excl_scan<kAW, 1, OpAdd>(vadd, tadd, s_slots[1]);
+    if constexpr (KIND != CH_COUNT) {
+        if (sm) {
+            uint64_t po = dpos + 2ull * (c.cpairs + vadd[0]);
+            uint32_t rs = cur;  // start + 1 of the run being closed
+            bool first = true;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                if (!((sm >> i) & 1u)) continue;
+                const uint32_t q = B + q0 + (uint32_t)i;
+                const uint32_t val = i ? byte_of(x, i - 1) : prev;
+                if (q != 0u) {
+                    uint32_t cnt = q - (rs - 1u);
+                    if (first) {
+                        if (KIND == CH_EMIT && first_full > kAnyLaneFull) {
+                            s_big->po = po;
+                            s_big->val = val;
+                            s_big->full = first_full;
+                            po += 2ull * first_full;
+                        } else {
+                            for (uint32_t f = 0; f < first_full; ++f) {
+                                put8(po, 255u);
+                                put8(po + 1, val);
+                                po += 2;
+                            }
+                        }
+                        cnt = first_rem;
+                    }
+                    put8(po, cnt);
+                    put8(po + 1, val);
+                    po += 2;
+                }
+                first = false;
+                rs = q + 1u;
+            }
+        }
+    }
+    if constexpr (KIND == CH_EMIT) {
+        __syncthreads();
+        const uint32_t full = s_big->full;
+        if (full) {  // (uniform) a run longer than a chunk: its 255-count pairs by every lane
+            const uint64_t po = s_big->po;
+            const uint32_t val = s_big->val;
+            for (uint32_t f = tid; f < full; f += kAnyTeam) {
+                put8(po + 2ull * f, 255u);
+                put8(po + 2ull * f + 1, val);
+            }
+        }
+    }
+    c.cstart = tmax[0] > c.cstart ? tmax[0] : c.cstart;
+    c.cpairs += tadd[0];
+    if (tid == 0 && Lc) s_buf[15] = (uint8_t)c.lastb;  // (only lane 0 reads it)
+}
+
+// The entropy of one byte position (calculate_entropy :470-480): the exact chain only.  Lane l of
+// a wave holds the counts of bins l, l + 64, l + 128, l + 192 and computes their (-prob, log2 prob)
+// (0, 0 for an empty bin: fma(0, 0, e) == e for the non-negative running sum), then every lane
+// runs the chain over the bins in order 0..255.
+__device__ __forceinline__ double any_entropy(const uint32_t (&c)[4], double total) {
+    double np[4], L[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        np[k] = 0.0;
+        L[k] = 0.0;
+        if (c[k]) {
+            const double prob = (double)c[k] / total;
+            L[k] = psy_log2_glibc(prob, c_log2_tab, c_log2_tab2);
+            np[k] = -prob;
+        }
+    }
+    double e = 0.0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        for (int l = 0; l < 64; ++l) e = __builtin_fma(readlane_f64(np[k], l), readlane_f64(L[k], l), e);
+    return e;
+}
+
+// ---------------------------------------------------------------------------------------
 // Encode.  HP: histogram positions held in LDS (>= ws; 1 for MODE_MAPPED, which has none).
 // MODE_SIZES: the size pass — the same analysis, mapping and split + RLE loop of both streams with
 // every store to the blob compiled out (stream 0's pair count places stream 1, so there is no
 // separate count to stop at); the length goes to out_len, and there is no slot.
+// mark (null: none): a non-zero word = the message belongs to the tile pipeline below.
 template <int MODE, int HP, bool PAIR = false>
-__global__ __launch_bounds__(kAnyTeam) void tdt_encode_any_kernel(EncodeArgs a, uint32_t ws) {
+__global__ __launch_bounds__(kAnyTeam) void tdt_encode_any_kernel(EncodeArgs a, uint32_t ws, const uint32_t *mark) {
     __shared__ uint32_t s_hist[HP * 256];
     __shared__ double s_ent[kAnyWsMax];
     __shared__ uint32_t s_map[kAnyWsMax];           // mapping[b] in {0, 1}
@@ -68,6 +241,7 @@ __global__ __launch_bounds__(kAnyTeam) void tdt_encode_any_kernel(EncodeArgs a, 
     const uint32_t tid = threadIdx.x, lane = (uint32_t)lane_id(), wv = tid >> 6;
     const uint32_t msg = blockIdx.x;
     if (msg >= a.n_msgs) return;
+    if (mark && mark[msg]) return;  // (uniform) a long message: the tile pipeline's
     const uint64_t off0 = a.in_off[table_at<PAIR>(msg, 0)];
     // (a mixed-width batch: this message belongs to another width's pipeline — nothing is touched)
     if (PAIR && pair_absent(off0, a.in_off[table_at<PAIR>(msg, 1)])) return;
@@ -159,31 +333,18 @@ __global__ __launch_bounds__(kAnyTeam) void tdt_encode_any_kernel(EncodeArgs a, 
             }
         }
         __syncthreads();
-        // ---- entropies (calculate_entropy :470-480): the exact chain only.  A wave takes one
-        // position at a time: lane l computes (-prob, log2 prob) of bins l, l + 64, l + 128,
-        // l + 192 (0, 0 for an empty bin: fma(0, 0, e) == e for the non-negative running sum),
-        // then every lane runs the chain over the bins in order 0..255.
+        // ---- entropies (any_entropy): a wave takes one position at a time
         const double total = (double)wc;
         for (uint32_t b = wv; b < ws; b += kAW) {
-            double np[4], L[4];
+            uint32_t c[4];
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                const uint32_t c = s_hist[b * 256u + 64u * k + lane];
+                c[k] = s_hist[b * 256u + 64u * k + lane];
                 if constexpr (MODE == MODE_ANALYZE) {
-                    if (a.hist_out) a.hist_out[((uint64_t)msg * ws + b) * 256 + 64u * k + lane] = c;
-                }
-                np[k] = 0.0;
-                L[k] = 0.0;
-                if (c) {
-                    const double prob = (double)c / total;
-                    L[k] = psy_log2_glibc(prob, c_log2_tab, c_log2_tab2);
-                    np[k] = -prob;
+                    if (a.hist_out) a.hist_out[((uint64_t)msg * ws + b) * 256 + 64u * k + lane] = c[k];
                 }
             }
-            double e = 0.0;
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                for (int l = 0; l < 64; ++l) e = __builtin_fma(readlane_f64(np[k], l), readlane_f64(L[k], l), e);
+            const double e = any_entropy(c, total);
             if (lane == 0) s_ent[b] = e;
         }
         __syncthreads();
@@ -244,119 +405,30 @@ __global__ __launch_bounds__(kAnyTeam) void tdt_encode_any_kernel(EncodeArgs a, 
         for (uint32_t s = 0; s < ns; ++s) {
             const uint32_t ks = s_before[s][ws];
             const uint64_t dpos = o + 4;  // the stream's pairs
-            // carries across chunks (uniform): last run start + 1 (0: none yet), pairs emitted
-            uint32_t cstart = 0u, cpairs = 0u, lastb = 0u;
+            AnyRunCarry c{0u, 0u, 0u};  // carries across chunks (uniform)
             if (ks) {
-                for (uint64_t cb64 = 0; cb64 < n; cb64 += kAnyChunk) {  // (n < 2^32; cb + 4096 may not be)
-                    // this lane's 16 message bytes, their word and position
-                    const uint32_t cb = (uint32_t)cb64;
-                    const uint32_t j0 = cb + 16u * tid;
-                    const int valid = cb64 + 16u * tid >= n ? 0 : (n32 - j0 >= 16u ? 16 : (int)(n32 - j0));
-                    // the chunk's stream bytes [B, B + Lc): stream index of message byte j =
-                    // (j / ws)·ks + s_before[s][j % ws]
-                    const uint32_t ce = n32 - cb < kAnyChunk ? n32 : cb + kAnyChunk;
-                    const uint32_t wcb = cb / ws, pcb = cb - wcb * ws;
-                    const uint32_t wce = ce / ws, pce = ce - wce * ws;
-                    const uint32_t B = wcb * ks + s_before[s][pcb];
-                    const uint32_t Lc = wce * ks + s_before[s][pce] - B;
-                    if (valid) {
-                        const uint4 v = ld16_msg(base + j0, valid, base, lim);
-                        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-                        uint32_t wj = j0 / ws, p = j0 - wj * ws;
-                        uint32_t rel = wj * ks - B;  // + s_before[s][p]: index in the chunk's stream bytes
-#pragma unroll
-                        for (int i = 0; i < 16; ++i) {
-                            if (i < valid && s_map[p] == s) s_buf[16u + rel + s_before[s][p]] = (uint8_t)byte_of(w, i);
-                            if (++p == ws) {
-                                p = 0u;
-                                rel += ks;
-                            }
-                        }
-                    }
-                    __syncthreads();
-                    // ---- RLE (simple_rle_compress :557-582) of the chunk's stream bytes, 16 per
-                    // lane.  A stream byte that differs from the one before it starts a run; every
-                    // run start closes the run before it, which began at the last run start so far
-                    // (a max-scan over the lanes, carried across chunks) and emits ceil(L / 255)
-                    // pairs: 255, ..., 255, remainder.  An add-scan of the pair counts places them.
-                    const uint32_t q0 = 16u * tid;
-                    const uint32_t m = q0 >= Lc ? 0u : (Lc - q0 >= 16u ? 16u : Lc - q0);
-                    const uint4 xv = *reinterpret_cast<const uint4 *>(s_buf + 16u + q0);
-                    const uint32_t x[4] = {xv.x, xv.y, xv.z, xv.w};
-                    const uint32_t prev = s_buf[15u + q0];
-                    if (Lc) lastb = s_buf[15u + Lc];
-                    uint32_t sm = neq_prev_mask4(x[0], prev << 24) | (neq_prev_mask4(x[1], x[0]) << 4) |
-                                  (neq_prev_mask4(x[2], x[1]) << 8) | (neq_prev_mask4(x[3], x[2]) << 12);
-                    if (B + q0 == 0u) sm |= 1u;  // the stream's first byte
-                    sm &= (1u << m) - 1u;
-                    uint32_t vmax[1] = {sm ? B + q0 + (31u - (uint32_t)__builtin_clz(sm)) + 1u : 0u}, tmax[1];
-                    team_excl_scan<kAW, 1, OpMax>(vmax, tmax, s_slots[0]);
-                    const uint32_t cur = vmax[0] > cstart ? vmax[0] : cstart;  // run start + 1 entering this lane
-                    // only a lane's first run start can close a run longer than its 16 bytes
-                    uint32_t first_full = 0u, first_rem = 0u, np = 0u;
-                    if (sm) {
-                        const uint32_t qf = B + q0 + (uint32_t)__builtin_ctz(sm);
-                        np = (uint32_t)__builtin_popcount(sm);
-                        if (qf == 0u) {
-                            --np;  // nothing before the stream's first byte
-                        } else {
-                            const uint32_t Lr = qf - (cur - 1u);
-                            first_full = (Lr - 1u) / 255u;
-                            first_rem = Lr - 255u * first_full;
-                            np += first_full;
-                        }
-                    }
-                    uint32_t vadd[1] = {np}, tadd[1];
-                    team_excl_scan<kAW, 1, OpAdd>(vadd, tadd, s_slots[1]);
-                    if (sm) {
-                        uint64_t po = dpos + 2ull * (cpairs + vadd[0]);
-                        uint32_t rs = cur;  // start + 1 of the run being closed
-                        bool first = true;
-#pragma unroll
-                        for (int i = 0; i < 16; ++i) {
-                            if (!((sm >> i) & 1u)) continue;
-                            const uint32_t q = B + q0 + (uint32_t)i;
-                            const uint32_t val = i ? byte_of(x, i - 1) : prev;
-                            if (q != 0u) {
-                                uint32_t cnt = q - (rs - 1u);
-                                if (first) {
-                                    for (uint32_t f = 0; f < first_full; ++f) {
-                                        put8(po, 255u);
-                                        put8(po + 1, val);
-                                        po += 2;
-                                    }
-                                    cnt = first_rem;
-                                }
-                                put8(po, cnt);
-                                put8(po + 1, val);
-                                po += 2;
-                            }
-                            first = false;
-                            rs = q + 1u;
-                        }
-                    }
-                    cstart = tmax[0] > cstart ? tmax[0] : cstart;
-                    cpairs += tadd[0];
-                    if (tid == 0 && Lc) s_buf[15] = (uint8_t)lastb;  // (only lane 0 reads it)
-                }
+                for (uint64_t cb64 = 0; cb64 < n; cb64 += kAnyChunk)  // (n < 2^32; cb + 4096 may not be)
+                    any_chunk<CH_ENCODE>(base, lim, n, ws, s, ks, dpos, cb64, s_map, s_before, s_buf, s_slots, c, put8,
+                                         nullptr, nullptr);
                 // the last run closes at the end of the stream
                 const uint32_t S = wc * ks;
-                const uint32_t Lr = S - (cstart - 1u);
+                const uint32_t Lr = S - (c.cstart - 1u);
                 const uint32_t full = (Lr - 1u) / 255u;
                 if (tid == 0) {
-                    uint64_t po = dpos + 2ull * cpairs;
+                    uint64_t po = dpos + 2ull * c.cpairs;
                     for (uint32_t f = 0; f < full; ++f) {
                         put8(po, 255u);
-                        put8(po + 1, lastb);
+                        put8(po + 1, c.lastb);
                         po += 2;
                     }
                     put8(po, Lr - 255u * full);
-                    put8(po + 1, lastb);
+                    put8(po + 1, c.lastb);
                     s_buf[15] = 0;
                 }
-                cpairs += full + 1u;
+                c.cpairs += full + 1u;
                 __syncthreads();  // the next stream's chunks reuse s_buf
             }
+            const uint32_t cpairs = c.cpairs;
             if (tid == 0) put32(o, 2u * cpairs);
             o = dpos + 2ull * cpairs;
         }
@@ -372,6 +444,373 @@ __global__ __launch_bounds__(kAnyTeam) void tdt_encode_any_kernel(EncodeArgs a, 
                 }
             }
         }
+    }
+}
+
+// ---------------------------------------------------------------------------------------
+// The tiled encode of long messages (tdt_anyws.h).  Every kernel below but the plan runs a fixed
+// grid striding over the records the plan claimed; their counts stay in device memory.
+
+// the records in use: what the plan claimed, within the budgets it ran with
+__device__ __forceinline__ uint32_t any_claimed(const AnyTiledArgs &t, AnyCount k, uint32_t cap) {
+    const unsigned long long c = t.cnt[k];
+    return (uint32_t)__builtin_amdgcn_readfirstlane((int)(c < cap ? (uint32_t)c : cap));
+}
+// The message of tile record e among the nl large records of this launch's width — each owns the
+// records [tile0, tile0 + ntiles) it claimed — and the tile's index in it; null: a hole left by a
+// failed claim, or another width's.  Every wave of the workgroup searches alike, 64 records a step
+// (one plan lane writing a long message's thousands of tile entries took 115 us of a 1.6 ms call).
+__device__ __forceinline__ const AnyLarge *any_tile_owner(const AnyTiledArgs &t, uint32_t nl, uint32_t e, uint32_t ws,
+                                                          uint32_t &tile) {
+    const uint32_t lane = (uint32_t)lane_id();
+    for (uint32_t L0 = 0; L0 < nl; L0 += 64u) {  // (uniform)
+        const uint32_t L = L0 + lane;
+        bool hit = false;
+        if (L < nl) {
+            const AnyLarge &g = t.large[L];
+            hit = g.ws == ws && e - g.tile0 < g.ntiles;
+        }
+        const uint64_t m = __ballot(hit);
+        if (m) {
+            const AnyLarge *g = t.large + L0 + (uint32_t)__builtin_ctzll(m);
+            tile = e - (uint32_t)__builtin_amdgcn_readfirstlane((int)g->tile0);
+            return g;
+        }
+    }
+    return nullptr;
+}
+
+// ---- plan: one lane per message
+template <bool PAIR>
+__global__ __launch_bounds__(256) void tdt_any_plan_kernel(EncodeArgs a, AnyTiledArgs t, uint32_t ws, int mode) {
+    const uint32_t msg = blockIdx.x * 256u + threadIdx.x;
+    if (msg >= a.n_msgs) return;
+    uint32_t mark = 0u;
+    const uint64_t off0 = a.in_off[table_at<PAIR>(msg, 0)], off1 = a.in_off[table_at<PAIR>(msg, 1)];
+    // the tiled path's threshold, as the tuned plan's (tdt_encode_plan_kernel)
+    const uint64_t share = (PAIR ? t.cnt[t.bytes_at] : a.in_off[a.n_msgs] - a.in_off[0]) / 4096;
+    const uint64_t thr = share > t.large_min ? share : t.large_min;
+    const uint64_t n = off1 - off0;
+    // (a message of 4 GiB or more stays where it is: UNCP on one workgroup)
+    if (!(PAIR && pair_absent(off0, off1)) && n > thr && n < (1ull << 32)) {
+        const bool sizes = mode == MODE_SIZES;
+        const bool compress = a.policy_on && n >= a.min_tensor && (n % 4 == 0) && n >= 64 && (n % ws == 0);
+        uint64_t bits = 0;
+        bool bad = false;
+        if (compress && mode == MODE_MAPPED) {
+            if constexpr (PAIR) {
+                bits = reinterpret_cast<const uint64_t *>(a.mapping_in)[msg];
+                bad = !mapbits_ok(bits, (int)ws);
+            } else {
+                for (uint32_t p = 0; p < ws; ++p) {
+                    const int32_t m = a.mapping_in[(uint64_t)msg * ws + p];
+                    bad = bad || m < 0 || m > 1;
+                    bits |= (uint64_t)(m & 1) << p;
+                }
+            }
+        }
+        uint64_t slot_b = 0, cap = ~0ull;
+        if (!sizes) {
+            slot_b = a.slot_off[table_at<PAIR>(msg, 0)];
+            cap = a.slot_off[table_at<PAIR>(msg, 1)] - slot_b;
+        }
+        bool claim = !bad;  // (an invalid mapping: the one-workgroup kernel reports it)
+        if (!compress) {
+            if (sizes || n + 4 > cap) {  // nothing to copy: the passthrough's length, or a slot too small for it
+                const bool fits = n + 4 <= cap;
+                if (a.status) a.status[msg] = fits ? ST_OK : ST_CAPACITY;
+                if (a.out_len) a.out_len[msg] = fits ? n + 4 : 0;
+                claim = false;
+                mark = 1u;
+            }
+        }
+        if (claim) {
+            const uint32_t nt = (uint32_t)((n + kAnyTile - 1) / kAnyTile);
+            const unsigned long long L = atomicAdd(t.cnt + AC_LARGE, 1ull);
+            const unsigned long long T = atomicAdd(t.cnt + AC_TILES, (unsigned long long)nt);
+            if (L < t.lcap && T + nt <= t.tcap) {
+                AnyLarge g{};
+                g.src = a.in + off0;
+                g.dst = sizes ? nullptr : a.out + slot_b;
+                g.cap = cap;
+                g.mapbits = bits;
+                g.msg = msg;
+                g.n = (uint32_t)n;
+                g.ws = ws;
+                g.flags = compress ? 0u : kAnyUncp;
+                g.tile0 = (uint32_t)T;
+                g.ntiles = nt;
+                t.large[L] = g;  // (its tile records [T, T + nt) are found through it: any_tile_owner)
+                if (!compress) {  // the passthrough blob's marker, length and status; its tiles copy the payload
+                    if (a.status) a.status[msg] = ST_OK;
+                    if (a.out_len) a.out_len[msg] = n + 4;
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) g.dst[i] = (uint8_t)(kMagicUNCP >> (8 * i));
+                }
+                mark = 1u;
+            } else if (L < t.lcap) {  // a budget is spent: the one-workgroup kernel keeps the message
+                AnyLarge g{};
+                t.large[L] = g;  // (ws 0, no tiles: no launch's record)
+            }
+        }
+    }
+    t.mark[msg] = mark;
+}
+
+// ---- histograms: ws x 256 counts of the tiles of kAnySpanTiles records, added to their message's.
+// kAnyHistTeam lanes: a span is one workgroup's serial walk, and a 256 MiB message has 512 of them
+// on 256 CUs — two 4-wave workgroups a CU left the LDS atomics' latency uncovered
+constexpr uint32_t kAnyHistTeam = 1024;
+template <int HP>
+__global__ __launch_bounds__(kAnyHistTeam) void tdt_any_hist_kernel(AnyTiledArgs t, uint32_t ws) {
+    __shared__ uint32_t s_hist[HP * 256];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t nt = any_claimed(t, AC_TILES, t.tcap), nl = any_claimed(t, AC_LARGE, t.lcap);
+    for (uint32_t i = tid; i < ws * 256u; i += kAnyHistTeam) s_hist[i] = 0u;
+    __syncthreads();
+    // the LDS counts → the message's histogram (integer adds: any order gives the same counts)
+    auto flush = [&](const AnyLarge *g) __attribute__((always_inline)) {
+        __syncthreads();
+        uint32_t *h = t.hist + (size_t)(g - t.large) * (kAnyWsMax * 256);
+        for (uint32_t i = tid; i < ws * 256u; i += kAnyHistTeam) {
+            const uint32_t c = s_hist[i];
+            if (c) {
+                atomicAdd(h + i, c);
+                s_hist[i] = 0u;
+            }
+        }
+        __syncthreads();
+    };
+    constexpr uint32_t kStride = 16u * kAnyHistTeam;  // message bytes per step of the workgroup
+    for (uint32_t e0 = blockIdx.x * kAnySpanTiles; e0 < nt; e0 += gridDim.x * kAnySpanTiles) {
+        const AnyLarge *cur = nullptr;
+        for (uint32_t e = e0; e < nt && e < e0 + kAnySpanTiles; ++e) {  // (uniform)
+            uint32_t tt = 0;
+            const AnyLarge *g = any_tile_owner(t, nl, e, ws, tt);
+            if (g && (g->flags & kAnyUncp)) g = nullptr;
+            if (g != cur) {
+                if (cur) flush(cur);
+                cur = g;
+            }
+            if (!g) continue;
+            const uint8_t *base = g->src;
+            const uint64_t n = g->n;
+            const uint64_t jb = (uint64_t)tt * kAnyTile, je = n - jb < kAnyTile ? n : jb + kAnyTile;
+            // byte j counts at position j mod ws
+            const uint32_t step = kStride % ws;
+            uint32_t p0 = (uint32_t)((jb + 16ull * tid) % ws);
+            for (uint64_t j0 = jb + 16ull * tid; j0 < je; j0 += kStride) {
+                const int valid = je - j0 >= 16 ? 16 : (int)(je - j0);
+                const uint4 v = ld16_msg(base + j0, valid, base, base + n);
+                const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+                uint32_t p = p0;
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    if (i < valid) atomicAdd(&s_hist[p * 256u + byte_of(w, i)], 1u);
+                    p = p + 1u == ws ? 0u : p + 1u;
+                }
+                p0 += step;
+                if (p0 >= ws) p0 -= ws;
+            }
+        }
+        if (cur) flush(cur);
+    }
+}
+
+// ---- mapping: the one-workgroup kernel's entropies and threshold over a large message's histogram
+__global__ __launch_bounds__(kAnyTeam) void tdt_any_map_kernel(AnyTiledArgs t, uint32_t ws) {
+    __shared__ double s_ent[kAnyWsMax];
+    const uint32_t tid = threadIdx.x, lane = (uint32_t)lane_id(), wv = tid >> 6;
+    const uint32_t nl = any_claimed(t, AC_LARGE, t.lcap);
+    for (uint32_t L = blockIdx.x; L < nl; L += gridDim.x) {
+        AnyLarge *g = t.large + L;
+        if ((uint32_t)__builtin_amdgcn_readfirstlane((int)g->ws) != ws || (g->flags & kAnyUncp)) continue;  // (uniform)
+        uint32_t *h = t.hist + (size_t)L * (kAnyWsMax * 256);
+        const double total = (double)(g->n / ws);
+        for (uint32_t b = wv; b < ws; b += kAW) {
+            uint32_t c[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                c[k] = h[b * 256u + 64u * k + lane];
+                h[b * 256u + 64u * k + lane] = 0u;  // (all zero again for the next call)
+            }
+            const double e = any_entropy(c, total);
+            if (lane == 0) s_ent[b] = e;
+        }
+        __syncthreads();
+        // perform_clustering :507-525: entropy > in-order sum / ws
+        if (tid == 0) {
+            double sum = 0.0;
+            for (uint32_t b = 0; b < ws; ++b) sum += s_ent[b];
+            const double thr = sum / (double)ws;
+            uint64_t bits = 0;
+            for (uint32_t b = 0; b < ws; ++b) bits |= (uint64_t)(s_ent[b] > thr ? 1u : 0u) << b;
+            g->mapbits = bits;
+        }
+        __syncthreads();
+    }
+}
+
+// ---- count (EMIT false) and emit (EMIT true): the chunks of one tile, stream after stream
+template <bool EMIT>
+__global__ __launch_bounds__(kAnyTeam) void tdt_any_tile_kernel(AnyTiledArgs t, uint32_t ws) {
+    __shared__ uint32_t s_map[kAnyWsMax];
+    __shared__ uint32_t s_before[2][kAnyWsMax + 1];
+    __shared__ __attribute__((aligned(16))) uint8_t s_buf[16 + kAnyChunk + 16];
+    __shared__ uint32_t s_slots[2][kAW];
+    __shared__ uint32_t s_first;
+    __shared__ AnyBigRun s_big;
+    const uint32_t tid = threadIdx.x;
+    const uint32_t nt = any_claimed(t, AC_TILES, t.tcap), nl = any_claimed(t, AC_LARGE, t.lcap);
+    for (uint32_t e = blockIdx.x; e < nt; e += gridDim.x) {  // (uniform)
+        AnyTile &r = t.tiles[e];
+        uint32_t tt = 0;
+        const AnyLarge *g = any_tile_owner(t, nl, e, ws, tt);
+        if (!g) continue;
+        const uint8_t *base = g->src;
+        const uint64_t n = g->n;
+        const uint64_t jb = (uint64_t)tt * kAnyTile, je = n - jb < kAnyTile ? n : jb + kAnyTile;
+        if (g->flags & kAnyUncp) {  // a passthrough message: the tile's payload bytes behind the marker
+            if constexpr (EMIT) copy_shifted<1, false>(g->dst + 4 + jb, base + jb, je - jb, tid, kAnyTeam);
+            continue;
+        }
+        if (EMIT && !g->ok) continue;  // the blob does not fit its slot: nothing is written
+        const uint64_t bits = g->mapbits;
+        __syncthreads();  // (the tile before is done with the arrays)
+        if (tid < ws) s_map[tid] = mapbits_at(bits, (int)tid);
+        if (tid <= ws) {
+            s_before[0][tid] = any_before(bits, 0u, tid);
+            s_before[1][tid] = any_before(bits, 1u, tid);
+        }
+        __syncthreads();
+        const uint32_t ns = s_before[1][ws] ? 2u : 1u;
+        uint8_t *dst = g->dst;
+        const uint64_t cap = g->cap;
+        auto put8 = [&](uint64_t o, uint32_t v) __attribute__((always_inline)) {
+            if (o < cap) dst[o] = (uint8_t)v;  // (every store is bounded by the slot)
+        };
+        for (uint32_t s = 0; s < ns; ++s) {
+            const uint32_t ks = s_before[s][ws];
+            if (!ks) continue;  // (an empty stream 0: its length word is the scan's)
+            // the stream's pairs: behind the header, the mapping and the length word(s); stream 0's total places stream 1
+            const uint64_t dpos = 20 + 4ull * ws + 4 + (s ? 2ull * g->pairs[0] + 4 : 0ull);
+            const AnyRange R = any_tile_range((uint32_t)jb, (uint32_t)je, ws, bits, s);
+            // the stream byte before the tile's first: at most ws message bytes back
+            const uint32_t pb = R.b ? base[any_pred_pos((uint32_t)jb, ws, bits, s)] : 0u;
+            AnyRunCarry c{EMIT ? r.carry[s] : 0u, EMIT ? r.base[s] : 0u, pb};
+            if (tid == 0) {
+                s_buf[15] = (uint8_t)pb;
+                s_first = 0u;
+            }
+            __syncthreads();
+            for (uint64_t cb64 = jb; cb64 < je; cb64 += kAnyChunk)
+                any_chunk<EMIT ? CH_EMIT : CH_COUNT>(base, base + n, n, ws, s, ks, dpos, cb64, s_map, s_before, s_buf, s_slots, c,
+                                                     put8, &s_first, &s_big);
+            __syncthreads();  // (s_first is written; the next stream's chunks reuse s_buf)
+            if constexpr (!EMIT) {
+                if (tid == 0) {
+                    r.first[s] = s_first;
+                    r.last[s] = c.cstart;
+                    r.inner[s] = c.cpairs;
+                }
+            } else if (tt + 1u == g->ntiles) {  // the stream's last tile: the run that closes at the stream's end
+                const uint32_t S = (g->n / ws) * ks;
+                const uint32_t Lr = S - (c.cstart - 1u);
+                const uint32_t full = (Lr - 1u) / 255u;
+                const uint64_t po = dpos + 2ull * c.cpairs;
+                for (uint32_t f = tid; f < full; f += kAnyTeam) {
+                    put8(po + 2ull * f, 255u);
+                    put8(po + 2ull * f + 1, c.lastb);
+                }
+                if (tid == 0) {
+                    put8(po + 2ull * full, Lr - 255u * full);
+                    put8(po + 2ull * full + 1, c.lastb);
+                }
+            }
+        }
+    }
+}
+
+// ---- scan: one workgroup per large message over its tile records; the blob's fixed words
+__global__ __launch_bounds__(kAnyTeam) void tdt_any_scan_kernel(EncodeArgs a, AnyTiledArgs t, uint32_t ws, int mode) {
+    __shared__ uint32_t s_slots[2][2 * kAW];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t nl = any_claimed(t, AC_LARGE, t.lcap);
+    for (uint32_t L = blockIdx.x; L < nl; L += gridDim.x) {
+        AnyLarge *g = t.large + L;
+        if ((uint32_t)__builtin_amdgcn_readfirstlane((int)g->ws) != ws || (g->flags & kAnyUncp)) continue;  // (uniform)
+        const uint64_t bits = g->mapbits;
+        const uint32_t n32 = g->n, wc = n32 / ws, nt = g->ntiles;
+        const uint32_t k[2] = {any_before(bits, 0u, ws), any_before(bits, 1u, ws)};
+        const uint32_t ns = k[1] ? 2u : 1u;
+        AnyTile *tiles = t.tiles + g->tile0;
+        uint32_t carry[2] = {0u, 0u}, base[2] = {0u, 0u};  // (uniform) behind the tiles so far
+        for (uint32_t i0 = 0; i0 < nt; i0 += kAnyTeam) {
+            const uint32_t i = i0 + tid;
+            AnyTileRuns runs[2] = {{0u, 0u, 0u}, {0u, 0u, 0u}};
+            if (i < nt) {
+#pragma unroll
+                for (int s = 0; s < 2; ++s)
+                    if ((uint32_t)s < ns && k[s]) runs[s] = AnyTileRuns{tiles[i].first[s], tiles[i].last[s], tiles[i].inner[s]};
+            }
+            uint32_t vmax[2] = {runs[0].last, runs[1].last}, tmax[2];
+            team_excl_scan<kAW, 2, OpMax>(vmax, tmax, s_slots[0]);
+            uint32_t vadd[2], tadd[2], cin[2];
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                cin[s] = vmax[s] > carry[s] ? vmax[s] : carry[s];
+                vadd[s] = any_tile_pairs(runs[s], cin[s]);
+            }
+            team_excl_scan<kAW, 2, OpAdd>(vadd, tadd, s_slots[1]);
+            if (i < nt) {
+#pragma unroll
+                for (int s = 0; s < 2; ++s) {
+                    tiles[i].carry[s] = cin[s];
+                    tiles[i].base[s] = base[s] + vadd[s];
+                }
+            }
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                carry[s] = tmax[s] > carry[s] ? tmax[s] : carry[s];
+                base[s] += tadd[s];
+            }
+        }
+        // the run that closes at either stream's end; stream 0's total places stream 1
+        uint32_t pairs[2] = {0u, 0u};
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+            if ((uint32_t)s < ns && k[s]) pairs[s] = base[s] + any_final_pairs(wc * k[s], carry[s]);
+        const bool sizes = mode == MODE_SIZES;
+        uint8_t *dst = g->dst;
+        const uint64_t cap = g->cap;
+        auto put32 = [&](uint64_t o, uint32_t v) __attribute__((always_inline)) {
+            if (sizes) return;
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if (o + i < cap) dst[o + i] = (uint8_t)(v >> (8 * i));
+        };
+        const uint64_t o0 = 20 + 4ull * ws, o1 = o0 + 4 + 2ull * pairs[0];
+        const uint64_t o = ns == 2u ? o1 + 4 + 2ull * pairs[1] : o1;
+        const bool fits = sizes || o <= cap;
+        // header (serialize :81-117): magic, original size, streams, word size, mapping; the length words
+        if (tid < ws) put32(20 + 4ull * tid, mapbits_at(bits, (int)tid));
+        if (tid == 0) {
+            put32(0, kMagicTDT);
+            put32(4, n32);
+            put32(8, ns);
+            put32(12, ws);
+            put32(16, ws);
+            put32(o0, 2u * pairs[0]);
+            if (ns == 2u) put32(o1, 2u * pairs[1]);
+            g->pairs[0] = pairs[0];
+            g->pairs[1] = pairs[1];
+            g->ok = fits ? 1u : 0u;
+            const uint32_t msg = g->msg;
+            if (a.status) a.status[msg] = fits ? ST_OK : ST_CAPACITY;
+            if (a.out_len) a.out_len[msg] = fits ? o : 0;
+            if (sizes && a.map_out) reinterpret_cast<uint64_t *>(a.map_out)[msg] = bits;  // (tdt_mappings_v)
+        }
+        __syncthreads();  // (the slots of the next message's scans)
     }
 }
 
@@ -498,26 +937,50 @@ __global__ __launch_bounds__(kAnyTeam) void tdt_decode_any_kernel(DecodeArgs a) 
 
 }  // namespace
 
-int launch_encode_any(const EncodeArgs &a, int ws, int mode, hipStream_t s, bool pair) {
+int launch_encode_any(const EncodeArgs &a, int ws, int mode, hipStream_t s, bool pair, const AnyTiledArgs *tiled) {
     if (a.n_msgs == 0) return 0;
     if (pair ? mode != MODE_ENCODE && mode != MODE_SIZES && mode != MODE_MAPPED : mode == MODE_SIZES)
         return (int)hipErrorInvalidValue;
     const dim3 g(a.n_msgs), t(kAnyTeam);
     const uint32_t w = (uint32_t)ws;
-#define PSY_ANY_HP(MODE_, PAIR_)                                                                              \
-    do {                                                                                                      \
-        if (ws <= 8) hipLaunchKernelGGL((tdt_encode_any_kernel<MODE_, 8, PAIR_>), g, t, 0, s, a, w);          \
-        else if (ws <= 16) hipLaunchKernelGGL((tdt_encode_any_kernel<MODE_, 16, PAIR_>), g, t, 0, s, a, w);   \
-        else if (ws <= 32) hipLaunchKernelGGL((tdt_encode_any_kernel<MODE_, 32, PAIR_>), g, t, 0, s, a, w);   \
-        else hipLaunchKernelGGL((tdt_encode_any_kernel<MODE_, 64, PAIR_>), g, t, 0, s, a, w);                 \
+    const uint32_t *mark = nullptr;
+    if (mode == MODE_ANALYZE) tiled = nullptr;
+    if (tiled) {  // the long messages' records and marks first: the kernel below returns at a marked message
+        const dim3 pg((a.n_msgs + 255u) / 256u), pt(256);
+        if (pair) hipLaunchKernelGGL(tdt_any_plan_kernel<true>, pg, pt, 0, s, a, *tiled, w, mode);
+        else hipLaunchKernelGGL(tdt_any_plan_kernel<false>, pg, pt, 0, s, a, *tiled, w, mode);
+        mark = tiled->mark;
+    }
+#define PSY_ANY_HP(MODE_, PAIR_)                                                                                    \
+    do {                                                                                                            \
+        if (ws <= 8) hipLaunchKernelGGL((tdt_encode_any_kernel<MODE_, 8, PAIR_>), g, t, 0, s, a, w, mark);          \
+        else if (ws <= 16) hipLaunchKernelGGL((tdt_encode_any_kernel<MODE_, 16, PAIR_>), g, t, 0, s, a, w, mark);   \
+        else if (ws <= 32) hipLaunchKernelGGL((tdt_encode_any_kernel<MODE_, 32, PAIR_>), g, t, 0, s, a, w, mark);   \
+        else hipLaunchKernelGGL((tdt_encode_any_kernel<MODE_, 64, PAIR_>), g, t, 0, s, a, w, mark);                 \
     } while (0)
     if (pair && mode == MODE_SIZES) PSY_ANY_HP(MODE_SIZES, true);
-    else if (pair && mode == MODE_MAPPED) hipLaunchKernelGGL((tdt_encode_any_kernel<MODE_MAPPED, 1, true>), g, t, 0, s, a, w);
+    else if (pair && mode == MODE_MAPPED) hipLaunchKernelGGL((tdt_encode_any_kernel<MODE_MAPPED, 1, true>), g, t, 0, s, a, w, mark);
     else if (pair) PSY_ANY_HP(MODE_ENCODE, true);
     else if (mode == MODE_ENCODE) PSY_ANY_HP(MODE_ENCODE, false);
     else if (mode == MODE_ANALYZE) PSY_ANY_HP(MODE_ANALYZE, false);
-    else hipLaunchKernelGGL((tdt_encode_any_kernel<MODE_MAPPED, 1>), g, t, 0, s, a, w);
+    else hipLaunchKernelGGL((tdt_encode_any_kernel<MODE_MAPPED, 1>), g, t, 0, s, a, w, mark);
 #undef PSY_ANY_HP
+    if (tiled && tiled->lcap && tiled->tcap) {  // the tile pipeline: fixed grids over the plan's device-side counts
+        const AnyTiledArgs &T = *tiled;
+        const uint32_t grid = T.grid ? T.grid : 1u;
+        const dim3 gl(std::min(grid, T.lcap)), gt(std::min(grid, T.tcap));
+        const dim3 gh(std::min(grid, (T.tcap + kAnySpanTiles - 1) / kAnySpanTiles));
+        if (mode != MODE_MAPPED) {  // (a known mapping is in the record already)
+            if (ws <= 8) hipLaunchKernelGGL(tdt_any_hist_kernel<8>, gh, dim3(kAnyHistTeam), 0, s, T, w);
+            else if (ws <= 16) hipLaunchKernelGGL(tdt_any_hist_kernel<16>, gh, dim3(kAnyHistTeam), 0, s, T, w);
+            else if (ws <= 32) hipLaunchKernelGGL(tdt_any_hist_kernel<32>, gh, dim3(kAnyHistTeam), 0, s, T, w);
+            else hipLaunchKernelGGL(tdt_any_hist_kernel<64>, gh, dim3(kAnyHistTeam), 0, s, T, w);
+            hipLaunchKernelGGL(tdt_any_map_kernel, gl, t, 0, s, T, w);
+        }
+        hipLaunchKernelGGL(tdt_any_tile_kernel<false>, gt, t, 0, s, T, w);
+        hipLaunchKernelGGL(tdt_any_scan_kernel, gl, t, 0, s, a, T, w, mode);
+        if (mode != MODE_SIZES) hipLaunchKernelGGL(tdt_any_tile_kernel<true>, gt, t, 0, s, T, w);
+    }
     return (int)hipGetLastError();
 }
 

@@ -200,6 +200,26 @@ struct PlanWS {
     }
 };
 
+// Workspace of the tiled generic-width encode (tdt_anyws.h), one per context: the calls that use it
+// hold the context's lock.  Budgets as the slotted plan's: a starting budget, the claimed counts in
+// the counter block, the pinned snapshot, growth on a later call with the old buffer retired.
+struct AnyTiledWS {
+    uint8_t *buf = nullptr;  // counters (kPlanCounterBytes) | one mark word per message
+    size_t bytes = 0;
+    uint8_t *rec = nullptr;  // AnyLarge records | AnyTile records | histograms
+    size_t rec_bytes = 0;
+    uint32_t lcap = 0, tcap = 0;
+    CountHist<psy::AnyCount> h;
+    void release() {
+        if (buf) (void)hipFree(buf);
+        if (rec) (void)hipFree(rec);
+        buf = rec = nullptr;
+        bytes = rec_bytes = 0;
+        lcap = tcap = 0;
+        h.release();
+    }
+};
+
 // host pipeline slots (chunks in flight per tdt_encode_host / tdt_decode_host call)
 constexpr int kHostSlots = 4;
 
@@ -289,6 +309,10 @@ struct tdt_ctx {
     uint32_t pack_cut = psy::kPackCut, pack_grid = psy::kPackGridCap;
     uint64_t large_min = 256 * 1024;  // messages (decode: decoded blobs) above this take the tiled path
     uint32_t tile_cap = ~0u;          // lower tile budget (tests)
+    // TDT_OPT_ANY_TILED (PSYNE_TDT_ANY_TILED): generic-width messages above the threshold take the tile
+    // pipeline; off: every one of them on the one-workgroup kernel
+    bool any_tiled = true;
+    AnyTiledWS anyw;
     // diagnostic knobs (read once at tdt_ctx_create from the environment, or tdt_ctx_set_option)
     bool no_side = false;       // PSYNE_TDT_NO_SIDE: no side stream for the tile pipeline
     bool small_main = false;    // PSYNE_TDT_SMALL_MAIN: small lists on the caller's stream
@@ -322,15 +346,17 @@ int ensure_ws(tdt_ctx *c, uint32_t n_msgs, hipStream_t s) {
 bool ws_supported(int ws) { return psy::anyws_tuned(ws) || (PSY_HAVE_ANYWS && psy::anyws_generic(ws)); }
 
 // the generic encode kernel (any word size in 1..64 the tuned kernels do not cover)
-int launch_any_encode(const psy::EncodeArgs &a, int ws, int mode, hipStream_t s, bool pair = false) {
+// (tiled: the tile pipeline's workspace for the long messages, any_tiled_begin below; null: none)
+int launch_any_encode(const psy::EncodeArgs &a, int ws, int mode, hipStream_t s, bool pair = false,
+                      const psy::AnyTiledArgs *tiled = nullptr) {
 #if PSY_HAVE_ANYWS
     if (psy::anyws_generic(ws)) {
-        const int e = psy::launch_encode_any(a, ws, mode, s, pair);
+        const int e = psy::launch_encode_any(a, ws, mode, s, pair, tiled);
         if (e) return set_err(TDT_E_HIP, std::string("generic encode launch: ") + hipGetErrorString((hipError_t)e));
         return TDT_OK;
     }
 #endif
-    (void)a, (void)mode, (void)s, (void)ws, (void)pair;
+    (void)a, (void)mode, (void)s, (void)ws, (void)pair, (void)tiled;
     return set_err(TDT_E_UNSUPPORTED, "word_size not supported on the GPU path");
 }
 // the follow-up launch of a decode call: the blobs of a generic word size its kernels deferred
@@ -642,6 +668,77 @@ int ensure_elarge(PlanWS &w, int ws, hipStream_t s) {
     return TDT_OK;
 }
 
+// ---------------------------------------------------------------------------------------
+// The tiled generic-width encode's workspace (AnyTiledWS; the kernels: tdt_anyws.h).  A call that
+// may launch the generic encode brackets it: any_tiled_begin (grows the buffers, zeroes the
+// counters, fills the kernels' arguments), the pair tables with AnyTiled::bytes as their byte
+// counter, launch_any_encode(..., AnyTiled::args()), any_tiled_end (the counters → the pinned
+// snapshot).  The host reads nothing back: the next call sizes the budgets from the snapshot.
+constexpr uint32_t kAnyL0 = 64, kAnyLmax = 4096;         // large messages per batch: the start, the full budget (64 KiB of histogram each)
+constexpr uint32_t kAnyT0 = 8192, kAnyTmax = 1u << 20;   // tiles per batch: 512 MiB of long messages, 64 GiB
+struct AnyRecLayout { size_t tiles, hist, bytes; };      // (the AnyLarge records at 0)
+AnyRecLayout any_rec_layout(uint32_t lcap, uint32_t tcap) {
+    const size_t tiles = (size_t)lcap * sizeof(psy::AnyLarge), hist = tiles + (size_t)tcap * sizeof(psy::AnyTile);
+    return {tiles, hist, hist + (size_t)lcap * psy::kAnyWsMax * 256 * sizeof(uint32_t)};
+}
+struct AnyTiled {
+    psy::AnyTiledArgs t{};
+    bool on = false;
+    // the byte counter of a pair-table batch (`route`: the width's index in a mixed-width call)
+    unsigned long long *bytes(int route = 0) const { return on ? t.cnt + psy::AC_BYTES + route : nullptr; }
+    const psy::AnyTiledArgs *args(int route = 0) {
+        t.bytes_at = (uint32_t)(psy::AC_BYTES + route);
+        return on ? &t : nullptr;
+    }
+};
+// own: the call holds the context's lock (a host-pipeline slot does not: its messages stay untiled)
+int any_tiled_begin(tdt_ctx *c, bool own, uint32_t n, hipStream_t s, AnyTiled &x) {
+    x = AnyTiled{};
+    if (!PSY_HAVE_ANYWS || !own || !c->any_tiled || n == 0) return TDT_OK;
+    AnyTiledWS &w = c->anyw;
+    const bool cap = capturing(s);
+    auto &H = w.h;
+    if (!cap) H.refresh();  // (event queries are not capturable)
+    const size_t need = psy::kPlanCounterBytes + 4ull * n;
+    if (int st = grow_retiring(w.buf, w.bytes, need, psy::cap_double(need, w.bytes), c->retired, s)) return st;
+    // the tile pipeline is off when an earlier plan found no long message (its launches would find none)
+    const bool tiles_on = !H.valid || H[psy::AC_LARGE] > 0;
+    if (tiles_on) {
+        uint32_t lc = w.lcap ? w.lcap : kAnyL0, tc = w.tcap ? w.tcap : kAnyT0;
+        if (H.valid) {  // what an earlier plan claimed, beyond its budget too
+            lc = std::max(lc, pow2_at_least(H[psy::AC_LARGE], kAnyL0, kAnyLmax));
+            tc = std::max(tc, pow2_at_least(H[psy::AC_TILES], kAnyT0, kAnyTmax));
+        }
+        if (lc != w.lcap || tc != w.tcap) {
+            if (int st = no_growth_in_capture(s)) return st;
+            const AnyRecLayout RL = any_rec_layout(lc, tc);
+            w.lcap = w.tcap = 0;
+            // (retired, not freed: calls still queued, or a captured graph, may use the old records)
+            if (int st = psy::grow(w.rec, w.rec_bytes, RL.bytes, RL.bytes, retire_to(c->retired), DevAlloc{})) return st;
+            HIPCHK(hipMemsetAsync(w.rec, 0, RL.bytes, s));  // (the histograms are zero between calls)
+            w.lcap = lc;
+            w.tcap = tc;
+        }
+    }
+    HIPCHK(hipMemsetAsync(w.buf, 0, psy::kPlanSnapBytes, s));
+    const AnyRecLayout RL = any_rec_layout(w.lcap, w.tcap);
+    x.on = true;
+    x.t.large = reinterpret_cast<psy::AnyLarge *>(w.rec);
+    x.t.tiles = reinterpret_cast<psy::AnyTile *>(w.rec + RL.tiles);
+    x.t.hist = reinterpret_cast<uint32_t *>(w.rec + RL.hist);
+    x.t.mark = reinterpret_cast<uint32_t *>(w.buf + psy::kPlanCounterBytes);
+    x.t.cnt = reinterpret_cast<unsigned long long *>(w.buf);
+    x.t.lcap = tiles_on && w.rec ? w.lcap : 0u;
+    x.t.tcap = tiles_on && w.rec ? std::min(w.tcap, std::max(c->tile_cap, 1u)) : 0u;
+    x.t.grid = (uint32_t)c->cus * 8u;
+    x.t.large_min = c->large_min;
+    return TDT_OK;
+}
+int any_tiled_end(tdt_ctx *c, const AnyTiled &x, uint32_t n, hipStream_t s) {
+    if (!x.on || capturing(s)) return TDT_OK;
+    return record_counts(c->anyw.h, c->anyw.buf, n, s);
+}
+
 // grid of one list-driven launch of TEAM-lane workgroups over `count` entries (launches of
 // < 2^32 threads each)
 template <class F>
@@ -879,12 +976,15 @@ int launch_slotted_any(tdt_ctx *c, PlanWS &pw, psy::EncodeArgs a, hipStream_t s,
                         : launch_slotted<W()>(c, pw, a, s);
         }))
         return st;
-    // generic widths: one workgroup per message, message id = block index, no plan
+    // generic widths: one workgroup per message, message id = block index; the long ones as tiles
+    AnyTiled x;
+    if (psy::anyws_generic(c->cfg.word_size) && (st = any_tiled_begin(c, &pw == &c->pw, a.n_msgs, s, x))) return st;
     if (v && psy::anyws_generic(c->cfg.word_size)) {  // (the plan buffer holds the pair tables alone)
         if ((st = ensure_plan(pw, a.n_msgs, s, true))) return st;
-        if ((st = launch_table(pw, *v, a.n_msgs, true, nullptr, a.in_off, a.slot_off, s))) return st;
+        if ((st = launch_table(pw, *v, a.n_msgs, true, x.bytes(), a.in_off, a.slot_off, s))) return st;
     }
-    return launch_any_encode(a, c->cfg.word_size, mapped ? psy::MODE_MAPPED : psy::MODE_ENCODE, s, v != nullptr);
+    st = launch_any_encode(a, c->cfg.word_size, mapped ? psy::MODE_MAPPED : psy::MODE_ENCODE, s, v != nullptr, x.args());
+    return st ? st : any_tiled_end(c, x, a.n_msgs, s);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1010,6 +1110,8 @@ int encode_mixed(tdt_ctx *c, const Scatter &v, const int32_t *d_word_size, uint6
     // the workspaces: the tables of every width, and a plan buffer per tuned width
     st = grow_retiring(c->mx_tab, c->mx_bytes, R.bytes, psy::cap_double(R.bytes, c->mx_bytes), c->retired, s);
     if (st) return st;
+    AnyTiled x;  // the generic widths of the call share one workspace: a byte counter each, one pool of records
+    if (R.n_generic && (st = any_tiled_begin(c, true, n, s, x))) return st;
     RouteArgs t{};
     t.v = v;
     t.ws = d_word_size;
@@ -1024,6 +1126,7 @@ int encode_mixed(tdt_ctx *c, const Scatter &v, const int32_t *d_word_size, uint6
         t.out_pair[k] = reinterpret_cast<ulonglong2 *>(c->mx_tab + q.pair[psy::PT_OUT]);
         if (!q.tuned) {
             if (!(PSY_HAVE_ANYWS)) return set_err(TDT_E_UNSUPPORTED, "this build holds no generic-width kernels");
+            t.bytes[k] = x.bytes(k);
             continue;
         }
         if (!with_word_size(q.ws, [](auto) {})) return set_err(TDT_E_UNSUPPORTED, "this build holds word size 4 only");
@@ -1060,10 +1163,11 @@ int encode_mixed(tdt_ctx *c, const Scatter &v, const int32_t *d_word_size, uint6
             psy::EncodeArgs g = a;
             g.in_off = r.in_pair;
             g.slot_off = mode == psy::MODE_SIZES ? nullptr : r.out_pair;
-            st = launch_any_encode(g, q.ws, mode, s, true);
+            st = launch_any_encode(g, q.ws, mode, s, true, x.args(k));
         }
         if (st) return st;
     }
+    if ((st = any_tiled_end(c, x, n, s))) return st;
     HIPCHK(hipGetLastError());
     return TDT_OK;
 }
@@ -1098,8 +1202,9 @@ bool lb_small_teams(tdt_ctx *c, hipStream_t s) {
 
 // small_teams: -1 from the context's history, 0 message-sized teams, 1 one-wave teams, 2
 // message-sized resident-only teams (see launch_encode_ws)
+// own: the call holds the context's lock (any_tiled_begin)
 template <int MODE, int LB>
-int launch_encode(tdt_ctx *c, psy::EncodeArgs a, hipStream_t s, int small_teams) {
+int launch_encode(tdt_ctx *c, psy::EncodeArgs a, hipStream_t s, int small_teams, bool own = false) {
     const bool small = small_teams < 0 ? lb_small_teams(c, s) : small_teams == 1;
     const bool res = small_teams == 2;
     int st = TDT_OK;
@@ -1109,7 +1214,11 @@ int launch_encode(tdt_ctx *c, psy::EncodeArgs a, hipStream_t s, int small_teams)
     // two-phase route, encode_two_phase_any)
     if (MODE != psy::MODE_ANALYZE && !a.slot_off && psy::anyws_generic(c->cfg.word_size))
         return set_err(TDT_E_UNSUPPORTED, "compacted one-pass encode needs word_size 1, 2, 4, 8 or 16");
-    return launch_any_encode(a, c->cfg.word_size, MODE, s);
+    AnyTiled x;
+    if (MODE != psy::MODE_ANALYZE && psy::anyws_generic(c->cfg.word_size) && (st = any_tiled_begin(c, own, a.n_msgs, s, x)))
+        return st;
+    st = launch_any_encode(a, c->cfg.word_size, MODE, s, false, x.args());
+    return st ? st : any_tiled_end(c, x, a.n_msgs, s);
 }
 
 // Zero the counters + look-back words of a batch; `wsp` = an explicit workspace (host
@@ -1152,10 +1261,10 @@ int encode_common(tdt_ctx *c, int mode, psy::EncodeArgs a, const Where &w) {
     wire_encode(c, a, wsp);
     if (mode == psy::MODE_ENCODE) {
         st = slotted ? launch_slotted_any(c, w.pws ? *w.pws : c->pw, a, s, v)
-                     : launch_encode<psy::MODE_ENCODE, 1>(c, a, s, w.small_teams);
+                     : launch_encode<psy::MODE_ENCODE, 1>(c, a, s, w.small_teams, !w.wsp);
     } else if (mode == psy::MODE_MAPPED) {
         st = v ? launch_slotted_any(c, w.pws ? *w.pws : c->pw, a, s, v, true)
-               : launch_encode<psy::MODE_MAPPED, 1>(c, a, s, w.small_teams);
+               : launch_encode<psy::MODE_MAPPED, 1>(c, a, s, w.small_teams, !w.wsp);
     } else {
         st = launch_encode<psy::MODE_ANALYZE, 1>(c, a, s, w.small_teams);
     }
@@ -1190,12 +1299,15 @@ int encoded_sizes_one(tdt_ctx *c, const Scatter *v, const Contig *g, uint32_t n,
         })) {
         // generic widths: one workgroup per message, no plan (the plan buffer holds the input table alone)
         if (!psy::anyws_generic(c->cfg.word_size)) return set_err(TDT_E_UNSUPPORTED, "word_size not supported on the GPU path");
+        AnyTiled x;
+        if ((st = any_tiled_begin(c, true, n, s, x))) return st;
         if ((st = ensure_plan(c->pw, n, s, true))) return st;
-        st = g ? launch_offsets_table(c->pw, *g, n, nullptr, a.in_off, s)
-               : launch_table(c->pw, *v, n, true, nullptr, a.in_off, a.slot_off, s);
+        st = g ? launch_offsets_table(c->pw, *g, n, x.bytes(), a.in_off, s)
+               : launch_table(c->pw, *v, n, true, x.bytes(), a.in_off, a.slot_off, s);
         if (st) return st;
         a.slot_off = nullptr;
-        st = launch_any_encode(a, c->cfg.word_size, psy::MODE_SIZES, s, true);
+        st = launch_any_encode(a, c->cfg.word_size, psy::MODE_SIZES, s, true, x.args());
+        if (!st) st = any_tiled_end(c, x, n, s);
     }
     if (st) return st;
     HIPCHK(hipGetLastError());
@@ -2268,6 +2380,7 @@ int tdt_ctx_create(int device, const tdt_config *cfg, tdt_ctx **out) {
     // tiled-path threshold, a lower tile budget (fallback tests), the diagnostic stream knobs
     if (const char *e = std::getenv("PSYNE_TDT_LARGE_MIN")) x->large_min = std::strtoull(e, nullptr, 10);
     if (const char *e = std::getenv("PSYNE_TDT_TILE_CAP")) x->tile_cap = (uint32_t)std::strtoul(e, nullptr, 10);
+    if (const char *e = std::getenv("PSYNE_TDT_ANY_TILED")) x->any_tiled = *e != '0';
     auto flag = [](const char *name) {
         const char *e = std::getenv(name);
         return e && *e == '1';
@@ -2310,6 +2423,7 @@ void tdt_ctx_destroy(tdt_ctx *ctx) {
     for (void *p : ctx->retired) (void)hipFree(p);
     for (void *p : ctx->retired_host) (void)hipHostFree(p);
     ctx->pw.release();
+    ctx->anyw.release();
     for (auto &w : ctx->mx_pw)
         if (w) w->release();
     if (ctx->one_stream) (void)hipStreamSynchronize(ctx->one_stream);
@@ -2369,6 +2483,7 @@ int tdt_ctx_set_option(tdt_ctx *ctx, int option, uint64_t value) {
         case TDT_OPT_SMALL_ON_CALLER_STREAM: ctx->small_main = value != 0; return TDT_OK;
         case TDT_OPT_NO_TWO_PHASE: ctx->no_two_phase = value != 0; return TDT_OK;
         case TDT_OPT_PACK_SIZES_FIRST: ctx->pack_sizes_first = value == 2 ? 2 : value != 0 ? 1 : 0; return TDT_OK;
+        case TDT_OPT_ANY_TILED: ctx->any_tiled = value != 0; return TDT_OK;
     }
     return set_err(TDT_E_ARG, "unknown option");
 }

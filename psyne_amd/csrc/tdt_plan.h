@@ -38,9 +38,18 @@ enum DecCount : int {
     DC_DEFERRED = 15     // blobs of a generic word size the class kernels deferred (the highest)
 };
 
+// The tiled generic-width encode (tdt_anyws.h) keeps a counter block of its own, one per context.
+// A mixed-width call zeroes it once and every generic width of the call claims from it in turn.
+enum AnyCount : int {
+    AC_LARGE = 0,        // large-message records claimed (beyond the budget too: the next call grows it)
+    AC_TILES = 1,        // tile records claimed (likewise)
+    AC_BYTES = 2         // pair tables: the sum of the message sizes; a mixed-width call: AC_BYTES + route index
+};
+
 // u32 view of the block: index of a counter's low word (the only place the two units meet)
 constexpr int lo32(EncCount k) { return 2 * (int)k; }
 constexpr int lo32(DecCount k) { return 2 * (int)k; }
+constexpr int lo32(AnyCount k) { return 2 * (int)k; }
 
 constexpr size_t kPlanCounterBytes = 256;  // the block
 constexpr size_t kPlanSnapBytes = 128;     // zeroed per call and copied to the host's snapshot
@@ -95,6 +104,7 @@ constexpr uint64_t kAbsentBegin = ~0ull, kAbsentEnd = 0;
 constexpr bool pair_absent(uint64_t begin, uint64_t end) { return begin == kAbsentBegin && end == kAbsentEnd; }
 
 constexpr int kMixedMaxWidths = 8;  // widths per call (TDT_MIXED_MAX_WIDTHS): the workspace and launch bound
+static_assert(8 * (AC_BYTES + kMixedMaxWidths) <= kPlanSnapBytes, "one byte counter per width of a mixed call");
 constexpr int kMixedWsMax = 64;     // widest record (kAnyWsMax)
 constexpr bool mixed_tuned(int ws) { return ws == 1 || ws == 2 || ws == 4 || ws == 8 || ws == 16; }
 

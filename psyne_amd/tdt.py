@@ -637,7 +637,9 @@ class TdtCodec:
         return int(fl.value)
 
     def set_option(self, option: int, value: int):
-        """tdt_ctx_set_option (tuning / diagnostic knobs; results are the same bytes)."""
+        """tdt_ctx_set_option (tuning / diagnostic knobs; results are the same bytes): the TDT_OPT_*
+        values of psyne_amd._lib.  TDT_OPT_LARGE_MIN and TDT_OPT_TILE_CAP govern the tiled paths of every
+        word size; TDT_OPT_ANY_TILED = 0 keeps every generic-width message on one workgroup."""
         check(self._lib.tdt_ctx_set_option(self._h, option, int(value)))
 
     # ---- host path (socket buffers) -------------------------------------------------------
