@@ -94,8 +94,9 @@ def guarded_output(nbytes, phase):
     return t, t[lead:lead + nbytes], lead
 
 
-def compare(exp, got_st, got_len, region, bad, tag):
-    """region(i) → the bytes the route gave case i, GAP guard bytes behind them included."""
+def compare(exp, got_st, got_len, region, bad, tag, where=None):
+    """region(i) → the bytes the route gave case i, GAP guard bytes behind them included.
+    where(e, at) → optional words on where byte `at` of case e's output lies."""
     for i, e in enumerate(exp):
         if int(got_st[i]) != e.status:
             bad.append("%s %s: status %d, expected %d" % (tag, e.name, got_st[i], e.status))
@@ -106,13 +107,14 @@ def compare(exp, got_st, got_len, region, bad, tag):
         r = region(i)
         if r[: e.size].tobytes() != e.out:
             diff = np.flatnonzero(r[: e.size] != np.frombuffer(e.out, np.uint8))
-            bad.append("%s %s: %d bytes differ, the first at %d" % (tag, e.name, diff.size, diff[0]))
+            bad.append("%s %s: %d bytes differ, the first at %d%s" % (tag, e.name, diff.size, diff[0],
+                                                                      " (%s)" % where(e, int(diff[0])) if where else ""))
         elif not (r[e.size:] == GUARD).all():
             bad.append("%s %s: wrote past its %d bytes" % (tag, e.name, e.size))
 
 
 # ------------------------------------------------------------------ a, b: slotted, two thresholds
-def run_slotted(codec, exp, in_phase, out_phase, tag, bad):
+def run_slotted(codec, exp, in_phase, out_phase, tag, bad, where=None):
     n = len(exp)
     d, o, _ = packed_input(exp, in_phase)
     sizes = np.array([e.size for e in exp], np.int64)
@@ -123,7 +125,7 @@ def run_slotted(codec, exp, in_phase, out_phase, tag, bad):
     torch.cuda.synchronize()
     h = whole.cpu().numpy()
     st, ln = st.cpu().numpy()[:n], ln.cpu().numpy()[:n]
-    compare(exp, st, ln, lambda i: h[lead + slots[i]:lead + slots[i + 1]], bad, tag)
+    compare(exp, st, ln, lambda i: h[lead + slots[i]:lead + slots[i + 1]], bad, tag, where)
     if not ((h[:lead] == GUARD).all() and (h[lead + slots[-1]:] == GUARD).all()):
         bad.append("%s: wrote outside the output buffer" % tag)
     return h[lead:lead + slots[-1]].copy(), st, ln

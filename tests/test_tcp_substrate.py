@@ -4,6 +4,7 @@ of the reference's benchmarks/tcp_tdt_benchmark.cpp) and the C++ decorator test
 tests/cpp/test_substrate (oversized-claim rejection, per-frame batch statuses)."""
 import json
 import pathlib
+import socket
 import subprocess
 
 import numpy as np
@@ -21,6 +22,15 @@ def run(*args, timeout=120):
     p = subprocess.run([str(BIN), *args], capture_output=True, text=True, timeout=timeout)
     assert p.returncode == 0, p.stderr + p.stdout
     return json.loads(p.stdout.strip().splitlines()[-1])
+
+
+def free_port() -> str:
+    """A loopback port nobody listens on.  The CPU tests take one per run instead of a fixed number:
+    two runs of this file on one host at the same time (two checkouts, two users) otherwise meet on
+    the same port, and one of them connects to the other's listener or fails to bind."""
+    with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
+        s.bind(("127.0.0.1", 0))
+        return str(s.getsockname()[1])
 
 
 def read_frames(path):
@@ -46,7 +56,7 @@ def check_frames_vs_oracle(dump, count, floats):
 
 def test_framing_passthrough_loopback():
     # no codec: u32-length frames over 127.0.0.1 (tcp_simple.hpp:68-150), byte-exact
-    r = run("--codec", "none", "--count", "64", "--floats", "16384", "--batch", "8", "--port", "18181")
+    r = run("--codec", "none", "--count", "64", "--floats", "16384", "--batch", "8", "--port", free_port())
     assert r["mismatches"] == 0 and r["tensors"] == 64
     assert abs(r["compression_ratio"] - 1.0) < 1e-9
 
@@ -54,7 +64,7 @@ def test_framing_passthrough_loopback():
 def test_framing_passthrough_two_processes():
     # --procs 2: the receiving end in a forked child (its own process, as the far host's end would
     # be); the child's end time and mismatch count come back through a pipe
-    r = run("--codec", "none", "--count", "64", "--floats", "16384", "--batch", "8", "--port", "18185",
+    r = run("--codec", "none", "--count", "64", "--floats", "16384", "--batch", "8", "--port", free_port(),
             "--procs", "2")
     assert r["mismatches"] == 0 and r["tensors"] == 64 and r["procs"] == 2
     assert r["seconds"] > 0
@@ -65,7 +75,7 @@ def test_reference_codec_loopback(tmp_path):
     # blobs are the oracle's (the oracle is pinned against this library)
     if not REF_LIB.exists():
         pytest.skip("oracle/_ref not built (make -C oracle ref; needs /root/reference)")
-    r = run("--codec", "cpu", "--count", "12", "--floats", "16384", "--batch", "4", "--port", "18183",
+    r = run("--codec", "cpu", "--count", "12", "--floats", "16384", "--batch", "4", "--port", free_port(),
             "--dump", str(tmp_path))
     assert r["mismatches"] == 0 and r["compression_ratio"] > 1.1
     check_frames_vs_oracle(tmp_path, 12, 16384)
