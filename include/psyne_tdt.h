@@ -412,7 +412,7 @@ int tdt_ctx_error_flags(tdt_ctx *ctx, void *hip_stream, uint32_t *flags);
 
 /* Tuning / diagnostic options (tdt_ctx_create reads the same from the environment once:
  * PSYNE_TDT_LARGE_MIN, PSYNE_TDT_TILE_CAP, PSYNE_TDT_NO_SIDE, PSYNE_TDT_SMALL_MAIN,
- * PSYNE_TDT_NO_TWO_PHASE, PSYNE_TDT_COPY_THREADS, PSYNE_TDT_ANY_TILED).  Not needed for correct results: every setting encodes and decodes
+ * PSYNE_TDT_NO_TWO_PHASE, PSYNE_TDT_COPY_THREADS, PSYNE_TDT_ANY_TILED, PSYNE_TDT_ANY_DEC_TILED).  Not needed for correct results: every setting encodes and decodes
  * the same bytes. */
 #define TDT_OPT_LARGE_MIN 1               /* messages above this many bytes take the tiled path (every word size:
                                              the tuned widths' tiles and the generic widths' alike) */
@@ -430,7 +430,26 @@ int tdt_ctx_error_flags(tdt_ctx *ctx, void *hip_stream, uint32_t *flags);
                                              are encoded as 64 KiB tiles over the whole device (default 1);
                                              0: every such message on one workgroup.  The A/B switch: the
                                              same bytes, lengths and statuses either way */
+#define TDT_OPT_ANY_DEC_TILED 9           /* word sizes other than 1, 2, 4, 8, 16: blobs that decode to more than
+                                             the tiled-path threshold (max(TDT_OPT_LARGE_MIN, 1/4096 of the
+                                             batch's blob bytes)), with one or two referenced streams, are
+                                             decoded as 32 KiB output tiles over the whole device (default 1);
+                                             0: every such blob on one workgroup.  The A/B switch: the same
+                                             bytes, lengths and statuses either way */
 int tdt_ctx_set_option(tdt_ctx *ctx, int option, uint64_t value);
+
+/* Read-only counters of the context (tests and tools: which path a call took).  The claims are those
+ * of the most recent call that ran the generic-width decode's plan and whose snapshot has landed — valid
+ * after the device (or the call's stream) has been synchronised; claims are counted beyond the budgets
+ * too, so a claim above its budget means that some blob fell back to one workgroup.  Until a call of
+ * the context has met a blob of such a width no plan runs (the call after the first such one is the
+ * first to be tiled); those calls leave the claims unchanged, as do the host pipeline's.  Returns TDT_E_ARG for an unknown `stat`. */
+#define TDT_STAT_ANY_DEC_LARGE 1          /* long generic-width blobs the decode plan claimed records for */
+#define TDT_STAT_ANY_DEC_BLOCKS 2         /* 2,048-pair block sums it claimed */
+#define TDT_STAT_ANY_DEC_TILES 3          /* 32 KiB output tiles it claimed */
+#define TDT_STAT_ANY_DEC_BUDGET_LARGE 4   /* the current budgets: long-blob records ... */
+#define TDT_STAT_ANY_DEC_BUDGET_TILES 5   /* ... and tiles (before TDT_OPT_TILE_CAP) */
+int tdt_ctx_get_stat(tdt_ctx *ctx, int stat, uint64_t *value);
 
 /* Host-memory analyze (analyze_data :206-222): h_entropy n*ws doubles, h_mapping n*ws int32
  * (either may be NULL).  Blocks the calling thread. */

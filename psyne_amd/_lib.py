@@ -18,6 +18,13 @@ TDT_OPT_LARGE_MIN, TDT_OPT_TILE_CAP, TDT_OPT_NO_SIDE_STREAM = 1, 2, 3
 TDT_OPT_SMALL_ON_CALLER_STREAM, TDT_OPT_NO_TWO_PHASE, TDT_OPT_COPY_THREADS = 4, 5, 6
 TDT_OPT_PACK_SIZES_FIRST = 7
 TDT_OPT_ANY_TILED = 8  # generic word sizes: long messages as tiles (default 1); 0: one workgroup per message
+TDT_OPT_ANY_DEC_TILED = 9  # generic word sizes: long blobs decoded as 32 KiB tiles (default 1); 0: one workgroup per blob
+# tdt_ctx_get_stat: the generic-width decode plan's claims of the last call whose snapshot landed, and the budgets
+TDT_STAT_ANY_DEC_LARGE, TDT_STAT_ANY_DEC_BLOCKS, TDT_STAT_ANY_DEC_TILES = 1, 2, 3
+TDT_STAT_ANY_DEC_BUDGET_LARGE, TDT_STAT_ANY_DEC_BUDGET_TILES = 4, 5
+STATS = {"ANY_DEC_LARGE": TDT_STAT_ANY_DEC_LARGE, "ANY_DEC_BLOCKS": TDT_STAT_ANY_DEC_BLOCKS,
+         "ANY_DEC_TILES": TDT_STAT_ANY_DEC_TILES, "ANY_DEC_BUDGET_LARGE": TDT_STAT_ANY_DEC_BUDGET_LARGE,
+         "ANY_DEC_BUDGET_TILES": TDT_STAT_ANY_DEC_BUDGET_TILES}
 
 
 class TdtConfigC(C.Structure):
@@ -73,6 +80,7 @@ SIGNATURES = {
     "tdt_analyze_host": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp]),
     "tdt_ctx_error_flags": (C.c_int, [_vp, _vp, C.POINTER(C.c_uint32)]),
     "tdt_ctx_set_option": (C.c_int, [_vp, C.c_int, C.c_uint64]),
+    "tdt_ctx_get_stat": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_uint64)]),
     "tdt_last_error": (C.c_char_p, []),
     "tdt_status_string": (C.c_char_p, [C.c_int]),
 }

@@ -13,13 +13,17 @@
 //   decode   blobs whose header carries a generic width are DEFERRED by the tuned decode kernels
 //            (blob_check returns ST_DEFER, the kernel appends the blob id to a device list); one
 //            follow-up launch, grid-strided over the device-side count, decodes the listed blobs.
-//            A batch without such blobs pays that one near-empty launch.
+//            A batch without such blobs pays that one near-empty launch.  A deferred blob that
+//            decodes to more than the batch's large-blob threshold, with one or two referenced
+//            streams, leaves that launch for the decode tile pipeline below (32 KiB output tiles).
 //
 // Reference: include/psyne/protocol/tdt_compression.hpp (line numbers as in tdt_encode.h /
 // tdt_decode.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "tdt_anyws_dec_tiles.h"
 
 namespace psy {
 
@@ -30,6 +34,7 @@ constexpr int kAnyWsMax = 64;           // largest word size the library encodes
 constexpr int kAnyTeam = 256;           // lanes per workgroup of both kernels
 constexpr uint32_t kAnyChunk = 4096;    // encode: message bytes per split + RLE chunk (16 per lane)
 constexpr uint32_t kAnyDecPairs = 2048; // decode: pairs per chunk (8 per lane)
+static_assert(kAnyDecPairs == kAnyDecBlockPairs, "a block of the tiled decode is one chunk of pairs");
 constexpr uint32_t kAnyTile = 65536;    // tiled encode: message bytes per tile
 constexpr uint32_t kAnySpanTiles = 8;   // tiled encode: tile records per histogram workgroup (512 KiB spans)
 static_assert(kAnyTile % kAnyChunk == 0, "a tile is a whole number of chunks");
@@ -102,9 +107,57 @@ struct AnyTiledArgs {
 int launch_encode_any(const EncodeArgs &a, int ws, int mode, hipStream_t s, bool pair = false,
                       const AnyTiledArgs *tiled = nullptr);
 
+// ---- the tiled decode of long blobs --------------------------------------------------------
+// A deferred blob that decodes to more than the batch's large-blob threshold (the tuned decode
+// plan's rule: max(large_min, 1/4096 of the batch's blob bytes)), fits its slot (the look-back
+// route: out_cap) and has one or two referenced streams — any number of stored ones, any mapping
+// shape, mapping_size >= ws — leaves the one-workgroup kernel (the arithmetic: tdt_anyws_dec_tiles.h):
+//   plan    one lane per entry of the deferred list: parses the header and the stream table, claims
+//           an AnyDecLarge record, ceil(np_r / 2048) block sums per referenced stream and
+//           ceil(wc / Tw) tiles from the budgets below, writes the blob's status and length and
+//           sets the entry's mark; tdt_decode_any_kernel skips a marked entry
+//   blocks  one wave per 2,048-pair block: the sum of its counts
+//   scan    one workgroup per long blob: per stream the exclusive prefix of the block sums, in
+//           place, clamped at the stream's share of the output
+//   tile    one workgroup per 32 KiB output tile: per stream a search of the prefix for the tile's
+//           first block, the chunk loop of the one-workgroup kernel from there with every pair cut
+//           to the tile, expanded into the stream's plane in LDS (zeroed first); then the planes
+//           are recombined through the mapping's rank table, 16 output bytes per lane and store
+// Every launch but the plan is a fixed grid striding over the device-side counts.  A blob that finds
+// a budget spent, does not fit or has three or more referenced streams stays unmarked: the
+// one-workgroup kernel decodes it (or reports it) as before.  The output bytes are that kernel's.
+struct AnyDecLarge {
+    const uint8_t *blob;  // the blob, and its length (every load is bounded by it)
+    uint64_t len;
+    uint8_t *dst;         // where it decodes to
+    uint32_t orig, ws;    // decoded size, word size (0: a claim that found a budget spent — no launch's record)
+    uint32_t tile0, ntiles;
+    uint32_t soff[2], np[2];  // per referenced stream: the pairs' offset in the blob, how many
+    uint32_t k[2];            // positions per word (k[1] = 0: one referenced stream)
+    uint32_t blk0[2], nb[2];  // its block sums [blk0, blk0 + nb); blk0[1] = blk0[0] + nb[0]
+    // the mapping's rank table: byte position p of a word is byte (rank[p] & 63) of its stream's k
+    // bytes of that word — the inverse of the stream's position table; bit 7: the second stream
+    uint8_t rank[kAnyWsMax];
+};
+constexpr uint32_t kAnyDecSecond = 0x80u;
+struct AnyDecArgs {
+    AnyDecLarge *large;
+    uint32_t *bsum;            // block sums, then (the scan) their clamped exclusive prefixes
+    uint32_t *mark;            // one word per entry of the deferred list: non-zero = the tile pipeline has it
+    unsigned long long *cnt;   // the counter block (AnyDecCount, tdt_plan.h)
+    const unsigned long long *batch_bytes;  // pair tables: the counter that holds the batch's blob bytes
+    uint32_t lcap, bcap, tcap; // the budgets of this call (0: nothing is tiled, claims are still counted)
+    uint32_t grid;             // workgroups of a tile-level launch
+    uint64_t large_min;
+};
+
 // Decode the blobs listed in a.dlist[0 .. *a.dcount) (slotted: a.slot_off; compacted: the
 // a.out_off the look-back kernel wrote, against a.out_cap); `grid` workgroups stride over them.
 // pair: a.slot_off is a scattered batch's pair table.
-int launch_decode_any(const DecodeArgs &a, uint32_t grid, hipStream_t s, bool pair = false);
+// tiled: the plan kernel and the tile pipeline run beside the one-workgroup kernel (with budgets of
+// 0 the plan alone, counting); null: every blob on the one-workgroup kernel.  seen (may be null):
+// pinned, where the one-workgroup kernel leaves the length of a list that is not empty (0 until then).
+int launch_decode_any(const DecodeArgs &a, uint32_t grid, hipStream_t s, bool pair = false,
+                      const AnyDecArgs *tiled = nullptr, uint32_t *seen = nullptr);
 
 }  // namespace psy

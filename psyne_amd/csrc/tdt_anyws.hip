@@ -820,15 +820,20 @@ __global__ __launch_bounds__(kAnyTeam) void tdt_any_scan_kernel(EncodeArgs a, An
 // and at least one whole word.  Every output byte is written exactly once: by the pair that
 // covers it, or as zero (a stream shorter than its share of the words, the bytes past the
 // last whole word: recombine_byte_streams :614-637 over its zero-initialised result).
+// mark (null: none): a non-zero word = the list entry belongs to the decode tile pipeline below.
+// seen (null: none): pinned memory for the next call's host — the length of the last list that was not empty.
 template <bool PAIR = false>
-__global__ __launch_bounds__(kAnyTeam) void tdt_decode_any_kernel(DecodeArgs a) {
+__global__ __launch_bounds__(kAnyTeam) void tdt_decode_any_kernel(DecodeArgs a, const uint32_t *mark, uint32_t *seen) {
     __shared__ uint32_t s_map[kAnyWsMax], s_soff[kAnyWsMax], s_slen[kAnyWsMax], s_ptab[kAnyWsMax];
     __shared__ uint32_t s_slots[2][kAW];
     const uint32_t tid = threadIdx.x, lane = (uint32_t)lane_id();
     const uint32_t listed = __builtin_amdgcn_readfirstlane(*a.dcount);
     const uint32_t cnt = listed < a.n_msgs ? listed : a.n_msgs;
+    // (sticky: a context that has listed a blob once keeps its plan; an unknown word (~0) takes the first length)
+    if (seen && blockIdx.x == 0 && tid == 0 && (listed || *seen == ~0u)) *seen = listed;
     for (uint32_t it = blockIdx.x; it < cnt; it += gridDim.x) {
         if (it != blockIdx.x) __syncthreads();
+        if (mark && mark[it]) continue;  // (uniform) a long blob: the tile pipeline's
         const uint32_t msg = a.dlist[it];
         const uint64_t boff = a.in_off[msg];
         const uint64_t len = a.in_len ? a.in_len[msg] : a.in_off[msg + 1] - boff;
@@ -935,6 +940,302 @@ __global__ __launch_bounds__(kAnyTeam) void tdt_decode_any_kernel(DecodeArgs a) 
     }
 }
 
+// ---------------------------------------------------------------------------------------
+// The tiled decode of long blobs (tdt_anyws.h; the arithmetic: tdt_anyws_dec_tiles.h).  Every
+// kernel below but the plan runs a fixed grid striding over what the plan claimed.
+
+// what the plan claimed, within the budgets it ran with
+__device__ __forceinline__ uint32_t anyd_claimed(const AnyDecArgs &t, AnyDecCount k, uint32_t cap) {
+    const unsigned long long c = t.cnt[k];
+    return (uint32_t)__builtin_amdgcn_readfirstlane((int)(c < cap ? (uint32_t)c : cap));
+}
+// The long blob that owns tile (BLOCKS: block sum) e among the nl records — each owns the range it
+// claimed — and e's index in that range; null: a hole left by a failed claim.  Every wave searches
+// alike, 64 records a step (any_tile_owner).
+template <bool BLOCKS>
+__device__ __forceinline__ const AnyDecLarge *anyd_owner(const AnyDecArgs &t, uint32_t nl, uint32_t e, uint32_t &idx) {
+    const uint32_t lane = (uint32_t)lane_id();
+    for (uint32_t L0 = 0; L0 < nl; L0 += 64u) {  // (uniform)
+        const uint32_t L = L0 + lane;
+        bool hit = false;
+        if (L < nl) {
+            const AnyDecLarge &g = t.large[L];
+            hit = g.ws != 0u && (BLOCKS ? e - g.blk0[0] < g.nb[0] + g.nb[1] : e - g.tile0 < g.ntiles);
+        }
+        const uint64_t m = __ballot(hit);
+        if (m) {
+            const AnyDecLarge *g = t.large + L0 + (uint32_t)__builtin_ctzll(m);
+            idx = e - (uint32_t)__builtin_amdgcn_readfirstlane((int)(BLOCKS ? g->blk0[0] : g->tile0));
+            return g;
+        }
+    }
+    return nullptr;
+}
+
+// ---- plan: one lane per entry of the deferred list
+template <bool PAIR>
+__global__ __launch_bounds__(256) void tdt_anyd_plan_kernel(DecodeArgs a, AnyDecArgs t) {
+    const uint32_t listed = *a.dcount;
+    const uint32_t cnt = listed < a.n_msgs ? listed : a.n_msgs;
+    // the tiled path's threshold, as the tuned plan's (tdt_decode_plan_kernel)
+    uint64_t thr = t.large_min;
+    if (a.n_msgs) {
+        uint64_t bytes;
+        if constexpr (PAIR) {
+            bytes = *t.batch_bytes;
+        } else {  // (the look-back route has no in_len: in_off[n] - in_off[0])
+            const uint64_t last = a.in_len ? a.in_off[a.n_msgs - 1] + a.in_len[a.n_msgs - 1] : a.in_off[a.n_msgs];
+            bytes = last - a.in_off[0];
+        }
+        const uint64_t share = bytes / 4096;
+        thr = share > thr ? share : thr;
+    }
+    for (uint32_t it = blockIdx.x * 256u + threadIdx.x; it < cnt; it += gridDim.x * 256u) {
+        uint32_t mark = 0u;
+        const uint32_t msg = a.dlist[it];
+        const uint64_t boff = a.in_off[msg];
+        const uint64_t len = a.in_len ? a.in_len[msg] : a.in_off[msg + 1] - boff;
+        const uint8_t *blob = a.in + boff;
+        // (blob_check has passed: header, mapping and stream table lie inside the blob)
+        const uint32_t orig = ld_u32_bytes(blob + 4), ns = ld_u32_bytes(blob + 8), ws = ld_u32_bytes(blob + 12),
+                       msize = ld_u32_bytes(blob + 16);
+        if (orig > thr && ws != 0u && ws <= (uint32_t)kAnyWsMax) {
+            uint64_t ob;
+            bool fits;
+            if (a.slot_off) {
+                ob = a.slot_off[table_at<PAIR>(msg, 0)];
+                fits = orig <= a.slot_off[table_at<PAIR>(msg, 1)] - ob;
+            } else {
+                ob = a.out_off[msg];
+                fits = ob + orig <= a.out_cap;
+            }
+            // the referenced streams: the first is position 0's
+            uint32_t id[2] = {0u, 0u}, k[2] = {0u, 0u}, nref = 0u;
+            bool many = false;
+            for (uint32_t p = 0; p < ws; ++p) {
+                const uint32_t m = ld_u32_bytes(blob + 20 + 4 * p);
+                if (nref > 0u && m == id[0]) ++k[0];
+                else if (nref > 1u && m == id[1]) ++k[1];
+                else if (nref < 2u) {
+                    id[nref] = m;
+                    k[nref++] = 1u;
+                } else many = true;
+            }
+            if (fits && !many) {
+                uint32_t soff[2] = {0u, 0u}, np[2] = {0u, 0u};
+                uint64_t off = 20 + 4ull * msize;
+                for (uint32_t s = 0; s < ns; ++s) {
+                    const uint32_t sl = ld_u32_bytes(blob + off);
+                    off += 4;
+#pragma unroll
+                    for (int r = 0; r < 2; ++r)
+                        if ((uint32_t)r < nref && id[r] == s) {
+                            soff[r] = (uint32_t)off;
+                            np[r] = sl / 2u;  // (an odd trailing byte is ignored :600)
+                        }
+                    off += sl;
+                }
+                const uint32_t wc = orig / ws, tw = any_dec_tile_words(ws);
+                const uint32_t nt = any_dec_ntiles(wc, tw);
+                const uint32_t nb[2] = {any_dec_nblocks(np[0]), nref > 1u ? any_dec_nblocks(np[1]) : 0u};
+                const unsigned long long L = atomicAdd(t.cnt + ADC_LARGE, 1ull);
+                const unsigned long long B = atomicAdd(t.cnt + ADC_BLOCKS, (unsigned long long)nb[0] + nb[1]);
+                const unsigned long long T = atomicAdd(t.cnt + ADC_TILES, (unsigned long long)nt);
+                if (L < t.lcap && B + nb[0] + nb[1] <= t.bcap && T + nt <= t.tcap) {
+                    AnyDecLarge *g = t.large + L;
+                    g->blob = blob;
+                    g->len = len;
+                    g->dst = a.out + ob;
+                    g->orig = orig;
+                    g->ws = ws;
+                    g->tile0 = (uint32_t)T;
+                    g->ntiles = nt;
+                    uint32_t seen[2] = {0u, 0u};
+                    for (uint32_t p = 0; p < ws; ++p) {  // the rank table: position p is byte seen[r] of its stream's k[r]
+                        const uint32_t r = nref > 1u && ld_u32_bytes(blob + 20 + 4 * p) == id[1] ? 1u : 0u;
+                        g->rank[p] = (uint8_t)(seen[r]++ | (r ? kAnyDecSecond : 0u));
+                    }
+#pragma unroll
+                    for (int r = 0; r < 2; ++r) {
+                        g->soff[r] = soff[r];
+                        g->np[r] = np[r];
+                        g->k[r] = (uint32_t)r < nref ? k[r] : 0u;
+                        g->nb[r] = nb[r];
+                    }
+                    g->blk0[0] = (uint32_t)B;
+                    g->blk0[1] = (uint32_t)B + nb[0];
+                    if (a.status) a.status[msg] = ST_OK;
+                    if (a.slot_off && a.out_len) a.out_len[msg] = orig;
+                    mark = 1u;
+                } else if (L < t.lcap) {  // a budget is spent: the one-workgroup kernel keeps the blob
+                    t.large[L].ws = 0u;  // (no launch's record)
+                }
+            }
+        }
+        t.mark[it] = mark;
+    }
+}
+
+// ---- block sums: one wave per 2,048-pair block, 64 B (32 pairs) per lane
+__global__ __launch_bounds__(kAnyTeam) void tdt_anyd_block_kernel(AnyDecArgs t) {
+    const uint32_t lane = (uint32_t)lane_id();
+    const uint32_t nbk = anyd_claimed(t, ADC_BLOCKS, t.bcap), nl = anyd_claimed(t, ADC_LARGE, t.lcap);
+    for (uint32_t e = blockIdx.x * (uint32_t)kAW + (threadIdx.x >> 6); e < nbk; e += gridDim.x * (uint32_t)kAW) {  // (per wave)
+        uint32_t idx = 0;
+        const AnyDecLarge *g = anyd_owner<true>(t, nl, e, idx);
+        if (!g) continue;
+        const uint32_t r = idx < g->nb[0] ? 0u : 1u, b = r ? idx - g->nb[0] : idx;
+        const uint32_t np = g->np[r];
+        const uint8_t *src = g->blob + g->soff[r], *lim = g->blob + g->len;
+        uint32_t s2 = 0u;
+#pragma unroll
+        for (uint32_t q = 0; q < 4u; ++q) {
+            const uint32_t p0 = kAnyDecPairs * b + 32u * lane + 8u * q;
+            const uint32_t nv = p0 < np ? (np - p0 < 8u ? np - p0 : 8u) : 0u;
+            const uint4 pv = nv ? ld16_span(src + 2ull * p0, (int)(2 * nv), lim) : make_uint4(0, 0, 0, 0);
+            s2 += (pv.x & 0x00ff00ffu) + (pv.y & 0x00ff00ffu) + (pv.z & 0x00ff00ffu) + (pv.w & 0x00ff00ffu);
+        }
+        const uint32_t tot = wave_reduce<OpAdd>((s2 & 0xffffu) + (s2 >> 16));
+        if (lane == 0) t.bsum[e] = tot;
+    }
+}
+
+// ---- scan: one workgroup per long blob; per stream the block sums → their exclusive prefixes, clamped
+__global__ __launch_bounds__(kAnyTeam) void tdt_anyd_scan_kernel(AnyDecArgs t) {
+    __shared__ uint32_t s_slots[2][kAW];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t nl = anyd_claimed(t, ADC_LARGE, t.lcap);
+    uint32_t alt = 0u;
+    for (uint32_t L = blockIdx.x; L < nl; L += gridDim.x) {
+        const AnyDecLarge *g = t.large + L;
+        const uint32_t ws = (uint32_t)__builtin_amdgcn_readfirstlane((int)g->ws);
+        if (ws == 0u) continue;  // (uniform)
+        const uint32_t wc = g->orig / ws;
+        for (uint32_t r = 0; r < 2u; ++r) {
+            const uint32_t k = g->k[r], nb = g->nb[r];
+            if (!k) continue;
+            const uint32_t S = wc * k;
+            uint32_t *E = t.bsum + g->blk0[r];
+            uint32_t carry = 0u;  // (uniform) the clamped prefix behind the blocks so far
+            for (uint32_t i0 = 0; i0 < nb; i0 += kAnyTeam) {
+                const uint32_t i = i0 + tid;
+                uint32_t v[1] = {i < nb ? E[i] : 0u}, tot[1];
+                team_excl_scan<kAW, 1, OpAdd>(v, tot, s_slots[alt]);  // (256 blocks: below 2^28)
+                alt ^= 1u;
+                if (i < nb) E[i] = any_dec_scan_step(carry, v[0], S);
+                carry = any_dec_scan_step(carry, tot[0], S);
+            }
+        }
+    }
+}
+
+// ---- tile: one workgroup per 32 KiB of output
+__global__ __launch_bounds__(kAnyTeam) void tdt_anyd_tile_kernel(AnyDecArgs t) {
+    // the referenced streams' planes: the decoded stream bytes of the tile's range, stream 1's
+    // behind stream 0's at the next multiple of 16 (Σ k_r = ws: at most kAnyDecTile bytes together)
+    __shared__ __attribute__((aligned(16))) uint8_t s_plane[kAnyDecTile + 16];
+    __shared__ uint8_t s_rank[kAnyWsMax];
+    __shared__ uint32_t s_slots[2][kAW];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t nt = anyd_claimed(t, ADC_TILES, t.tcap), nl = anyd_claimed(t, ADC_LARGE, t.lcap);
+    uint32_t alt = 0u;
+    for (uint32_t e = blockIdx.x; e < nt; e += gridDim.x) {  // (uniform)
+        uint32_t tt = 0;
+        const AnyDecLarge *g = anyd_owner<false>(t, nl, e, tt);
+        if (!g) continue;
+        const uint32_t ws = (uint32_t)__builtin_amdgcn_readfirstlane((int)g->ws);
+        const uint32_t orig = (uint32_t)__builtin_amdgcn_readfirstlane((int)g->orig);
+        const uint32_t ntiles = (uint32_t)__builtin_amdgcn_readfirstlane((int)g->ntiles);
+        const uint32_t kk[2] = {(uint32_t)__builtin_amdgcn_readfirstlane((int)g->k[0]),
+                                (uint32_t)__builtin_amdgcn_readfirstlane((int)g->k[1])};
+        const uint32_t wc = orig / ws, wbytes = wc * ws;
+        const AnyDecWords W = any_dec_tile_words_of(tt, wc, any_dec_tile_words(ws));
+        const AnyDecBytes J = any_dec_tile_bytes(tt, ntiles, W, ws, orig);
+        const uint32_t nw = W.w1 - W.w0;
+        const uint32_t off1 = (nw * kk[0] + 15u) & ~15u;  // stream 1's plane
+        const uint32_t used = off1 + nw * kk[1];           // (<= kAnyDecTile + 15)
+        __syncthreads();  // (the tile before is done with the planes)
+        for (uint32_t i = 16u * tid; i < used; i += 16u * kAnyTeam)  // zero: a short or empty stream leaves zeros
+            *reinterpret_cast<uint4 *>(s_plane + i) = make_uint4(0, 0, 0, 0);
+        if (tid < ws) s_rank[tid] = g->rank[tid];
+        __syncthreads();
+        const uint8_t *blob = g->blob, *blim = blob + g->len;
+        for (uint32_t r = 0; r < 2u; ++r) {
+            const uint32_t k = kk[r];
+            const uint32_t np = (uint32_t)__builtin_amdgcn_readfirstlane((int)g->np[r]);
+            if (!k || !np) continue;  // (uniform)
+            const AnyDecRange R = any_dec_stream_range(W, k);
+            const uint32_t *E = t.bsum + g->blk0[r];
+            const uint32_t b = any_dec_first_block([&](uint32_t i) { return gload<uint32_t>(E + i); },
+                                                   (uint32_t)__builtin_amdgcn_readfirstlane((int)g->nb[r]), R.q0);
+            uint64_t sbase = gload<uint32_t>(E + b);  // decoded bytes before this chunk (exact: below the stream's share)
+            const uint8_t *src = blob + g->soff[r];
+            uint8_t *plane = s_plane + (r ? off1 : 0u);
+            for (uint32_t pc = b * kAnyDecPairs; pc < np && sbase < R.q1; pc += kAnyDecPairs) {
+                const uint32_t p0 = pc + 8u * tid;
+                const uint32_t nv = p0 < np ? (np - p0 < 8u ? np - p0 : 8u) : 0u;
+                const uint4 pv = nv ? ld16_span(src + 2ull * p0, (int)(2 * nv), blim) : make_uint4(0, 0, 0, 0);
+                const uint32_t pw[4] = {pv.x, pv.y, pv.z, pv.w};
+                const uint32_t s2 = (pw[0] & 0x00ff00ffu) + (pw[1] & 0x00ff00ffu) + (pw[2] & 0x00ff00ffu) +
+                                    (pw[3] & 0x00ff00ffu);
+                uint32_t v[1] = {(s2 & 0xffffu) + (s2 >> 16)}, tot[1];
+                const uint32_t mine = v[0];
+                team_excl_scan<kAW, 1, OpAdd>(v, tot, s_slots[alt]);
+                alt ^= 1u;
+                uint64_t q = sbase + v[0];
+                if (mine && q < R.q1 && q + mine > R.q0) {
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) {
+                        const uint32_t pr = pw[i >> 1] >> (16 * (i & 1));
+                        const uint32_t c = pr & 0xffu;  // (count 0 emits nothing :602)
+                        const uint8_t val = (uint8_t)(pr >> 8);
+                        const AnyDecClip cl = any_dec_clip(q, c, R.q0, R.q1);
+                        for (uint32_t j = 0; j < cl.n; ++j) plane[cl.off + j] = val;
+                        q += c;
+                    }
+                }
+                sbase += tot[0];
+            }
+        }
+        __syncthreads();
+        // ---- recombine: output byte j of word w, position p, is byte (w - w0) * k_r + rank[p] of its stream's plane
+        uint8_t *dst = g->dst;
+        auto byte_at = [&](uint32_t j) -> uint32_t {
+            if (j >= wbytes) return 0u;  // past the last whole word
+            const uint32_t w = j / ws, p = j - w * ws, rk = s_rank[p];
+            return s_plane[((rk & kAnyDecSecond) ? off1 + (w - W.w0) * kk[1] : (w - W.w0) * kk[0]) + (rk & 63u)];
+        };
+        // the bytes before the first 16-byte boundary of the destination and behind the last, one lane each
+        const uint32_t nbytes = J.je - J.jb;
+        const uint32_t mis = (uint32_t)(16u - ((uintptr_t)(dst + J.jb) & 15u)) & 15u;
+        const uint32_t head = mis < nbytes ? mis : nbytes;
+        const uint32_t ngroups = (nbytes - head) / 16u;
+        const uint32_t jt = J.jb + head + 16u * ngroups;  // the tail's first byte
+        if (tid < head) dst[J.jb + tid] = (uint8_t)byte_at(J.jb + tid);
+        if (tid >= 64u && jt + (tid - 64u) < J.je) dst[jt + (tid - 64u)] = (uint8_t)byte_at(jt + (tid - 64u));
+        for (uint32_t gi = tid; gi < ngroups; gi += kAnyTeam) {
+            const uint32_t j = J.jb + head + 16u * gi;
+            const uint32_t w = j / ws;
+            uint32_t p = j - w * ws;  // wraps at ws: no division per byte
+            uint32_t a0 = (w - W.w0) * kk[0], a1 = off1 + (w - W.w0) * kk[1];
+            uint32_t o[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                if (j + (uint32_t)i < wbytes) {
+                    const uint32_t rk = s_rank[p];
+                    o[i >> 2] |= (uint32_t)s_plane[((rk & kAnyDecSecond) ? a1 : a0) + (rk & 63u)] << (8 * (i & 3));
+                }
+                if (++p == ws) {
+                    p = 0u;
+                    a0 += kk[0];
+                    a1 += kk[1];
+                }
+            }
+            st16_nt(dst + j, make_uint4(o[0], o[1], o[2], o[3]));  // aligned in the destination
+        }
+    }
+}
+
 }  // namespace
 
 int launch_encode_any(const EncodeArgs &a, int ws, int mode, hipStream_t s, bool pair, const AnyTiledArgs *tiled) {
@@ -984,9 +1285,23 @@ int launch_encode_any(const EncodeArgs &a, int ws, int mode, hipStream_t s, bool
     return (int)hipGetLastError();
 }
 
-int launch_decode_any(const DecodeArgs &a, uint32_t grid, hipStream_t s, bool pair) {
-    if (pair) hipLaunchKernelGGL(tdt_decode_any_kernel<true>, dim3(grid ? grid : 1u), dim3(kAnyTeam), 0, s, a);
-    else hipLaunchKernelGGL(tdt_decode_any_kernel<false>, dim3(grid ? grid : 1u), dim3(kAnyTeam), 0, s, a);
+int launch_decode_any(const DecodeArgs &a, uint32_t grid, hipStream_t s, bool pair, const AnyDecArgs *tiled, uint32_t *seen) {
+    const uint32_t *mark = nullptr;
+    if (tiled) {  // the long blobs' records and marks first: the kernel below skips a marked entry
+        const dim3 pg(std::max(1u, std::min((a.n_msgs + 255u) / 256u, tiled->grid ? tiled->grid : 1u))), pt(256);
+        if (pair) hipLaunchKernelGGL(tdt_anyd_plan_kernel<true>, pg, pt, 0, s, a, *tiled);
+        else hipLaunchKernelGGL(tdt_anyd_plan_kernel<false>, pg, pt, 0, s, a, *tiled);
+        mark = tiled->mark;
+    }
+    if (pair) hipLaunchKernelGGL(tdt_decode_any_kernel<true>, dim3(grid ? grid : 1u), dim3(kAnyTeam), 0, s, a, mark, seen);
+    else hipLaunchKernelGGL(tdt_decode_any_kernel<false>, dim3(grid ? grid : 1u), dim3(kAnyTeam), 0, s, a, mark, seen);
+    if (tiled && tiled->lcap && tiled->bcap && tiled->tcap) {  // the tile pipeline: fixed grids over the plan's device-side counts
+        const AnyDecArgs &T = *tiled;
+        const uint32_t g = T.grid ? T.grid : 1u;
+        hipLaunchKernelGGL(tdt_anyd_block_kernel, dim3(std::min(g, (T.bcap + kAW - 1) / kAW)), dim3(kAnyTeam), 0, s, T);
+        hipLaunchKernelGGL(tdt_anyd_scan_kernel, dim3(std::min(g, T.lcap)), dim3(kAnyTeam), 0, s, T);
+        hipLaunchKernelGGL(tdt_anyd_tile_kernel, dim3(std::min(g, T.tcap)), dim3(kAnyTeam), 0, s, T);
+    }
     return (int)hipGetLastError();
 }
 

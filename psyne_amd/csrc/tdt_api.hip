@@ -220,6 +220,32 @@ struct AnyTiledWS {
     }
 };
 
+// Workspace of the tiled generic-width decode (tdt_anyws.h), one per context, as AnyTiledWS: the
+// calls that use it hold the context's lock.
+struct AnyDecWS {
+    uint8_t *buf = nullptr;  // counters (kPlanCounterBytes) | one mark word per entry of the deferred list
+    size_t bytes = 0;
+    uint8_t *rec = nullptr;  // AnyDecLarge records | block sums
+    size_t rec_bytes = 0;
+    uint32_t lcap = 0, bcap = 0, tcap = 0;  // (tiles need no records: their budget bounds the launch)
+    CountHist<psy::AnyDecCount> h;
+    // pinned: the length of the last deferred list that was not empty (0: every list so far was empty),
+    // written by tdt_decode_any_kernel.  A hint only, read without waiting: while it is 0 (a context that
+    // has decoded tuned widths only) a call launches neither the plan nor the snapshot; from the first
+    // listed blob on, every call of the context runs the plan.
+    uint32_t *seen = nullptr;
+    void release() {
+        if (buf) (void)hipFree(buf);
+        if (rec) (void)hipFree(rec);
+        if (seen) (void)hipHostFree(seen);
+        buf = rec = nullptr;
+        seen = nullptr;
+        bytes = rec_bytes = 0;
+        lcap = bcap = tcap = 0;
+        h.release();
+    }
+};
+
 // host pipeline slots (chunks in flight per tdt_encode_host / tdt_decode_host call)
 constexpr int kHostSlots = 4;
 
@@ -313,6 +339,10 @@ struct tdt_ctx {
     // pipeline; off: every one of them on the one-workgroup kernel
     bool any_tiled = true;
     AnyTiledWS anyw;
+    // TDT_OPT_ANY_DEC_TILED (PSYNE_TDT_ANY_DEC_TILED): generic-width blobs that decode to more than the
+    // threshold take the decode tile pipeline; off: every one of them on the one-workgroup kernel
+    bool any_dec_tiled = true;
+    AnyDecWS anydw;
     // diagnostic knobs (read once at tdt_ctx_create from the environment, or tdt_ctx_set_option)
     bool no_side = false;       // PSYNE_TDT_NO_SIDE: no side stream for the tile pipeline
     bool small_main = false;    // PSYNE_TDT_SMALL_MAIN: small lists on the caller's stream
@@ -361,13 +391,15 @@ int launch_any_encode(const psy::EncodeArgs &a, int ws, int mode, hipStream_t s,
 }
 // the follow-up launch of a decode call: the blobs of a generic word size its kernels deferred
 // (grid: workgroups striding over the device-side list; any grid decodes every listed blob)
-int launch_any_decode(const psy::DecodeArgs &a, uint32_t grid, hipStream_t s, bool pair = false) {
+// (tiled: the decode tile pipeline's workspace for the long blobs, any_dec_begin below; null: none)
+int launch_any_decode(const psy::DecodeArgs &a, uint32_t grid, hipStream_t s, bool pair = false,
+                      const psy::AnyDecArgs *tiled = nullptr, uint32_t *seen = nullptr) {
 #if PSY_HAVE_ANYWS
     if (!a.dlist) return TDT_OK;
-    const int e = psy::launch_decode_any(a, std::max(1u, std::min(a.n_msgs, grid)), s, pair);
+    const int e = psy::launch_decode_any(a, std::max(1u, std::min(a.n_msgs, grid)), s, pair, tiled, seen);
     if (e) return set_err(TDT_E_HIP, std::string("generic decode launch: ") + hipGetErrorString((hipError_t)e));
 #else
-    (void)a, (void)grid, (void)s, (void)pair;
+    (void)a, (void)grid, (void)s, (void)pair, (void)tiled, (void)seen;
 #endif
     return TDT_OK;
 }
@@ -737,6 +769,76 @@ int any_tiled_begin(tdt_ctx *c, bool own, uint32_t n, hipStream_t s, AnyTiled &x
 int any_tiled_end(tdt_ctx *c, const AnyTiled &x, uint32_t n, hipStream_t s) {
     if (!x.on || capturing(s)) return TDT_OK;
     return record_counts(c->anyw.h, c->anyw.buf, n, s);
+}
+
+// ---------------------------------------------------------------------------------------
+// The tiled generic-width decode's workspace (AnyDecWS; the kernels: tdt_anyws.h), handled as the
+// encode's above: budgets that start small, the claims in a counter block, the pinned snapshot behind
+// the call, growth in powers of two on a later call with the old buffer retired.  The host reads
+// nothing back.  Under stream capture nothing grows and nothing is snapshotted, and the call never
+// fails because of this workspace: what finds no budget stays on the one-workgroup kernel.
+constexpr uint32_t kAnyDL0 = 64, kAnyDLmax = 1u << 16;      // long blobs per batch
+constexpr uint32_t kAnyDB0 = 1u << 18, kAnyDBmax = 1u << 26; // block sums (4 KiB of pairs each): 512 MiB of long blobs and more, 256 GiB
+constexpr uint32_t kAnyDT0 = 16384, kAnyDTmax = 1u << 22;   // 32 KiB tiles: 512 MiB of output, 128 GiB
+size_t any_dec_rec_bytes(uint32_t lcap, uint32_t bcap) { return (size_t)lcap * sizeof(psy::AnyDecLarge) + 4ull * bcap; }
+// The follow-up launch of a decode call (launch_any_decode) with the tile pipeline beside it.
+// own: the call holds the context's lock (a host-pipeline slot does not: its blobs stay untiled).
+// batch_bytes: a scattered batch's byte counter (DC_BYTES of its plan).
+int decode_deferred(tdt_ctx *c, bool own, const psy::DecodeArgs &a, hipStream_t s, bool pair = false,
+                    const unsigned long long *batch_bytes = nullptr) {
+    const uint32_t grid = (uint32_t)c->cus * 4u, n = a.n_msgs;
+    if (!PSY_HAVE_ANYWS || !a.dlist) return TDT_OK;
+    if (!own || !c->any_dec_tiled || n == 0) return launch_any_decode(a, grid, s, pair);
+    AnyDecWS &w = c->anydw;
+    const bool cap = capturing(s);
+    if (!w.seen) {
+        if (cap) return launch_any_decode(a, grid, s, pair);  // (a cold context: nothing to allocate under capture)
+        HIPCHK(hipHostMalloc(&w.seen, sizeof(uint32_t), hipHostMallocDefault));
+        *w.seen = ~0u;  // (unknown)
+    }
+    // no call has listed a blob yet: a call like them pays no launch for the long blobs it does not have
+    if (*static_cast<volatile uint32_t *>(w.seen) == 0u) return launch_any_decode(a, grid, s, pair, nullptr, w.seen);
+    auto &H = w.h;
+    if (!cap) H.refresh();  // (event queries are not capturable)
+    const size_t need = psy::kPlanCounterBytes + 4ull * n;
+    if (need > w.bytes) {
+        if (cap) return launch_any_decode(a, grid, s, pair, nullptr, w.seen);
+        if (int st = grow_retiring(w.buf, w.bytes, need, psy::cap_double(need, w.bytes), c->retired, s)) return st;
+    }
+    // the tile pipeline is off when an earlier plan found no long blob (its launches would find none)
+    const bool tiles_on = !H.valid || H[psy::ADC_LARGE] > 0;
+    if (tiles_on && !cap) {
+        uint32_t lc = w.lcap ? w.lcap : kAnyDL0, bc = w.bcap ? w.bcap : kAnyDB0, tc = w.tcap ? w.tcap : kAnyDT0;
+        if (H.valid) {  // what an earlier plan claimed, beyond its budget too
+            lc = std::max(lc, pow2_at_least(H[psy::ADC_LARGE], kAnyDL0, kAnyDLmax));
+            bc = std::max(bc, pow2_at_least(H[psy::ADC_BLOCKS], kAnyDB0, kAnyDBmax));
+            tc = std::max(tc, pow2_at_least(H[psy::ADC_TILES], kAnyDT0, kAnyDTmax));
+        }
+        if (lc != w.lcap || bc != w.bcap) {
+            const size_t b = any_dec_rec_bytes(lc, bc);
+            w.lcap = w.bcap = 0;
+            // (retired, not freed: calls still queued, or a captured graph, may use the old records)
+            if (int st = psy::grow(w.rec, w.rec_bytes, b, b, retire_to(c->retired), DevAlloc{})) return st;
+            w.lcap = lc;
+            w.bcap = bc;
+        }
+        w.tcap = tc;
+    }
+    HIPCHK(hipMemsetAsync(w.buf, 0, psy::kPlanSnapBytes, s));
+    psy::AnyDecArgs t{};
+    t.large = reinterpret_cast<psy::AnyDecLarge *>(w.rec);
+    t.bsum = reinterpret_cast<uint32_t *>(w.rec + (size_t)w.lcap * sizeof(psy::AnyDecLarge));
+    t.mark = reinterpret_cast<uint32_t *>(w.buf + psy::kPlanCounterBytes);
+    t.cnt = reinterpret_cast<unsigned long long *>(w.buf);
+    t.batch_bytes = batch_bytes;
+    const bool on = tiles_on && w.rec;
+    t.lcap = on ? w.lcap : 0u;
+    t.bcap = on ? w.bcap : 0u;
+    t.tcap = on ? std::min(w.tcap, std::max(c->tile_cap, 1u)) : 0u;
+    t.grid = (uint32_t)c->cus * 8u;
+    t.large_min = c->large_min;
+    if (int st = launch_any_decode(a, grid, s, pair, &t, w.seen)) return st;
+    return cap ? TDT_OK : record_counts(H, w.buf, n, s);
 }
 
 // grid of one list-driven launch of TEAM-lane workgroups over `count` entries (launches of
@@ -1447,7 +1549,7 @@ int launch_decode_slotted(tdt_ctx *c, PlanWS &pw, psy::DecodeArgs a, hipStream_t
     // the deferred blobs (generic word sizes): near-empty when no kernel above listed one.  (A
     // fixed grid: the plan's count snapshot is taken before the class kernels append to the list,
     // so the history cannot size it — 64 workgroups for 4,096 listed blobs ran at a twelfth of the rate.)
-    return launch_any_decode(a, (uint32_t)c->cus * 4u, s, PAIR);
+    return decode_deferred(c, &pw == &c->pw, a, s, PAIR, cnt + DC_BYTES);
 }
 
 int decode_common(tdt_ctx *c, bool sizes_only, psy::DecodeArgs a, const Where &w) {
@@ -1478,7 +1580,7 @@ int decode_common(tdt_ctx *c, bool sizes_only, psy::DecodeArgs a, const Where &w
         launch_list(n_msgs, 64, [&](uint32_t, uint32_t g) {  // ids from the ticket
             hipLaunchKernelGGL((psy::tdt_decode_kernel<1>), dim3(g), dim3(64), 0, s, a);
         });
-        st = launch_any_decode(a, (uint32_t)c->cus * 4u, s);
+        st = decode_deferred(c, lk.owns_lock(), a, s);
         if (st) return st;
     }
     HIPCHK(hipGetLastError());
@@ -2381,6 +2483,7 @@ int tdt_ctx_create(int device, const tdt_config *cfg, tdt_ctx **out) {
     if (const char *e = std::getenv("PSYNE_TDT_LARGE_MIN")) x->large_min = std::strtoull(e, nullptr, 10);
     if (const char *e = std::getenv("PSYNE_TDT_TILE_CAP")) x->tile_cap = (uint32_t)std::strtoul(e, nullptr, 10);
     if (const char *e = std::getenv("PSYNE_TDT_ANY_TILED")) x->any_tiled = *e != '0';
+    if (const char *e = std::getenv("PSYNE_TDT_ANY_DEC_TILED")) x->any_dec_tiled = *e != '0';
     auto flag = [](const char *name) {
         const char *e = std::getenv(name);
         return e && *e == '1';
@@ -2424,6 +2527,7 @@ void tdt_ctx_destroy(tdt_ctx *ctx) {
     for (void *p : ctx->retired_host) (void)hipHostFree(p);
     ctx->pw.release();
     ctx->anyw.release();
+    ctx->anydw.release();
     for (auto &w : ctx->mx_pw)
         if (w) w->release();
     if (ctx->one_stream) (void)hipStreamSynchronize(ctx->one_stream);
@@ -2484,8 +2588,24 @@ int tdt_ctx_set_option(tdt_ctx *ctx, int option, uint64_t value) {
         case TDT_OPT_NO_TWO_PHASE: ctx->no_two_phase = value != 0; return TDT_OK;
         case TDT_OPT_PACK_SIZES_FIRST: ctx->pack_sizes_first = value == 2 ? 2 : value != 0 ? 1 : 0; return TDT_OK;
         case TDT_OPT_ANY_TILED: ctx->any_tiled = value != 0; return TDT_OK;
+        case TDT_OPT_ANY_DEC_TILED: ctx->any_dec_tiled = value != 0; return TDT_OK;
     }
     return set_err(TDT_E_ARG, "unknown option");
+}
+
+int tdt_ctx_get_stat(tdt_ctx *ctx, int stat, uint64_t *value) {
+    if (!ctx || !value) return set_err(TDT_E_ARG, "null context or value");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    AnyDecWS &w = ctx->anydw;
+    w.h.refresh();  // (the newest snapshot that has landed; never waits)
+    switch (stat) {
+        case TDT_STAT_ANY_DEC_LARGE: *value = w.h.valid ? w.h[psy::ADC_LARGE] : 0; return TDT_OK;
+        case TDT_STAT_ANY_DEC_BLOCKS: *value = w.h.valid ? w.h[psy::ADC_BLOCKS] : 0; return TDT_OK;
+        case TDT_STAT_ANY_DEC_TILES: *value = w.h.valid ? w.h[psy::ADC_TILES] : 0; return TDT_OK;
+        case TDT_STAT_ANY_DEC_BUDGET_LARGE: *value = w.lcap; return TDT_OK;
+        case TDT_STAT_ANY_DEC_BUDGET_TILES: *value = w.tcap; return TDT_OK;
+    }
+    return set_err(TDT_E_ARG, "unknown stat");
 }
 
 int tdt_should_transform(const tdt_ctx *ctx, uint64_t n) {

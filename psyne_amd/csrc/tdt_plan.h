@@ -46,10 +46,18 @@ enum AnyCount : int {
     AC_BYTES = 2         // pair tables: the sum of the message sizes; a mixed-width call: AC_BYTES + route index
 };
 
+// The tiled generic-width decode (tdt_anyws.h) likewise: zeroed before the plan of a call that runs it.
+enum AnyDecCount : int {
+    ADC_LARGE = 0,       // long-blob records claimed (beyond the budget too: the next call grows it)
+    ADC_BLOCKS = 1,      // block sums claimed (likewise)
+    ADC_TILES = 2        // tiles claimed (likewise)
+};
+
 // u32 view of the block: index of a counter's low word (the only place the two units meet)
 constexpr int lo32(EncCount k) { return 2 * (int)k; }
 constexpr int lo32(DecCount k) { return 2 * (int)k; }
 constexpr int lo32(AnyCount k) { return 2 * (int)k; }
+constexpr int lo32(AnyDecCount k) { return 2 * (int)k; }
 
 constexpr size_t kPlanCounterBytes = 256;  // the block
 constexpr size_t kPlanSnapBytes = 128;     // zeroed per call and copied to the host's snapshot

@@ -639,8 +639,19 @@ class TdtCodec:
     def set_option(self, option: int, value: int):
         """tdt_ctx_set_option (tuning / diagnostic knobs; results are the same bytes): the TDT_OPT_*
         values of psyne_amd._lib.  TDT_OPT_LARGE_MIN and TDT_OPT_TILE_CAP govern the tiled paths of every
-        word size; TDT_OPT_ANY_TILED = 0 keeps every generic-width message on one workgroup."""
+        word size; TDT_OPT_ANY_TILED = 0 keeps every generic-width message on one workgroup, and
+        TDT_OPT_ANY_DEC_TILED = 0 every generic-width blob."""
         check(self._lib.tdt_ctx_set_option(self._h, option, int(value)))
+
+    def stat(self, name) -> int:
+        """tdt_ctx_get_stat: a name of psyne_amd._lib.STATS ("ANY_DEC_LARGE", "ANY_DEC_BLOCKS",
+        "ANY_DEC_TILES": what the generic-width decode's plan claimed in the most recent call whose
+        snapshot has landed — synchronise first; "ANY_DEC_BUDGET_LARGE", "ANY_DEC_BUDGET_TILES": the
+        current budgets) or a TDT_STAT_* value."""
+        from ._lib import STATS
+        v = C.c_uint64(0)
+        check(self._lib.tdt_ctx_get_stat(self._h, STATS[name] if isinstance(name, str) else int(name), C.byref(v)))
+        return int(v.value)
 
     # ---- host path (socket buffers) -------------------------------------------------------
     def encode_host(self, data: np.ndarray, offsets: np.ndarray):
