@@ -29,7 +29,8 @@
  *   tdt_analyze_batch                 analyze_data / extract_features / perform_clustering
  *                                     :206-222, :434-525 (full-sample histograms, entropies,
  *                                     mapping per message)
- *   tdt_encode_bound                  worst-case blob size (sizing out buffers)
+ *   tdt_encode_bound /                worst-case blob size (sizing out buffers), and the same under the
+ *   tdt_ctx_encode_bound              context's options (n + 4 with TDT_OPT_RAW_FALLBACK)
  *   tdt_encoded_sizes_batch /         transformation_ratio (encoded size / original size) of each
  *   tdt_encoded_sizes_v               message BEFORE it is encoded: the exact blob length, no blob written
  *   tdt_mappings_v /                  analyze_data's clustering kept between encodes: the mapping of each
@@ -72,8 +73,9 @@ extern "C" {
 #define TDT_E_BAD_MAPPING 4   /* mapping shorter than word_size or value >= num_streams (reference: UB) */
 #define TDT_E_CAPACITY 5      /* output buffer too small for this message */
 #define TDT_E_UNSUPPORTED 6   /* word_size above 64 (tdt_ctx_create, or a blob's header); a compacted
-                                 encode at a word size other than 1, 2, 4, 8, 16 under stream capture
-                                 or TDT_OPT_NO_TWO_PHASE (tdt_last_error has the text) */
+                                 encode at a word size other than 1, 2, 4, 8, 16, or with
+                                 TDT_OPT_RAW_FALLBACK set, under stream capture or TDT_OPT_NO_TWO_PHASE
+                                 (tdt_last_error has the text) */
 #define TDT_E_BAD_HEADER 7    /* word_size == 0 in a blob (reference: division by zero) */
 #define TDT_E_CONFIG 8        /* invalid tdt_config */
 #define TDT_E_HIP 10          /* HIP runtime error (tdt_last_error has the text) */
@@ -125,6 +127,10 @@ int tdt_should_transform(const tdt_ctx *ctx, uint64_t n);
 
 /* Worst-case encoded size of one n-byte message: max(n + 4, 28 + 4*ws + 2n). */
 uint64_t tdt_encode_bound(uint64_t n, int32_t word_size);
+/* The same for this context: n + 4 with TDT_OPT_RAW_FALLBACK set (below), else
+ * tdt_encode_bound(n, the context's word_size).  What tdt_encode_slots sums and what a slot of the
+ * device-batch encodes needs at most. */
+uint64_t tdt_ctx_encode_bound(const tdt_ctx *ctx, uint64_t n);
 
 /* Encode a batch.  out_cap: bytes available at d_out (use the sum of tdt_encode_bound).
  * Messages whose compressed blob would overflow out_cap get TDT_E_CAPACITY.
@@ -132,7 +138,8 @@ uint64_t tdt_encode_bound(uint64_t n, int32_t word_size);
  * At a word size other than 1, 2, 4, 8, 16 this call and tdt_encode_with_mapping_batch always
  * encode into slots and gather (they read the batch's byte count back), so under stream capture
  * or with TDT_OPT_NO_TWO_PHASE they return TDT_E_UNSUPPORTED: capture the slotted entry points
- * (tdt_encode_slots + tdt_encode_batch_into), which read nothing back at any word size. */
+ * (tdt_encode_slots + tdt_encode_batch_into), which read nothing back at any word size.  The same holds
+ * at every word size with TDT_OPT_RAW_FALLBACK set (below); use the context's bound for out_cap then. */
 int tdt_encode_batch(tdt_ctx *ctx, const uint8_t *d_in, const uint64_t *d_in_off, uint32_t n_msgs,
                      uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_off, int32_t *d_status,
                      void *hip_stream);
@@ -351,7 +358,8 @@ int tdt_encode_mapped_vp(tdt_ctx *ctx, const uint8_t *const *d_msgs, const uint6
 /* Decoded size of each scattered blob (0 with an error status), as tdt_decoded_sizes_batch. */
 int tdt_decoded_sizes_v(tdt_ctx *ctx, const uint8_t *const *d_blobs, const uint64_t *d_blob_len, uint32_t n_msgs,
                         uint64_t *d_sizes, int32_t *d_status, void *hip_stream);
-/* d_slot_off (n+1 entries) = exclusive prefix sum of tdt_encode_bound(size_i, word_size). */
+/* d_slot_off (n+1 entries) = exclusive prefix sum of tdt_ctx_encode_bound(size_i): of
+ * tdt_encode_bound(size_i, word_size), or of size_i + 4 with TDT_OPT_RAW_FALLBACK. */
 int tdt_encode_slots(tdt_ctx *ctx, const uint64_t *d_in_off, uint32_t n_msgs, uint64_t *d_slot_off,
                      void *hip_stream);
 /* d_slot_off (n+1 entries) = exclusive prefix sum of the decoded sizes (header parse). */
@@ -412,8 +420,9 @@ int tdt_ctx_error_flags(tdt_ctx *ctx, void *hip_stream, uint32_t *flags);
 
 /* Tuning / diagnostic options (tdt_ctx_create reads the same from the environment once:
  * PSYNE_TDT_LARGE_MIN, PSYNE_TDT_TILE_CAP, PSYNE_TDT_NO_SIDE, PSYNE_TDT_SMALL_MAIN,
- * PSYNE_TDT_NO_TWO_PHASE, PSYNE_TDT_COPY_THREADS, PSYNE_TDT_ANY_TILED, PSYNE_TDT_ANY_DEC_TILED).  Not needed for correct results: every setting encodes and decodes
- * the same bytes. */
+ * PSYNE_TDT_NO_TWO_PHASE, PSYNE_TDT_COPY_THREADS, PSYNE_TDT_ANY_TILED, PSYNE_TDT_ANY_DEC_TILED,
+ * PSYNE_TDT_RAW_FALLBACK).  Not needed for correct results: every setting encodes and decodes
+ * the same bytes — except TDT_OPT_RAW_FALLBACK, which changes which blob an expanding message gets. */
 #define TDT_OPT_LARGE_MIN 1               /* messages above this many bytes take the tiled path (every word size:
                                              the tuned widths' tiles and the generic widths' alike) */
 #define TDT_OPT_TILE_CAP 2                /* lower tile budget per batch (tests of the fallback; every word size) */
@@ -436,6 +445,37 @@ int tdt_ctx_error_flags(tdt_ctx *ctx, void *hip_stream, uint32_t *flags);
                                              decoded as 32 KiB output tiles over the whole device (default 1);
                                              0: every such blob on one workgroup.  The A/B switch: the same
                                              bytes, lengths and statuses either way */
+/* RAW FALLBACK.  TDT never falls back to the raw bytes by itself: a message that does not compress
+ * (a dense fp32 gradient, random bytes) leaves as a TDT blob of up to 28 + 4*ws + 2n bytes.  With this
+ * option at 1 (default 0: every call launches and writes exactly what it does without the option) the
+ * device-batch encodes store such a message as its UNCP blob, which every decoder reads already.
+ *   Rule: take a message that goes down the TDT route — the UNCP routing (the policy, min_tensor_size,
+ *     n % 4, n >= 64, n % word_size) did not take it, and its status would be TDT_OK given enough room —
+ *     and let E be its TDT blob length (under the caller's mapping in the mapped calls).  If E > n + 4
+ *     the output is exactly the UNCP blob: the marker, then the n message bytes; length n + 4, status
+ *     TDT_OK.  If E <= n + 4 (the tie included) the blob stays TDT, byte for byte as without the option.
+ *   Capacity: a message is written, as TDT or as UNCP, if and only if min(E, n + 4) <= capacity;
+ *     otherwise TDT_E_CAPACITY and length 0.  A slot of n + 4 bytes always suffices.  No byte outside
+ *     [ptr, ptr + cap) is written whatever the status; bytes of a slot beyond the final blob may hold
+ *     anything, as without the option.
+ *   Other statuses: rejected widths, TDT_E_BAD_MAPPING, size-0 messages and messages that took UNCP
+ *     by the routing are untouched.
+ *   Where: tdt_encode_batch_into, tdt_encode_batch_v / _vw, tdt_encode_batch_vp (two phases and
+ *     TDT_OPT_PACK_SIZES_FIRST 1 and 2), tdt_encode_mapped_v / _vp; tdt_encoded_sizes_batch / _v and
+ *     tdt_mappings_v report min(E, n + 4) — d_mapbits[i] stays the mapping the analysis decided, also
+ *     for a message that falls back, so mappings of the same bytes still give the same blobs.
+ *     tdt_encode_batch takes its two-phase form (slots of n + 4, scan, gather), and so returns
+ *     TDT_E_UNSUPPORTED under stream capture or TDT_OPT_NO_TWO_PHASE, as it does at generic widths.
+ *     Every word size, every message class, TDT_OPT_ANY_TILED 0 and 1.
+ *   Bounds: tdt_ctx_encode_bound gives n + 4, tdt_encode_slots sums it, and the packed two-phase
+ *     scratch of tdt_encode_batch_vp is total_bytes + 4 * n_msgs.  tdt_encode_bound does not change.
+ *   Device rules: nothing is read back, calls are asynchronous on the caller's stream and capturable
+ *     once one eager call of the same n_msgs (and mask) has grown the workspaces (TDT_E_CAPTURE
+ *     otherwise); n_msgs == 0 touches nothing.  d_out_len and d_status may be NULL as before.
+ *   Calls that ignore the option: tdt_encode_with_mapping_batch (the parity hook), the host calls
+ *     tdt_encode_host / tdt_encode_host_v, and with them the one-message path behind
+ *     HipTDTCompressionProtocol and TdtSubstrate. */
+#define TDT_OPT_RAW_FALLBACK 10
 int tdt_ctx_set_option(tdt_ctx *ctx, int option, uint64_t value);
 
 /* Read-only counters of the context (tests and tools: which path a call took).  The claims are those
@@ -449,6 +489,13 @@ int tdt_ctx_set_option(tdt_ctx *ctx, int option, uint64_t value);
 #define TDT_STAT_ANY_DEC_TILES 3          /* 32 KiB output tiles it claimed */
 #define TDT_STAT_ANY_DEC_BUDGET_LARGE 4   /* the current budgets: long-blob records ... */
 #define TDT_STAT_ANY_DEC_BUDGET_TILES 5   /* ... and tiles (before TDT_OPT_TILE_CAP) */
+#define TDT_STAT_RAW_FALLBACKS 6          /* messages the most recent device-batch encode whose snapshot has landed
+                                             stored raw by TDT_OPT_RAW_FALLBACK's rule (0 after an encode with the
+                                             option off; the size calls and captured replays leave it as it is) */
+#define TDT_STAT_PACK_SCRATCH_BYTES 7     /* bytes of the context's scratch (the slots of the two-phase
+                                             tdt_encode_batch_vp and of the two-phase compacted encode): sized
+                                             exactly by the largest such call so far, 2 * total_bytes + n_msgs *
+                                             (28 + 4 * wmax) — total_bytes + 4 * n_msgs with TDT_OPT_RAW_FALLBACK */
 int tdt_ctx_get_stat(tdt_ctx *ctx, int stat, uint64_t *value);
 
 /* Host-memory analyze (analyze_data :206-222): h_entropy n*ws doubles, h_mapping n*ws int32

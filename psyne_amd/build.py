@@ -26,6 +26,8 @@ ANYWS_SRC = CSRC / "tdt_anyws.hip"  # encode and decode of every other word size
 SOURCES.append(ANYWS_SRC)
 PACK_SRC = CSRC / "tdt_pack.hip"  # the pack kernel of tdt_pack_v / tdt_encode_batch_vp
 SOURCES.append(PACK_SRC)
+RAWFB_SRC = CSRC / "tdt_rawfb.hip"  # the raw fallback's kernels (TDT_OPT_RAW_FALLBACK)
+SOURCES.append(RAWFB_SRC)
 # every source and header under csrc/ (tdt_api.hip includes the headers, directly or not)
 DEPS = SOURCES + [ENC_WS_SRC, ENC_SIZES_WS_SRC, ENC_MAPPED_WS_SRC] + sorted(CSRC.glob("*.h")) + [ROOT / "include" / "psyne_tdt.h"]
 OBJ_DIR = PKG / "build"
@@ -39,7 +41,7 @@ def needs_build() -> bool:
 
 
 def build(force: bool = False, verbose: bool = False) -> pathlib.Path:
-    """Compile tdt_api.hip, tdt_anyws.hip, tdt_pack.hip and one tdt_enc_ws.hip, tdt_enc_sizes_ws.hip and
+    """Compile tdt_api.hip, tdt_anyws.hip, tdt_pack.hip, tdt_rawfb.hip and one tdt_enc_ws.hip, tdt_enc_sizes_ws.hip and
     tdt_enc_mapped_ws.hip object per word size in parallel (the encode kernels dominate the compile time), then
     link libpsyne_tdt.so."""
     if force or needs_build():

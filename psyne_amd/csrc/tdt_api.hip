@@ -29,6 +29,7 @@
 #include "tdt_grow.h"
 #include "tdt_pack.h"
 #include "tdt_plan.h"
+#include "tdt_rawfb.h"
 #include "tdt_slots.h"
 
 // The encode kernels live in tdt_enc_ws.hip (one translation unit per word size); diagnostic
@@ -360,6 +361,15 @@ struct tdt_ctx {
     uint64_t dsmall_max = 8192;
     uint64_t dbig_min = 128 * 1024;  // PSYNE_TDT_DBIG_MIN: one-wave blobs above this are dispatched first
     int cus = 256;              // compute units (overflow grids)
+    // TDT_OPT_RAW_FALLBACK (PSYNE_TDT_RAW_FALLBACK): the device-batch encodes store a message whose TDT
+    // blob would exceed n + 4 bytes as its UNCP blob (tdt_rawfb.h).  Its workspace, rf_buf: counters
+    // (kPlanCounterBytes) | clamped capacities (n) | raw lengths, scanned (n + 1) | lengths (n, where the
+    // caller gave none) | a contiguous batch's tables (4n) | statuses (n int32, where the caller gave none)
+    bool raw_fallback = false;
+    uint8_t *rf_buf = nullptr;
+    size_t rf_bytes = 0;
+    CountHist<psy::RawCount> rf_h;          // TDT_STAT_RAW_FALLBACKS: the flagged messages of a call
+    std::atomic<bool> rf_last_on{false};    // the most recent device-batch encode ran under the option
 };
 
 namespace {
@@ -2428,6 +2438,15 @@ __global__ __launch_bounds__(256) void byte_copy_kernel(const uint8_t *__restric
 
 extern "C" {
 
+// (the raw fallback's routes, defined with the scattered encodes below)
+static int encode_v_any(tdt_ctx *ctx, const Scatter &v, const int32_t *d_word_size, uint64_t width_mask, uint32_t n,
+                        uint64_t *d_out_len, int32_t *d_status, void *stream, const uint64_t *d_mapbits);
+static int encode_into_raw(tdt_ctx *ctx, const uint8_t *d_in, const uint64_t *d_in_off, uint32_t n, uint8_t *d_out,
+                           const uint64_t *d_slot_off, uint64_t *d_out_len, int32_t *d_status, void *stream);
+static int encode_compacted_raw(tdt_ctx *ctx, const psy::EncodeArgs &a, void *stream);
+static int raw_min_sizes(tdt_ctx *ctx, const uint64_t *d_sizes, const uint64_t *d_in_off, uint64_t *d_enc, uint32_t n,
+                         hipStream_t s);
+
 int tdt_copy_device(void *d_dst, const void *d_src, uint64_t bytes, void *hip_stream) {
     if (bytes == 0) return TDT_OK;
     if (!d_dst || !d_src) return set_err(TDT_E_ARG, "null buffer");
@@ -2491,6 +2510,7 @@ int tdt_ctx_create(int device, const tdt_config *cfg, tdt_ctx **out) {
     x->no_side = flag("PSYNE_TDT_NO_SIDE");
     x->small_main = flag("PSYNE_TDT_SMALL_MAIN");
     x->no_two_phase = flag("PSYNE_TDT_NO_TWO_PHASE");
+    x->raw_fallback = flag("PSYNE_TDT_RAW_FALLBACK");
     x->no_one = flag("PSYNE_TDT_NO_ONE");
     x->one_wave = flag("PSYNE_TDT_ONE_WAVE");
     x->dout_sdma = flag("PSYNE_TDT_DOUT_SDMA");
@@ -2521,13 +2541,14 @@ void tdt_ctx_destroy(tdt_ctx *ctx) {
     // every buffer the grower replaces is either freed at once or retired to exactly one list
     // (ctx->retired, ctx->retired_host, a PlanWS's own): the current buffers here, each list once
     for (void *p : {(void *)ctx->ws, (void *)ctx->slot_sums, (void *)ctx->cp_buf, (void *)ctx->cp_idx, (void *)ctx->mx_tab,
-                    (void *)ctx->hbases})
+                    (void *)ctx->hbases, (void *)ctx->rf_buf})
         if (p) (void)hipFree(p);
     for (void *p : ctx->retired) (void)hipFree(p);
     for (void *p : ctx->retired_host) (void)hipHostFree(p);
     ctx->pw.release();
     ctx->anyw.release();
     ctx->anydw.release();
+    ctx->rf_h.release();
     for (auto &w : ctx->mx_pw)
         if (w) w->release();
     if (ctx->one_stream) (void)hipStreamSynchronize(ctx->one_stream);
@@ -2589,6 +2610,7 @@ int tdt_ctx_set_option(tdt_ctx *ctx, int option, uint64_t value) {
         case TDT_OPT_PACK_SIZES_FIRST: ctx->pack_sizes_first = value == 2 ? 2 : value != 0 ? 1 : 0; return TDT_OK;
         case TDT_OPT_ANY_TILED: ctx->any_tiled = value != 0; return TDT_OK;
         case TDT_OPT_ANY_DEC_TILED: ctx->any_dec_tiled = value != 0; return TDT_OK;
+        case TDT_OPT_RAW_FALLBACK: ctx->raw_fallback = value != 0; return TDT_OK;
     }
     return set_err(TDT_E_ARG, "unknown option");
 }
@@ -2596,6 +2618,15 @@ int tdt_ctx_set_option(tdt_ctx *ctx, int option, uint64_t value) {
 int tdt_ctx_get_stat(tdt_ctx *ctx, int stat, uint64_t *value) {
     if (!ctx || !value) return set_err(TDT_E_ARG, "null context or value");
     std::lock_guard<std::mutex> lk(ctx->mu);
+    if (stat == TDT_STAT_PACK_SCRATCH_BYTES) {
+        *value = ctx->cp_bytes;
+        return TDT_OK;
+    }
+    if (stat == TDT_STAT_RAW_FALLBACKS) {
+        ctx->rf_h.refresh();  // (as below: the newest snapshot that has landed)
+        *value = ctx->rf_last_on.load() && ctx->rf_h.valid ? ctx->rf_h[psy::RC_FLAGGED] : 0;
+        return TDT_OK;
+    }
     AnyDecWS &w = ctx->anydw;
     w.h.refresh();  // (the newest snapshot that has landed; never waits)
     switch (stat) {
@@ -2616,9 +2647,12 @@ int tdt_should_transform(const tdt_ctx *ctx, uint64_t n) {
 }
 
 uint64_t tdt_encode_bound(uint64_t n, int32_t word_size) {
-    const uint64_t w = word_size > 0 ? (uint64_t)word_size : 4;
-    const uint64_t tdt = 20 + 4 * w + 8 + 2 * n;
-    return std::max<uint64_t>(tdt, n + 4);
+    return psy::encode_bound_of(n, word_size > 0 ? (uint32_t)word_size : 4u, false);
+}
+
+uint64_t tdt_ctx_encode_bound(const tdt_ctx *ctx, uint64_t n) {
+    if (!ctx) return psy::encode_bound_of(n, 4u, false);
+    return psy::encode_bound_of(n, (uint32_t)ctx->cfg.word_size, ctx->raw_fallback);
 }
 
 
@@ -2646,9 +2680,13 @@ static int encode_two_phase(tdt_ctx *ctx, int mode, const psy::EncodeArgs &a, ui
         e.slot_off = ctx->cp_idx;
         e.out_len = ctx->cp_idx + n + 1;
     }
-    int st = tdt_encode_slots(ctx, a.in_off, n, ctx->cp_idx, stream);
+    // (slots of the TDT bound whatever TDT_OPT_RAW_FALLBACK says: this route serves the calls that ignore
+    // the option — tdt_encode_batch leaves before it when the option is set)
+    hipLaunchKernelGGL(psy::tdt_encode_slots_kernel, dim3((n + 256) / 256), dim3(256), 0, s, a.in_off, ctx->cp_idx, n,
+                       (uint32_t)ctx->cfg.word_size);
+    HIPCHK(hipGetLastError());
+    int st = encode_common(ctx, mode, e, Where(stream));
     if (st) return st;
-    if ((st = encode_common(ctx, mode, e, Where(stream)))) return st;
     if ((st = scan_lengths(ctx, e.out_len, a.out_off, n, s))) return st;
     hipLaunchKernelGGL(cp_gather_kernel, dim3((n + 3) / 4), dim3(256), 0, s, e.out, e.slot_off, e.out_len, a.out, a.out_off,
                        a.out_cap, a.status, n);
@@ -2680,6 +2718,8 @@ int tdt_encode_batch(tdt_ctx *ctx, const uint8_t *d_in, const uint64_t *d_in_off
     auto a = batch_args<psy::EncodeArgs>(d_in, d_in_off, n_msgs, d_out, d_status);
     a.out_cap = out_cap;
     a.out_off = d_out_off;
+    if (ctx && n_msgs && ctx->raw_fallback) return encode_compacted_raw(ctx, a, stream);
+    if (ctx) ctx->rf_last_on.store(false);
     if (ctx && n_msgs && psy::anyws_generic(ctx->cfg.word_size)) return encode_two_phase_any(ctx, psy::MODE_ENCODE, a, stream);
     if (!ctx || n_msgs == 0 || !d_in_off || !d_out || !d_out_off || !two_phase_ok(ctx, stream))
         return encode_common(ctx, psy::MODE_ENCODE, a, Where(stream));
@@ -2770,6 +2810,9 @@ int tdt_encode_batch_into(tdt_ctx *ctx, const uint8_t *d_in, const uint64_t *d_i
                           uint8_t *d_out, const uint64_t *d_slot_off, uint64_t *d_out_len, int32_t *d_status,
                           void *stream) {
     if (n_msgs && !d_slot_off) return set_err(TDT_E_ARG, "null slot offsets");
+    if (ctx && ctx->raw_fallback)
+        return encode_into_raw(ctx, d_in, d_in_off, n_msgs, d_out, d_slot_off, d_out_len, d_status, stream);
+    if (ctx) ctx->rf_last_on.store(false);
     auto a = batch_args<psy::EncodeArgs>(d_in, d_in_off, n_msgs, d_out, d_status);
     a.slot_off = d_slot_off;
     a.out_len = d_out_len;
@@ -2802,15 +2845,17 @@ static int encode_scattered(tdt_ctx *ctx, const Scatter &v, uint32_t n_msgs, uin
 int tdt_encode_batch_v(tdt_ctx *ctx, const uint8_t *const *d_msgs, const uint64_t *d_sizes, uint32_t n_msgs,
                        uint8_t *const *d_blobs, const uint64_t *d_blob_cap, uint64_t *d_out_len, int32_t *d_status,
                        void *stream) {
-    return encode_scattered(ctx, scatter_of(d_msgs, d_sizes, d_blobs, d_blob_cap), n_msgs, d_out_len, d_status, stream);
+    return encode_v_any(ctx, scatter_of(d_msgs, d_sizes, d_blobs, d_blob_cap), nullptr, 0, n_msgs, d_out_len, d_status,
+                        stream, nullptr);
 }
 
 int tdt_encode_batch_vw(tdt_ctx *ctx, const uint8_t *const *d_msgs, const uint64_t *d_sizes,
                         const int32_t *d_word_size, uint64_t width_mask, uint32_t n_msgs, uint8_t *const *d_blobs,
                         const uint64_t *d_blob_cap, uint64_t *d_out_len, int32_t *d_status, void *stream) {
     static_assert(TDT_MIXED_MAX_WIDTHS == psy::kMixedMaxWidths, "the header states the routes' limit");
-    return encode_mixed(ctx, scatter_of(d_msgs, d_sizes, d_blobs, d_blob_cap), d_word_size, width_mask, n_msgs, d_out_len,
-                        d_status, (hipStream_t)stream);
+    if (ctx && n_msgs && !d_word_size) return set_err(TDT_E_ARG, "null pointer, size or word-size array");
+    return encode_v_any(ctx, scatter_of(d_msgs, d_sizes, d_blobs, d_blob_cap), d_word_size, width_mask, n_msgs, d_out_len,
+                        d_status, stream, nullptr);
 }
 
 // lengths → d_out_off, scanned in place, then the byte-balanced pack kernel (tdt_pack.h)
@@ -2844,6 +2889,122 @@ static int encode_scattered_mapped(tdt_ctx *ctx, const Scatter &v, uint32_t n_ms
     Where w(stream);
     w.v = &v;
     return encode_common(ctx, psy::MODE_MAPPED, a, w);
+}
+
+// ---------------------------------------------------------------------------------------
+// The raw fallback (TDT_OPT_RAW_FALLBACK, tdt_rawfb.h) around the scattered encodes.  Every device-batch
+// encode reaches its messages through encode_v_any: option off, the call as it always was; option on,
+// the slots clamped to n + 4 in front of it and the flag, scan and copy passes behind it, all on the
+// caller's stream.  The host reads nothing back.
+static_assert(psy::kRawMarker == psy::kMagicUNCP, "the fallback's blob is the UNCP blob");
+struct RawWS {
+    unsigned long long *cnt;  // the counter block (RawCount)
+    uint64_t *cap, *raw_off, *len, *tab;
+    int32_t *status;
+};
+// rf_buf with room for n messages, under ctx->mu (a buffer a captured graph may point at: retired, not freed)
+static int raw_ws(tdt_ctx *ctx, uint32_t n, hipStream_t s, RawWS &w) {
+    const size_t words = 7ull * n + 1, need = psy::kPlanCounterBytes + 8 * words + 4ull * n;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (int st = grow_retiring(ctx->rf_buf, ctx->rf_bytes, need, psy::cap_double(need, ctx->rf_bytes), ctx->retired, s))
+        return st;
+    uint64_t *u = reinterpret_cast<uint64_t *>(ctx->rf_buf + psy::kPlanCounterBytes);
+    w.cnt = reinterpret_cast<unsigned long long *>(ctx->rf_buf);
+    w.cap = u;
+    w.raw_off = u + n;
+    w.len = u + 2ull * n + 1;
+    w.tab = u + 3ull * n + 1;
+    w.status = reinterpret_cast<int32_t *>(u + words);
+    return TDT_OK;
+}
+// the scattered encode of every form: one width or one per message, the analysis or the caller's mappings
+static int encode_v_plain(tdt_ctx *ctx, const Scatter &v, const int32_t *d_word_size, uint64_t width_mask, uint32_t n,
+                          uint64_t *d_out_len, int32_t *d_status, void *stream, const uint64_t *d_mapbits) {
+    if (d_word_size)
+        return encode_mixed(ctx, v, d_word_size, width_mask, n, d_out_len, d_status, (hipStream_t)stream,
+                            d_mapbits ? psy::MODE_MAPPED : psy::MODE_ENCODE, const_cast<uint64_t *>(d_mapbits));
+    return d_mapbits ? encode_scattered_mapped(ctx, v, n, d_mapbits, d_out_len, d_status, stream)
+                     : encode_scattered(ctx, v, n, d_out_len, d_status, stream);
+}
+static int encode_v_any(tdt_ctx *ctx, const Scatter &v, const int32_t *d_word_size, uint64_t width_mask, uint32_t n,
+                        uint64_t *d_out_len, int32_t *d_status, void *stream, const uint64_t *d_mapbits) {
+    if (!ctx) return set_err(TDT_E_ARG, "null context");
+    if (!ctx->raw_fallback) {
+        ctx->rf_last_on.store(false);
+        return encode_v_plain(ctx, v, d_word_size, width_mask, n, d_out_len, d_status, stream, d_mapbits);
+    }
+    if (n == 0) return TDT_OK;
+    if (!(v.ptr && v.size && v.out_ptr && v.out_cap)) return set_err(TDT_E_ARG, "null pointer or size array");
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(hipSetDevice(ctx->device));
+    RawWS w{};
+    if (int st = raw_ws(ctx, n, s, w)) return st;
+    HIPCHK(hipMemsetAsync(w.cnt, 0, psy::kPlanSnapBytes, s));
+    HIPCHK((hipError_t)psy::launch_raw_clamp(v.size, v.out_cap, w.cap, n, s));
+    const Scatter vc{v.ptr, v.size, v.out_ptr, w.cap};
+    int32_t *status = d_status ? d_status : w.status;
+    uint64_t *len = d_out_len ? d_out_len : w.len;
+    if (int st = encode_v_plain(ctx, vc, d_word_size, width_mask, n, len, status, stream, d_mapbits)) return st;
+    HIPCHK((hipError_t)psy::launch_raw_flag(v.size, v.out_cap, status, len, w.raw_off, w.cnt + psy::RC_FLAGGED, n, s));
+    if (int st = scan_sizes(ctx, w.raw_off, n, s)) return st;
+    HIPCHK((hipError_t)psy::launch_raw_copy(v.ptr, v.out_ptr, w.raw_off, n, ctx->pack_cut, (uint32_t)ctx->cus * 4u, s));
+    ctx->rf_last_on.store(true);
+    if (capturing(s)) return TDT_OK;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    return record_counts(ctx->rf_h, w.cnt, n, s);
+}
+// tdt_encode_batch_into under the option: the contiguous batch as a scattered one
+static int encode_into_raw(tdt_ctx *ctx, const uint8_t *d_in, const uint64_t *d_in_off, uint32_t n, uint8_t *d_out,
+                           const uint64_t *d_slot_off, uint64_t *d_out_len, int32_t *d_status, void *stream) {
+    if (n == 0) return TDT_OK;
+    if (!d_in_off || !d_out || !d_slot_off) return set_err(TDT_E_ARG, "null offsets or output");
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(hipSetDevice(ctx->device));
+    RawWS w{};
+    if (int st = raw_ws(ctx, n, s, w)) return st;
+    uint64_t *t = w.tab;
+    HIPCHK((hipError_t)psy::launch_raw_contig(d_in, d_in_off, d_out, d_slot_off, t, t + n, t + 2ull * n, t + 3ull * n, n, s));
+    const Scatter v{t, t + n, t + 2ull * n, t + 3ull * n};
+    return encode_v_any(ctx, v, nullptr, 0, n, d_out_len, d_status, stream, nullptr);
+}
+// tdt_encode_batch under the option: slots of n + 4 bytes in cp_buf, the slotted encode with the
+// fallback, the lengths scanned into a.out_off, the blobs gathered into a.out (the one-pass look-back
+// publishes a blob's TDT length from inside the kernel, so it cannot serve here)
+static int encode_compacted_raw(tdt_ctx *ctx, const psy::EncodeArgs &a, void *stream) {
+    if (!a.in_off || !a.out || !a.out_off) return set_err(TDT_E_ARG, "null argument");
+    if (!two_phase_ok(ctx, stream))
+        return set_err(TDT_E_UNSUPPORTED, "compacted encode under TDT_OPT_RAW_FALLBACK takes the two phases and reads the "
+                                          "batch size back: not under stream capture or TDT_OPT_NO_TWO_PHASE (use the "
+                                          "slotted or scattered entry points there)");
+    hipStream_t s = (hipStream_t)stream;
+    const uint32_t n = a.n_msgs;
+    HIPCHK(hipSetDevice(ctx->device));
+    uint64_t h2[2];
+    HIPCHK(hipMemcpyAsync(&h2[0], a.in_off, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&h2[1], a.in_off + n, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    uint8_t *buf;
+    uint64_t *slot, *len;
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        if (int st = ensure_cp(ctx, 2ull * n + 2, (h2[1] - h2[0]) + 4ull * n, s)) return st;
+        buf = ctx->cp_buf, slot = ctx->cp_idx, len = ctx->cp_idx + n + 1;
+    }
+    HIPCHK((hipError_t)psy::launch_raw_slots(a.in_off, slot, n, s));
+    if (int st = encode_into_raw(ctx, a.in, a.in_off, n, buf, slot, len, a.status, stream)) return st;
+    if (int st = scan_lengths(ctx, len, a.out_off, n, s)) return st;
+    hipLaunchKernelGGL(cp_gather_kernel, dim3((n + 3) / 4), dim3(256), 0, s, buf, slot, len, a.out, a.out_off, a.out_cap,
+                       a.status, n);
+    HIPCHK(hipGetLastError());
+    return TDT_OK;
+}
+// the size routes under the option: min(E, n + 4) behind the size pass (sizes: the scattered sizes, or
+// null and in_off the contiguous batch's offsets)
+static int raw_min_sizes(tdt_ctx *ctx, const uint64_t *d_sizes, const uint64_t *d_in_off, uint64_t *d_enc, uint32_t n,
+                         hipStream_t s) {
+    if (!ctx || !ctx->raw_fallback || n == 0) return TDT_OK;
+    HIPCHK((hipError_t)psy::launch_raw_min(d_sizes, d_in_off, d_enc, n, s));
+    return TDT_OK;
 }
 
 // tdt_encode_batch_vp (d_mapbits null) and tdt_encode_mapped_vp (the caller's mapping bits: always the
@@ -2889,41 +3050,34 @@ static int encode_packed(tdt_ctx *ctx, const uint8_t *const *d_msgs, const uint6
         int st = d_word_size ? encode_mixed(ctx, vs, d_word_size, width_mask, n_msgs, d_out_off, d_status, s, psy::MODE_SIZES, bits)
                              : encoded_sizes_one(ctx, &vs, nullptr, n_msgs, d_out_off, d_status, s, bits);
         if (st) return st;
+        // (the raw fallback: the exact slots become min(E, n + 4), and the second pass falls back into them)
+        if ((st = raw_min_sizes(ctx, d_sizes, nullptr, d_out_off, n_msgs, s))) return st;
         if ((st = scan_sizes(ctx, d_out_off, n_msgs, s))) return st;
         HIPCHK((hipError_t)psy::launch_pack_exact_slots(d_out_off, d_out, out_cap, ptr, cap, n_msgs, s));
         const Scatter v{msgs, d_sizes, ptr, cap};
-        if (bits)
-            return d_word_size ? encode_mixed(ctx, v, d_word_size, width_mask, n_msgs, nullptr, d_status, s, psy::MODE_MAPPED, bits)
-                               : encode_scattered_mapped(ctx, v, n_msgs, bits, nullptr, d_status, stream);
-        return d_word_size ? encode_mixed(ctx, v, d_word_size, width_mask, n_msgs, nullptr, d_status, s)
-                           : encode_scattered(ctx, v, n_msgs, nullptr, d_status, stream);
+        return encode_v_any(ctx, v, d_word_size, width_mask, n_msgs, nullptr, d_status, stream, bits);
     }
-    // the scratch: every blob in a slot of its encode bound, Σ bounds <= 2·total_bytes + n·(28 + 4·wmax);
+    // the scratch: every blob in a slot of its encode bound, Σ bounds <= 2·total_bytes + n·(28 + 4·wmax) —
+    // under the raw fallback n + 4 per message, total_bytes + 4·n;
     // the tables: slots (n + 1) | blob addresses (n) | capacities (n) | lengths (n)
+    const bool raw = ctx->raw_fallback;
+    const uint64_t scratch = raw ? total_bytes + 4ull * n_msgs : 2 * total_bytes + (uint64_t)n_msgs * (28 + 4 * wmax);
     uint8_t *buf;
     uint64_t buf_bytes, *idx;
     {
         std::lock_guard<std::mutex> lk(ctx->mu);
-        if (int st = ensure_cp(ctx, 4ull * n_msgs + 2, 2 * total_bytes + (uint64_t)n_msgs * (28 + 4 * wmax), s, true))
-            return st;
+        if (int st = ensure_cp(ctx, 4ull * n_msgs + 2, scratch, s, true)) return st;
         buf = ctx->cp_buf, buf_bytes = ctx->cp_bytes, idx = ctx->cp_idx;
     }
     uint64_t *slot = idx, *ptr = idx + n_msgs + 1, *cap = ptr + n_msgs, *len = cap + n_msgs;
-    HIPCHK((hipError_t)psy::launch_pack_bounds(d_sizes, d_word_size, ctx->cfg.word_size, width_mask, slot, n_msgs, s));
+    HIPCHK((hipError_t)(raw ? psy::launch_raw_bounds(d_sizes, d_word_size, ctx->cfg.word_size, width_mask, slot, n_msgs, s)
+                            : psy::launch_pack_bounds(d_sizes, d_word_size, ctx->cfg.word_size, width_mask, slot, n_msgs, s)));
     if (int st = scan_sizes(ctx, slot, n_msgs, s)) return st;
     // (a slot that would end past the scratch — total_bytes was understated — gets capacity 0:
     // TDT_E_CAPACITY for that message, never a write outside the scratch)
     HIPCHK((hipError_t)psy::launch_pack_slots(slot, buf, buf_bytes, ptr, cap, n_msgs, s));
     const Scatter v{reinterpret_cast<const uint64_t *>(d_msgs), d_sizes, ptr, cap};
-    int st;
-    if (d_mapbits)
-        st = d_word_size ? encode_mixed(ctx, v, d_word_size, width_mask, n_msgs, len, d_status, s, psy::MODE_MAPPED,
-                                        const_cast<uint64_t *>(d_mapbits))
-                         : encode_scattered_mapped(ctx, v, n_msgs, d_mapbits, len, d_status, stream);
-    else
-        st = d_word_size ? encode_mixed(ctx, v, d_word_size, width_mask, n_msgs, len, d_status, s)
-                         : encode_scattered(ctx, v, n_msgs, len, d_status, stream);
-    if (st) return st;
+    if (int st = encode_v_any(ctx, v, d_word_size, width_mask, n_msgs, len, d_status, stream, d_mapbits)) return st;
     return pack_common(ctx, ptr, len, n_msgs, d_out, out_cap, d_out_off, d_status, true, s);
 }
 
@@ -2952,10 +3106,8 @@ int tdt_encode_mapped_v(tdt_ctx *ctx, const uint8_t *const *d_msgs, const uint64
     if (!ctx) return set_err(TDT_E_ARG, "null context");
     if (n_msgs == 0) return TDT_OK;
     if (!d_mapbits) return set_err(TDT_E_ARG, "null mapping");
-    const Scatter v = scatter_of(d_msgs, d_sizes, d_blobs, d_blob_cap);
-    if (!d_word_size) return encode_scattered_mapped(ctx, v, n_msgs, d_mapbits, d_out_len, d_status, stream);
-    return encode_mixed(ctx, v, d_word_size, width_mask, n_msgs, d_out_len, d_status, (hipStream_t)stream, psy::MODE_MAPPED,
-                        const_cast<uint64_t *>(d_mapbits));
+    return encode_v_any(ctx, scatter_of(d_msgs, d_sizes, d_blobs, d_blob_cap), d_word_size, width_mask, n_msgs, d_out_len,
+                        d_status, stream, d_mapbits);
 }
 
 int tdt_mappings_v(tdt_ctx *ctx, const uint8_t *const *d_msgs, const uint64_t *d_sizes, const int32_t *d_word_size,
@@ -2976,24 +3128,29 @@ int tdt_mappings_v(tdt_ctx *ctx, const uint8_t *const *d_msgs, const uint64_t *d
     HIPCHK(hipMemsetAsync(d_mapbits, 0, 8ull * n_msgs, s));
     const uint64_t *msgs = reinterpret_cast<const uint64_t *>(d_msgs);
     const Scatter v{msgs, d_sizes, d_sizes, d_sizes};  // (the size pass has no outputs: launch_slotted)
-    if (!d_word_size) return encoded_sizes_one(ctx, &v, nullptr, n_msgs, d_enc_sizes, d_status, s, d_mapbits);
-    return encode_mixed(ctx, v, d_word_size, width_mask, n_msgs, d_enc_sizes, d_status, s, psy::MODE_SIZES, d_mapbits);
+    const int st = !d_word_size ? encoded_sizes_one(ctx, &v, nullptr, n_msgs, d_enc_sizes, d_status, s, d_mapbits)
+                                : encode_mixed(ctx, v, d_word_size, width_mask, n_msgs, d_enc_sizes, d_status, s,
+                                               psy::MODE_SIZES, d_mapbits);
+    // (the raw fallback lowers the sizes alone: d_mapbits[i] stays the mapping the analysis decided)
+    return st ? st : raw_min_sizes(ctx, d_sizes, nullptr, d_enc_sizes, n_msgs, s);
 }
 
 int tdt_encoded_sizes_batch(tdt_ctx *ctx, const uint8_t *d_in, const uint64_t *d_in_off, uint32_t n_msgs,
                             uint64_t *d_enc_sizes, int32_t *d_status, void *stream) {
     const Contig g{d_in, d_in_off};
-    return encoded_sizes_one(ctx, nullptr, &g, n_msgs, d_enc_sizes, d_status, (hipStream_t)stream);
+    const int st = encoded_sizes_one(ctx, nullptr, &g, n_msgs, d_enc_sizes, d_status, (hipStream_t)stream);
+    return st ? st : raw_min_sizes(ctx, nullptr, d_in_off, d_enc_sizes, n_msgs, (hipStream_t)stream);
 }
 
 int tdt_encoded_sizes_v(tdt_ctx *ctx, const uint8_t *const *d_msgs, const uint64_t *d_sizes, const int32_t *d_word_size,
                         uint64_t width_mask, uint32_t n_msgs, uint64_t *d_enc_sizes, int32_t *d_status, void *stream) {
     const uint64_t *msgs = reinterpret_cast<const uint64_t *>(d_msgs);
     const Scatter v{msgs, d_sizes, d_sizes, d_sizes};  // (the size pass has no outputs: launch_slotted)
-    if (!d_word_size) return encoded_sizes_one(ctx, &v, nullptr, n_msgs, d_enc_sizes, d_status, (hipStream_t)stream);
-    if (ctx && n_msgs && !d_enc_sizes) return set_err(TDT_E_ARG, "null output array");
-    return encode_mixed(ctx, v, d_word_size, width_mask, n_msgs, d_enc_sizes, d_status, (hipStream_t)stream,
-                        psy::MODE_SIZES);
+    if (d_word_size && ctx && n_msgs && !d_enc_sizes) return set_err(TDT_E_ARG, "null output array");
+    const int st = !d_word_size ? encoded_sizes_one(ctx, &v, nullptr, n_msgs, d_enc_sizes, d_status, (hipStream_t)stream)
+                                : encode_mixed(ctx, v, d_word_size, width_mask, n_msgs, d_enc_sizes, d_status,
+                                               (hipStream_t)stream, psy::MODE_SIZES);
+    return st ? st : raw_min_sizes(ctx, d_sizes, nullptr, d_enc_sizes, n_msgs, (hipStream_t)stream);
 }
 
 int tdt_decode_batch_v(tdt_ctx *ctx, const uint8_t *const *d_blobs, const uint64_t *d_blob_len, uint32_t n_msgs,
@@ -3026,6 +3183,10 @@ int tdt_encode_slots(tdt_ctx *ctx, const uint64_t *d_in_off, uint32_t n_msgs, ui
     HIPCHK(hipSetDevice(ctx->device));
     if (n_msgs == 0) {  // d_in_off may be null for an empty batch
         HIPCHK(hipMemsetAsync(d_slot_off, 0, 8, (hipStream_t)stream));
+        return TDT_OK;
+    }
+    if (ctx->raw_fallback) {  // n + 4 per message
+        HIPCHK((hipError_t)psy::launch_raw_slots(d_in_off, d_slot_off, n_msgs, (hipStream_t)stream));
         return TDT_OK;
     }
     hipLaunchKernelGGL(psy::tdt_encode_slots_kernel, dim3((n_msgs + 256) / 256), dim3(256), 0, (hipStream_t)stream,

@@ -105,7 +105,10 @@ def _ptr(t) -> int:
 class TdtCodec:
     """Batched TDT codec bound to one HIP device."""
 
-    def __init__(self, config: TDTConfig | None = None, device: int = 0, lib=None):
+    def __init__(self, config: TDTConfig | None = None, device: int = 0, lib=None, raw_fallback: bool = False):
+        """raw_fallback=True sets TDT_OPT_RAW_FALLBACK: the batch encodes store a message whose TDT blob
+        would be longer than the message plus 4 bytes as its UNCP blob (marker + the raw bytes), so a blob
+        never exceeds n + 4 bytes, and the bounds, slots and allocations below follow."""
         self.config = config or TDTConfig()
         self.device = device
         self._lib = lib if lib is not None else _lib.load()  # `lib`: diagnostic builds only
@@ -113,6 +116,15 @@ class TdtCodec:
         cfg = self.config.to_c()
         check(self._lib.tdt_ctx_create(device, C.byref(cfg), C.byref(h)))
         self._h = h
+        if raw_fallback:
+            self.set_option(_lib.TDT_OPT_RAW_FALLBACK, 1)
+
+    @property
+    def raw_fallback(self) -> bool:
+        """Whether the context runs with TDT_OPT_RAW_FALLBACK — however it was set: the constructor,
+        set_option or PSYNE_TDT_RAW_FALLBACK.  Asked of the context: its bound of a message is n + 4
+        exactly then (the TDT bound is at least 2n + 32)."""
+        return self.encode_bound(0) == 4
 
     def close(self):
         if getattr(self, "_h", None):
@@ -141,7 +153,21 @@ class TdtCodec:
         return bool(self._lib.tdt_should_transform(self._h, n))
 
     def encode_bound(self, n: int) -> int:
-        return int(self._lib.tdt_encode_bound(n, self.config.word_size))
+        """tdt_ctx_encode_bound: n + 4 under raw_fallback, else the TDT bound at this codec's word_size."""
+        f = getattr(self._lib, "tdt_ctx_encode_bound", None)
+        if f is None:  # (an older build chosen for an A/B run, which has no raw fallback either)
+            return int(self._lib.tdt_encode_bound(n, self.config.word_size))
+        return int(f(self._h, n))
+
+    @staticmethod
+    def _tdt_bounds(sizes, ws):
+        """tdt_encode_bound over a host int64 array of sizes at width(s) `ws`: what the calls that ignore
+        TDT_OPT_RAW_FALLBACK (the host calls, encode_batch(mapping=...)) may write."""
+        return np.maximum(sizes + 4, 28 + 4 * ws + 2 * sizes)
+
+    def _bounds(self, sizes, ws):
+        """tdt_ctx_encode_bound over a host int64 array of sizes at width(s) `ws`."""
+        return sizes + 4 if self.raw_fallback else self._tdt_bounds(sizes, ws)
 
     # ---- batches (device tensors) ------------------------------------------------------
     @staticmethod
@@ -152,8 +178,7 @@ class TdtCodec:
 
     def batch_bound(self, offsets_host: np.ndarray) -> int:
         sizes = np.diff(np.asarray(offsets_host, dtype=np.int64))
-        ws = self.config.word_size
-        return int(np.maximum(sizes + 4, 28 + 4 * ws + 2 * sizes).sum()) if sizes.size else 0
+        return int(self._bounds(sizes, self.config.word_size).sum()) if sizes.size else 0
 
     def encode_batch(self, data, offsets, out=None, out_offsets=None, status=None, mapping=None,
                      out_capacity: int | None = None, stream=None):
@@ -162,7 +187,11 @@ class TdtCodec:
         import torch
         n = offsets.numel() - 1
         if out is None:
-            cap = out_capacity if out_capacity is not None else self.batch_bound(offsets.cpu().numpy())
+            cap = out_capacity
+            if cap is None and mapping is not None:  # (tdt_encode_with_mapping_batch ignores TDT_OPT_RAW_FALLBACK)
+                cap = int(self._tdt_bounds(np.diff(offsets.cpu().numpy().astype(np.int64)), self.config.word_size).sum())
+            elif cap is None:
+                cap = self.batch_bound(offsets.cpu().numpy())
             out = torch.empty(max(cap, 1), dtype=torch.uint8, device=data.device)
         if out_offsets is None:
             out_offsets = torch.empty(n + 1, dtype=torch.int64, device=data.device)
@@ -550,7 +579,7 @@ class TdtCodec:
                 _, status = self.encode_vw(d[:n], d[n:2 * n], dw, mask, optrs, caps, stream=stream, mapbits=mapbits)
             return out, offsets, status[:n]
         slots = np.zeros(n + 1, np.int64)
-        np.cumsum(np.maximum(sizes + 4, 28 + 4 * ws + 2 * sizes), out=slots[1:])
+        np.cumsum(self._bounds(sizes, ws), out=slots[1:])
         if packed:
             if out is None:
                 out = torch.empty(max(int(slots[-1]), 1), dtype=torch.uint8, device=dev)
@@ -658,7 +687,8 @@ class TdtCodec:
         data = np.ascontiguousarray(data, dtype=np.uint8)
         offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
         n = offsets.size - 1
-        cap = self.batch_bound(offsets)
+        # (the host calls ignore TDT_OPT_RAW_FALLBACK: their blobs reach the TDT bound)
+        cap = int(self._tdt_bounds(np.diff(offsets.astype(np.int64)), self.config.word_size).sum()) if n else 0
         out = np.empty(max(cap, 1), np.uint8)
         out_off = np.zeros(n + 1, np.uint64)
         st = np.zeros(max(n, 1), np.int32)

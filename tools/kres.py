@@ -50,6 +50,8 @@ def main(argv):
     with tempfile.TemporaryDirectory() as tmp:
         jobs = [(csrc / "tdt_api.hip", flags, tmp + "/api.o"), (csrc / "tdt_anyws.hip", flags, tmp + "/anyws.o"),
                 (csrc / "tdt_pack.hip", flags, tmp + "/pack.o")]
+        if (csrc / "tdt_rawfb.hip").exists():  # (absent in a parent tree, as the mapped instances below)
+            jobs.append((csrc / "tdt_rawfb.hip", flags, tmp + "/rawfb.o"))
         jobs += [(csrc / "tdt_enc_ws.hip", flags + ["-DPSY_INST_WS=%d" % ws], tmp + "/ws%d.o" % ws) for ws in ws_list]
         jobs += [(csrc / "tdt_enc_sizes_ws.hip", flags + ["-DPSY_INST_WS=%d" % ws], tmp + "/sws%d.o" % ws) for ws in ws_list]
         if (csrc / "tdt_enc_mapped_ws.hip").exists():  # (absent in a parent tree this file is copied into for an A/B)
