@@ -72,6 +72,15 @@ public:
     HipTDTCompressionProtocol(const HipTDTCompressionProtocol &) = delete;
     HipTDTCompressionProtocol &operator=(const HipTDTCompressionProtocol &) = delete;
 
+    // Raw fallback on the host path (TDT_OPT_HOST_RAW_FALLBACK, psyne_tdt.h; not in the reference, default
+    // off): encode returns "UNCP" + the message where the TDT blob would be longer than size + 4 bytes.
+    // Such a message leaves transformation_ratio() and the times as a message the policy routes to UNCP does.
+    void set_raw_fallback(bool on) {
+        if (tdt_ctx_set_option(ctx_, TDT_OPT_HOST_RAW_FALLBACK, on ? 1 : 0) != TDT_OK)
+            throw std::runtime_error(tdt_last_error());
+    }
+    bool raw_fallback() const { return tdt_ctx_host_encode_bound(ctx_, 0) == 4; }
+
     // PROTOCOL CONCEPT IMPLEMENTATION -------------------------------------------------
     bool should_transform(void *, size_t size) { return tdt_should_transform(ctx_, size) != 0; }
 
@@ -93,7 +102,7 @@ public:
     std::vector<uint8_t> encode(void *data, size_t size) {
         const auto t0 = std::chrono::steady_clock::now();
         const uint64_t off[2] = {0, size};
-        std::vector<uint8_t> out(tdt_encode_bound(size, config_.word_size));
+        std::vector<uint8_t> out(tdt_ctx_host_encode_bound(ctx_, size));  // (n + 4 under set_raw_fallback)
         uint64_t ooff[2] = {0, 0};
         int32_t st = 0;
         if (tdt_encode_host(ctx_, static_cast<const uint8_t *>(data), off, 1, out.data(), out.size(), ooff, &st) !=

@@ -337,6 +337,10 @@ public:
         double bandwidth_mbps = 100.0;
         double latency_ms = 1.0;
         int device = 0;
+        // TDT_OPT_HOST_RAW_FALLBACK on the decorator's codec: a frame whose TDT blob would be longer than
+        // the message plus 4 bytes leaves as "UNCP" + the message, and send_batch's pinned ring is sized by
+        // n + 4 per message instead of the TDT bound
+        bool raw_fallback = false;
     };
     static Defaults &defaults() {
         static Defaults d;
@@ -349,6 +353,7 @@ public:
     explicit TdtSubstrate(const TDTConfig &cfg, InnerArgs &&...inner_args)
         : inner_(std::forward<InnerArgs>(inner_args)...), codec_(cfg, defaults().device) {
         codec_.update_network_metrics(defaults().bandwidth_mbps, defaults().latency_ms);
+        if (defaults().raw_fallback) codec_.set_raw_fallback(true);
         name_ = std::string("TDT+") + inner_.substrate_name();
     }
     ~TdtSubstrate() {
@@ -522,7 +527,7 @@ public:
             uint64_t cap = 0, payload = 0;
             for (size_t i = 0; i < n && (i == 0 || payload + sizes[i] <= kSubBytes) && i < kSubFrames; ++i) {
                 payload += sizes[i];
-                cap += tdt_encode_bound(sizes[i], codec_.word_size());
+                cap += tdt_ctx_host_encode_bound(codec_.context(), sizes[i]);
             }
             for (auto &t : tx_ring_) t.mem.reserve(cap);
             tx_thread_ = std::thread([this] { tx_loop(); });
@@ -539,7 +544,7 @@ public:
             uint64_t payload = 0, cap = 0;
             while (i + m < n && (m == 0 || (payload + sz[i + m] <= kSubBytes && m < kSubFrames))) {
                 payload += sz[i + m];
-                cap += tdt_encode_bound(sz[i + m], codec_.word_size());
+                cap += tdt_ctx_host_encode_bound(codec_.context(), sz[i + m]);  // (n + 4 under raw_fallback)
                 ++m;
             }
             auto t0 = Clock::now();

@@ -30,7 +30,8 @@
  *                                     :206-222, :434-525 (full-sample histograms, entropies,
  *                                     mapping per message)
  *   tdt_encode_bound /                worst-case blob size (sizing out buffers), and the same under the
- *   tdt_ctx_encode_bound              context's options (n + 4 with TDT_OPT_RAW_FALLBACK)
+ *   tdt_ctx_encode_bound /            context's options (n + 4 with TDT_OPT_RAW_FALLBACK; for the host calls
+ *   tdt_ctx_host_encode_bound         n + 4 with TDT_OPT_HOST_RAW_FALLBACK)
  *   tdt_encoded_sizes_batch /         transformation_ratio (encoded size / original size) of each
  *   tdt_encoded_sizes_v               message BEFORE it is encoded: the exact blob length, no blob written
  *   tdt_mappings_v /                  analyze_data's clustering kept between encodes: the mapping of each
@@ -131,6 +132,9 @@ uint64_t tdt_encode_bound(uint64_t n, int32_t word_size);
  * tdt_encode_bound(n, the context's word_size).  What tdt_encode_slots sums and what a slot of the
  * device-batch encodes needs at most. */
 uint64_t tdt_ctx_encode_bound(const tdt_ctx *ctx, uint64_t n);
+/* The same for the host calls (tdt_encode_host / tdt_encode_host_v): n + 4 with TDT_OPT_HOST_RAW_FALLBACK
+ * set (below), else tdt_encode_bound(n, the context's word_size).  What h_out must hold per message. */
+uint64_t tdt_ctx_host_encode_bound(const tdt_ctx *ctx, uint64_t n);
 
 /* Encode a batch.  out_cap: bytes available at d_out (use the sum of tdt_encode_bound).
  * Messages whose compressed blob would overflow out_cap get TDT_E_CAPACITY.
@@ -421,8 +425,9 @@ int tdt_ctx_error_flags(tdt_ctx *ctx, void *hip_stream, uint32_t *flags);
 /* Tuning / diagnostic options (tdt_ctx_create reads the same from the environment once:
  * PSYNE_TDT_LARGE_MIN, PSYNE_TDT_TILE_CAP, PSYNE_TDT_NO_SIDE, PSYNE_TDT_SMALL_MAIN,
  * PSYNE_TDT_NO_TWO_PHASE, PSYNE_TDT_COPY_THREADS, PSYNE_TDT_ANY_TILED, PSYNE_TDT_ANY_DEC_TILED,
- * PSYNE_TDT_RAW_FALLBACK).  Not needed for correct results: every setting encodes and decodes
- * the same bytes — except TDT_OPT_RAW_FALLBACK, which changes which blob an expanding message gets. */
+ * PSYNE_TDT_RAW_FALLBACK, PSYNE_TDT_HOST_RAW_FALLBACK).  Not needed for correct results: every setting
+ * encodes and decodes the same bytes — except TDT_OPT_RAW_FALLBACK and TDT_OPT_HOST_RAW_FALLBACK, which
+ * change which blob an expanding message gets. */
 #define TDT_OPT_LARGE_MIN 1               /* messages above this many bytes take the tiled path (every word size:
                                              the tuned widths' tiles and the generic widths' alike) */
 #define TDT_OPT_TILE_CAP 2                /* lower tile budget per batch (tests of the fallback; every word size) */
@@ -472,10 +477,26 @@ int tdt_ctx_error_flags(tdt_ctx *ctx, void *hip_stream, uint32_t *flags);
  *   Device rules: nothing is read back, calls are asynchronous on the caller's stream and capturable
  *     once one eager call of the same n_msgs (and mask) has grown the workspaces (TDT_E_CAPTURE
  *     otherwise); n_msgs == 0 touches nothing.  d_out_len and d_status may be NULL as before.
- *   Calls that ignore the option: tdt_encode_with_mapping_batch (the parity hook), the host calls
- *     tdt_encode_host / tdt_encode_host_v, and with them the one-message path behind
- *     HipTDTCompressionProtocol and TdtSubstrate. */
+ *   Calls that ignore the option: tdt_encode_with_mapping_batch (the parity hook, which no option
+ *     changes), and the host calls tdt_encode_host / tdt_encode_host_v with the one-message path behind
+ *     HipTDTCompressionProtocol and TdtSubstrate — those have an option of their own, next. */
 #define TDT_OPT_RAW_FALLBACK 10
+/* RAW FALLBACK ON THE HOST PATH.  The same rule for tdt_encode_host and tdt_encode_host_v (pageable and
+ * pinned buffers, every word size, one message or many), and through them HipTDTCompressionProtocol::
+ * encode and TdtSubstrate::send / send_batch.  Default 0: every host call launches and writes exactly what
+ * it does without the option; independent of TDT_OPT_RAW_FALLBACK (PSYNE_TDT_HOST_RAW_FALLBACK).
+ *   Rule: as above — a message that goes down the TDT route and whose TDT blob length E exceeds n + 4
+ *     comes out as the marker and the n message bytes, length n + 4, status TDT_OK; E <= n + 4 (the tie
+ *     included) stays TDT byte for byte; messages the UNCP routing takes and size-0 messages are untouched.
+ *   Bound: tdt_ctx_host_encode_bound(ctx, n) is n + 4; h_out_off stays the exclusive prefix of the final
+ *     lengths, and the call returns TDT_E_CAPACITY only if their sum exceeds out_cap.  Nothing is
+ *     written past h_out + out_cap.
+ *   How: every chunk of the pipeline takes the slotted route with slots of n + 4 bytes; behind the
+ *     chunk's encode a flag pass decides, and the chunk's gather to host memory takes a flagged blob
+ *     straight from the chunk's input — a fallen-back message is never written on the device.  A
+ *     one-message call stores the raw bytes on the host, with no second launch.
+ *   TDT_STAT_HOST_RAW_FALLBACKS counts the messages of the most recent host encode call. */
+#define TDT_OPT_HOST_RAW_FALLBACK 11
 int tdt_ctx_set_option(tdt_ctx *ctx, int option, uint64_t value);
 
 /* Read-only counters of the context (tests and tools: which path a call took).  The claims are those
@@ -496,6 +517,9 @@ int tdt_ctx_set_option(tdt_ctx *ctx, int option, uint64_t value);
                                              tdt_encode_batch_vp and of the two-phase compacted encode): sized
                                              exactly by the largest such call so far, 2 * total_bytes + n_msgs *
                                              (28 + 4 * wmax) — total_bytes + 4 * n_msgs with TDT_OPT_RAW_FALLBACK */
+#define TDT_STAT_HOST_RAW_FALLBACKS 8     /* messages the most recent host encode call of the context (tdt_encode_host
+                                             / _v) stored raw by TDT_OPT_HOST_RAW_FALLBACK's rule.  Host calls block, so
+                                             the value is final when the call returns; 0 after a call with the option off */
 int tdt_ctx_get_stat(tdt_ctx *ctx, int stat, uint64_t *value);
 
 /* Host-memory analyze (analyze_data :206-222): h_entropy n*ws doubles, h_mapping n*ws int32

@@ -20,15 +20,17 @@ TDT_OPT_PACK_SIZES_FIRST = 7
 TDT_OPT_ANY_TILED = 8  # generic word sizes: long messages as tiles (default 1); 0: one workgroup per message
 TDT_OPT_ANY_DEC_TILED = 9  # generic word sizes: long blobs decoded as 32 KiB tiles (default 1); 0: one workgroup per blob
 TDT_OPT_RAW_FALLBACK = 10  # 1: a message whose TDT blob would exceed n + 4 bytes is stored as its UNCP blob (default 0)
+TDT_OPT_HOST_RAW_FALLBACK = 11  # 1: the same rule for the host calls (tdt_encode_host / _v); independent of option 10
 # tdt_ctx_get_stat: the generic-width decode plan's claims of the last call whose snapshot landed, and the budgets
 TDT_STAT_ANY_DEC_LARGE, TDT_STAT_ANY_DEC_BLOCKS, TDT_STAT_ANY_DEC_TILES = 1, 2, 3
 TDT_STAT_ANY_DEC_BUDGET_LARGE, TDT_STAT_ANY_DEC_BUDGET_TILES = 4, 5
 TDT_STAT_RAW_FALLBACKS = 6  # messages the last device-batch encode stored raw by TDT_OPT_RAW_FALLBACK's rule
 TDT_STAT_PACK_SCRATCH_BYTES = 7  # bytes of the context's two-phase scratch (sized exactly by the largest call so far)
+TDT_STAT_HOST_RAW_FALLBACKS = 8  # messages the last host encode call stored raw by TDT_OPT_HOST_RAW_FALLBACK's rule
 STATS = {"ANY_DEC_LARGE": TDT_STAT_ANY_DEC_LARGE, "ANY_DEC_BLOCKS": TDT_STAT_ANY_DEC_BLOCKS,
          "ANY_DEC_TILES": TDT_STAT_ANY_DEC_TILES, "ANY_DEC_BUDGET_LARGE": TDT_STAT_ANY_DEC_BUDGET_LARGE,
          "ANY_DEC_BUDGET_TILES": TDT_STAT_ANY_DEC_BUDGET_TILES, "RAW_FALLBACKS": TDT_STAT_RAW_FALLBACKS,
-         "PACK_SCRATCH_BYTES": TDT_STAT_PACK_SCRATCH_BYTES}
+         "PACK_SCRATCH_BYTES": TDT_STAT_PACK_SCRATCH_BYTES, "HOST_RAW_FALLBACKS": TDT_STAT_HOST_RAW_FALLBACKS}
 
 
 class TdtConfigC(C.Structure):
@@ -53,6 +55,7 @@ SIGNATURES = {
     "tdt_should_transform": (C.c_int, [_vp, C.c_uint64]),
     "tdt_encode_bound": (C.c_uint64, [C.c_uint64, C.c_int32]),
     "tdt_ctx_encode_bound": (C.c_uint64, [_vp, C.c_uint64]),
+    "tdt_ctx_host_encode_bound": (C.c_uint64, [_vp, C.c_uint64]),
     "tdt_encode_batch": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _vp, C.c_uint64, _vp, _vp, _vp]),
     "tdt_encode_with_mapping_batch": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint64, _vp, _vp, _vp]),
     "tdt_decode_batch": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _vp, C.c_uint64, _vp, _vp, _vp]),

@@ -79,6 +79,10 @@ LOOPBACK_SRC = ROOT / "tests" / "native" / "tcp_loopback.cpp"
 LOOPBACK_BIN = ROOT / "tests" / "native" / "tcp_loopback"
 SUBSTRATE_TEST_SRC = ROOT / "tests" / "cpp" / "test_substrate.cpp"
 SUBSTRATE_TEST_BIN = ROOT / "tests" / "cpp" / "test_substrate"
+HOST_RAW_TEST_SRC = ROOT / "tests" / "cpp" / "test_host_raw_fallback.cpp"  # TDT_OPT_HOST_RAW_FALLBACK through the C++ layers
+HOST_RAW_TEST_BIN = ROOT / "tests" / "cpp" / "test_host_raw_fallback"
+HOST_RAW_PARTS_SRC = ROOT / "tests" / "cpp" / "test_host_raw_parts.cpp"  # the raw gather's part arithmetic (host only)
+HOST_RAW_PARTS_BIN = ROOT / "tests" / "cpp" / "test_host_raw_parts"
 SELFTEST_SRC = ROOT / "tests" / "native" / "selftest.hip"
 SELFTEST_LIB = ROOT / "tests" / "native" / "libtdt_selftest.so"
 
@@ -108,6 +112,20 @@ def build_tests(verbose: bool = False):
         cmd = ["g++", "-std=c++20", "-O2", "-I", str(ROOT / "include"), str(SUBSTRATE_TEST_SRC), "-o",
                str(SUBSTRATE_TEST_BIN), "-L", str(PKG), "-lpsyne_tdt", "-pthread", "-Wl,-rpath," + str(PKG),
                "-Wl,-rpath,$ORIGIN/../../psyne_amd"]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        subprocess.check_call(cmd)
+    if not HOST_RAW_TEST_BIN.exists() or HOST_RAW_TEST_BIN.stat().st_mtime < max(
+            [HOST_RAW_TEST_SRC.stat().st_mtime, LIB.stat().st_mtime] + [h.stat().st_mtime for h in hdrs]):
+        cmd = ["g++", "-std=c++20", "-O2", "-I", str(ROOT / "include"), str(HOST_RAW_TEST_SRC), "-o",
+               str(HOST_RAW_TEST_BIN), "-L", str(PKG), "-lpsyne_tdt", "-pthread", "-Wl,-rpath," + str(PKG),
+               "-Wl,-rpath,$ORIGIN/../../psyne_amd"]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        subprocess.check_call(cmd)
+    if not HOST_RAW_PARTS_BIN.exists() or HOST_RAW_PARTS_BIN.stat().st_mtime < max(
+            HOST_RAW_PARTS_SRC.stat().st_mtime, (CSRC / "tdt_rawfb.h").stat().st_mtime, (CSRC / "tdt_pack.h").stat().st_mtime):
+        cmd = ["g++", "-std=c++17", "-O2", str(HOST_RAW_PARTS_SRC), "-o", str(HOST_RAW_PARTS_BIN)]
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.check_call(cmd)

@@ -370,6 +370,11 @@ struct tdt_ctx {
     size_t rf_bytes = 0;
     CountHist<psy::RawCount> rf_h;          // TDT_STAT_RAW_FALLBACKS: the flagged messages of a call
     std::atomic<bool> rf_last_on{false};    // the most recent device-batch encode ran under the option
+    // TDT_OPT_HOST_RAW_FALLBACK (PSYNE_TDT_HOST_RAW_FALLBACK): the same rule for the host calls
+    // (host_encode, host_one).  Independent of the option above; its flag words live in each chunk's own
+    // device layout (Chunk), since up to kHostSlots chunks are in flight.
+    bool host_raw_fallback = false;
+    std::atomic<uint64_t> host_rf_count{0};  // TDT_STAT_HOST_RAW_FALLBACKS: of the most recent host encode call
 };
 
 namespace {
@@ -1682,9 +1687,12 @@ struct Chunk {
     uint32_t m0 = 0, n = 0;
     uint64_t in_bytes = 0, cap = 0, base = 0;
     uint64_t scap = 0;  // encode through the slotted kernels: the blobs' slot bytes (Σ bounds)
-    // device layout: input | in_off (n+1), slots (n+1) | out (cap) | out_off (n+1) | status (n)
-    // | workspace | lengths (n) | slotted blobs (scap)
-    size_t o_off = 0, o_out = 0, o_ooff = 0, o_st = 0, o_ws = 0, o_len = 0, o_sbuf = 0, end = 0;
+    // encode under TDT_OPT_HOST_RAW_FALLBACK: slots of n + 4 (always slotted), and the flag pass's words —
+    // the chunk's count behind out_off, a flag per message in front of the slot buffer
+    bool raw = false;
+    // device layout: input | in_off (n+1), slots (n+1) | out (cap) | out_off (n+1) [raw: | count] | status (n)
+    // | workspace | lengths (n) [raw: | flags (n u32)] | slotted blobs (scap)
+    size_t o_off = 0, o_out = 0, o_ooff = 0, o_st = 0, o_ws = 0, o_len = 0, o_rf = 0, o_sbuf = 0, end = 0;
 };
 
 // Chunk size of a call: an eighth of its input (with four slots in flight the H2D of later
@@ -1696,15 +1704,16 @@ uint64_t host_chunk_bytes(const uint64_t *h_in_off, uint32_t n_msgs) {
 }
 
 Chunk plan_chunk(const uint64_t *h_in_off, uint32_t m0, uint32_t n_msgs, bool encode, bool slotted, int ws,
-                 const uint64_t *dec_sizes, uint64_t chunk_bytes) {
+                 const uint64_t *dec_sizes, uint64_t chunk_bytes, bool raw = false) {
     Chunk k;
     k.m0 = m0;
+    k.raw = raw;
     uint32_t m = m0;
     uint64_t cap = 0;
     while (m < n_msgs) {
         const uint64_t len = h_in_off[m + 1] - h_in_off[m];
         if (m > m0 && h_in_off[m + 1] - h_in_off[m0] > chunk_bytes) break;
-        cap += encode ? tdt_encode_bound(len, ws) : dec_sizes[m];
+        cap += !encode ? dec_sizes[m] : raw ? psy::raw_blob_bytes(len) : tdt_encode_bound(len, ws);
         ++m;
     }
     k.n = m - m0;
@@ -1715,20 +1724,24 @@ Chunk plan_chunk(const uint64_t *h_in_off, uint32_t m0, uint32_t n_msgs, bool en
     k.o_out = align_up(k.o_off + 16ull * (k.n + 1), 256);
     // (the slotted encode writes its blobs into the slot buffer at o_sbuf: no compacted region)
     k.o_ooff = align_up(k.o_out + (k.scap ? 1ull : std::max<uint64_t>(cap, 1)), 256);
-    k.o_st = align_up(k.o_ooff + 8ull * (k.n + 1), 256);
+    k.o_st = align_up(k.o_ooff + 8ull * (k.n + 1 + (raw ? 1 : 0)), 256);
     k.o_ws = align_up(k.o_st + 4ull * k.n, 256);
     k.o_len = align_up(k.o_ws + kCounterBytes + 8ull * (k.n + 1), 256);
-    k.o_sbuf = align_up(k.o_len + 8ull * k.n, 256);
+    k.o_rf = align_up(k.o_len + 8ull * k.n, 256);
+    k.o_sbuf = align_up(k.o_rf + (raw ? 4ull * k.n : 0), 256);
     k.end = k.o_sbuf + (k.scap ? k.scap + 16 : 0);  // (+16: more than the gather's copy needs — the over-read rule, tdt_copy.h)
     return k;
 }
 
 size_t chunk_dev_bytes(const Chunk &k) { return k.end; }
-// pinned words of a slot: in_off (n+1) | slots (n+1) | out_off or lengths (n+1) | status (n int32)
-size_t chunk_pin_words(const Chunk &k) { return 3ull * k.n + 3 + (k.n + 1) / 2; }
+// pinned words of a slot: in_off (n+1) | slots (n+1) | out_off or lengths (n+1) [raw: | count] | status (n int32)
+size_t chunk_back_words(const Chunk &k) { return (size_t)k.n + 1 + (k.raw ? 1 : 0); }
+size_t chunk_pin_words(const Chunk &k) { return 2ull * k.n + 2 + chunk_back_words(k) + (k.n + 1) / 2; }
 uint64_t *pin_slots(tdt_ctx::HostSlot &h, const Chunk &k) { return h.pin + (k.n + 1); }
 uint64_t *pin_back(tdt_ctx::HostSlot &h, const Chunk &k) { return h.pin + 2ull * (k.n + 1); }
-int32_t *pin_status(tdt_ctx::HostSlot &h, const Chunk &k) { return reinterpret_cast<int32_t *>(h.pin + 3ull * k.n + 3); }
+int32_t *pin_status(tdt_ctx::HostSlot &h, const Chunk &k) {
+    return reinterpret_cast<int32_t *>(h.pin + 2ull * k.n + 2 + chunk_back_words(k));
+}
 
 // decode: the decoded size of every blob from its header (the kernel validates; a blob it
 // rejects gets 0 and its bytes are dropped when the output is compacted)
@@ -1835,6 +1848,69 @@ __global__ __launch_bounds__(256) void host_gather_kernel(const uint8_t *src, co
     }
 }
 
+// TDT_OPT_HOST_RAW_FALLBACK: the flag pass behind a chunk's slotted encode into slots of n + 4 bytes.
+// One workgroup striding over the chunk's messages, one lane per message at a time, as the scan that
+// follows it: so the chunk's count is a plain sum with no word to clear first.  The decision is
+// tdt_rawfb.h's; a flagged message gets its final status and length here, flag[i] says where the gather
+// takes blob i from, and *count is the chunk's share of TDT_STAT_HOST_RAW_FALLBACKS.
+__global__ __launch_bounds__(1024) void host_raw_flag_kernel(const uint64_t *in_off, const uint64_t *slot, int32_t *status,
+                                                             uint64_t *len, uint32_t *flag, uint64_t *count, uint32_t n) {
+    __shared__ uint32_t wsum[16];
+    uint32_t mine = 0;
+    for (uint32_t i = threadIdx.x; i < n; i += 1024) {
+        const uint64_t sz = in_off[i + 1] - in_off[i];
+        const bool f = psy::raw_flagged(status[i], len[i], sz, slot[i + 1] - slot[i]);
+        if (f) {
+            status[i] = TDT_OK;
+            len[i] = psy::raw_blob_bytes(sz);
+        }
+        flag[i] = f ? 1u : 0u;
+        mine += f ? 1u : 0u;
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) mine += __shfl_down(mine, d);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = mine;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint64_t tot = 0;
+        for (int w = 0; w < 16; ++w) tot += wsum[w];
+        *count = tot;
+    }
+}
+
+// host_gather_kernel under TDT_OPT_HOST_RAW_FALLBACK: the same P waves per blob, running base and
+// `direct` handling, with the source chosen per blob.  An unflagged blob comes from its slot.  A flagged
+// one was never written there: a wave's part [a, e) of its n + 4 bytes is tdt_rawfb.h's raw_span — marker
+// bytes from raw_marker_byte, and payload bytes straight from the chunk's input at in + in_off[i].  That
+// source obeys the copy's over-read rule (tdt_copy.h) inside the chunk buffer: the input starts the
+// buffer, and the offset tables follow it.
+__global__ __launch_bounds__(256) void host_raw_gather_kernel(const uint8_t *in, const uint64_t *in_off, const uint8_t *src,
+                                                              const uint64_t *slot, const uint64_t *len,
+                                                              const uint32_t *flag, const uint64_t *out_off, uint32_t n,
+                                                              uint32_t P, uint8_t *dst, uint64_t *bases, uint32_t ci,
+                                                              uint64_t cap, int direct) {
+    const uint64_t total = out_off[n];
+    const uint64_t base = bases[ci];
+    if (blockIdx.x == 0 && threadIdx.x == 0) bases[ci + 1] = base + total;
+    if (base + total > cap || total == 0) return;
+    uint8_t *d = direct ? dst + base : dst;
+    const uint64_t nw = (uint64_t)n * P;
+    const uint32_t lane = threadIdx.x & 63u;
+    for (uint64_t w = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); w < nw; w += (uint64_t)gridDim.x * 4) {
+        const uint32_t i = (uint32_t)(w / P), p = (uint32_t)(w % P);
+        const uint64_t l = len[i], a = l * p / P, e = l * (p + 1) / P;
+        if (e <= a) continue;
+        uint8_t *o = d + out_off[i];
+        if (!flag[i]) {
+            psy::copy_shifted<1, false>(o + a, src + slot[i] + a, e - a, lane, 64);
+            continue;
+        }
+        const psy::RawSeg s = psy::raw_span(a, e);
+        if (lane < s.marker_n) o[s.marker_at + lane] = psy::raw_marker_byte(s.marker_at + lane);
+        if (s.len) psy::copy_shifted<1, false>(o + s.dst_off, in + in_off[i] + s.src_off, s.len, lane, 64);
+    }
+}
+
 // The issue / finish loop of a host call: chunk ci is issued on slot ci % kHostSlots once that
 // slot's previous chunk is done, and finished (its outputs and statuses read back) kHostSlots - 1
 // chunks later, so that up to kHostSlots chunks are in flight.
@@ -1931,10 +2007,16 @@ int host_encode(tdt_ctx *c, const uint8_t *h_in, const uint64_t *h_in_off, uint3
     // 64 KiB tiles instead of running in one workgroup) and a gather into the host buffer
     bool lb = h_in_off[n_msgs] - h_in_off[0] >= 16384ull * n_msgs;
     for (uint32_t i = 0; i < n_msgs && lb; ++i) lb = h_in_off[i + 1] - h_in_off[i] <= kBigMin;
+    // TDT_OPT_HOST_RAW_FALLBACK: always the slots, of n + 4 bytes each (the look-back kernel publishes a
+    // blob's TDT length from inside, so it cannot serve), and behind the chunk's encode the flag pass, the
+    // scan of the final lengths and the gather that takes a flagged blob from the chunk's input
+    const bool raw = c->host_raw_fallback;
+    if (raw) lb = false;
+    uint64_t fallen = 0;
     std::vector<Chunk> ch;
     const uint64_t cb = host_chunk_bytes(h_in_off, n_msgs);
     for (uint32_t m = 0; m < n_msgs;) {
-        ch.push_back(plan_chunk(h_in_off, m, n_msgs, true, !lb, ws, nullptr, cb));
+        ch.push_back(plan_chunk(h_in_off, m, n_msgs, true, !lb, ws, nullptr, cb, raw));
         m += ch.back().n;
     }
     if (int st = psy::grow(c->hbases, c->hbases_n, ch.size() + 1, psy::cap_exact(ch.size() + 1, c->hbases_n), dev_free,
@@ -1943,7 +2025,10 @@ int host_encode(tdt_ctx *c, const uint8_t *h_in, const uint64_t *h_in_off, uint3
     uint64_t base = 0;  // output bytes of the chunks finished so far
     bool capacity = false;
     const HostIn in{h_in, h_in_off, msgs, sizes, pin_in || msgs_pinned};
-    auto bound_of = [&](uint32_t i) { return tdt_encode_bound(h_in_off[i + 1] - h_in_off[i], ws); };
+    auto bound_of = [&](uint32_t i) {
+        const uint64_t len = h_in_off[i + 1] - h_in_off[i];
+        return raw ? psy::raw_blob_bytes(len) : tdt_encode_bound(len, ws);
+    };
     auto issue = [&](size_t ci) -> int {
         const Chunk &k = ch[ci];
         auto &h = c->hs[ci % kHostSlots];
@@ -1984,6 +2069,11 @@ int host_encode(tdt_ctx *c, const uint8_t *h_in, const uint64_t *h_in_off, uint3
             a.out_len = v.dlen;
             w.pws = &h.pw;
             if ((st = encode_common(c, psy::MODE_ENCODE, a, w))) return st;
+            if (raw) {  // (the count: the word behind the chunk's out_off, read back with it)
+                hipLaunchKernelGGL(host_raw_flag_kernel, dim3(1), dim3(1024), 0, s_ex, v.doff, v.dslot, v.dst, v.dlen,
+                                   reinterpret_cast<uint32_t *>(d + k.o_rf), v.dooff + k.n + 1, k.n);
+                HIPCHK(hipGetLastError());
+            }
             hipLaunchKernelGGL(host_scan_kernel, dim3(1), dim3(1024), 0, s_ex, v.dlen, v.dooff, k.n);
             HIPCHK(hipGetLastError());
         } else {
@@ -2000,8 +2090,13 @@ int host_encode(tdt_ctx *c, const uint8_t *h_in, const uint64_t *h_in_off, uint3
         if (k.scap) {
             const uint32_t P = (uint32_t)std::min<uint64_t>(64, std::max<uint64_t>(1, k.in_bytes / k.n / 16384));
             const uint32_t grid = (uint32_t)std::min<uint64_t>(2048, ((uint64_t)k.n * P + 3) / 4);
-            hipLaunchKernelGGL(host_gather_kernel, dim3(grid), dim3(256), 0, s_ex, d + k.o_sbuf, v.dslot, v.dlen, v.dooff,
-                               k.n, P, odst, c->hbases, (uint32_t)ci, out_cap, pin_out ? 1 : 0);
+            if (raw)
+                hipLaunchKernelGGL(host_raw_gather_kernel, dim3(grid), dim3(256), 0, s_ex, d, v.doff, d + k.o_sbuf, v.dslot,
+                                   v.dlen, reinterpret_cast<const uint32_t *>(d + k.o_rf), v.dooff, k.n, P, odst,
+                                   c->hbases, (uint32_t)ci, out_cap, pin_out ? 1 : 0);
+            else
+                hipLaunchKernelGGL(host_gather_kernel, dim3(grid), dim3(256), 0, s_ex, d + k.o_sbuf, v.dslot, v.dlen,
+                                   v.dooff, k.n, P, odst, c->hbases, (uint32_t)ci, out_cap, pin_out ? 1 : 0);
         } else {
             const uint32_t grid = (uint32_t)std::min<uint64_t>(1024, k.cap / 4096 + 1);
             hipLaunchKernelGGL(host_out_kernel, dim3(grid), dim3(256), 0, s_ex, d + k.o_out, v.dooff, k.n, odst,
@@ -2009,7 +2104,7 @@ int host_encode(tdt_ctx *c, const uint8_t *h_in, const uint64_t *h_in_off, uint3
         }
         HIPCHK(hipGetLastError());
         if (c->slot_streams) HIPCHK(hipEventRecord(h.evc, s_ex));
-        if ((st = small_copies(s_ex, d + k.o_ws + 4, h.flag, 4, v.dooff, pin_back(h, k), 8ull * (k.n + 1), v.dst,
+        if ((st = small_copies(s_ex, d + k.o_ws + 4, h.flag, 4, v.dooff, pin_back(h, k), 8ull * chunk_back_words(k), v.dst,
                                pin_status(h, k), 4ull * k.n)))
             return st;
         HIPCHK(hipEventRecord(h.ev, s_ex));
@@ -2025,6 +2120,7 @@ int host_encode(tdt_ctx *c, const uint8_t *h_in, const uint64_t *h_in_off, uint3
         if (capacity || base + total > out_cap) capacity = true;
         for (uint32_t i = 0; i < k.n; ++i) h_out_off[k.m0 + i] = base + (capacity ? 0 : pin_out_off[i]);
         if (h_status) std::memcpy(h_status + k.m0, pin_status(h, k), 4ull * k.n);
+        if (raw) fallen += pin_out_off[k.n + 1];
         // (the copy kernel has written the output: into h_out directly, or into the staging)
         if (!capacity && total && !pin_out) c->pool->copy(h_out + base, h.stage_out, total);
         if (!capacity) base += total;
@@ -2035,6 +2131,7 @@ int host_encode(tdt_ctx *c, const uint8_t *h_in, const uint64_t *h_in_off, uint3
     for (auto &h : c->hs)
         if (h.stream && (st = sync_slot(c, h))) return st;
     h_out_off[n_msgs] = base;
+    c->host_rf_count.store(fallen);
     if (capacity) return set_err(TDT_E_CAPACITY, "host output capacity exceeded");
     return TDT_OK;
 }
@@ -2192,7 +2289,8 @@ int host_one(tdt_ctx *c, bool encode, const uint8_t *h_in, const uint64_t *h_in_
     uint64_t osize;
     if (encode) {
         if (len > kOneMax || !psy::anyws_tuned(c->cfg.word_size)) return -1;  // (generic widths: the pipeline)
-        osize = tdt_encode_bound(len, c->cfg.word_size);
+        // (TDT_OPT_HOST_RAW_FALLBACK: a slot of n + 4 — a longer TDT blob leaves TDT_E_CAPACITY, below)
+        osize = c->host_raw_fallback ? psy::raw_blob_bytes(len) : tdt_encode_bound(len, c->cfg.word_size);
     } else {
         // a TDT blob of a generic word size is decoded by the pipeline's follow-up launch
         if (len >= 16) {
@@ -2280,15 +2378,28 @@ int host_one(tdt_ctx *c, bool encode, const uint8_t *h_in, const uint64_t *h_in_
     }
     if (!done) HIPCHK(hipStreamSynchronize(s));
     c->host_flags.fetch_or(A->flags);
-    const uint64_t olen = A->len;
-    const int32_t ost = A->status;
+    uint64_t olen = A->len;
+    int32_t ost = A->status;
+    // TDT_OPT_HOST_RAW_FALLBACK: the TDT blob did not fit n + 4 bytes — the host stores the message raw,
+    // from the caller's own bytes: no second launch, and no blob byte crosses PCIe
+    const bool fell = encode && c->host_raw_fallback && psy::raw_flagged(ost, olen, len, osize);
+    if (fell) {
+        olen = psy::raw_blob_bytes(len);
+        ost = TDT_OK;
+    }
     if (h_status) h_status[0] = ost;
     h_out_off[0] = 0;
     if (encode && olen > out_cap) {
         h_out_off[1] = 0;
         return set_err(TDT_E_CAPACITY, "host output capacity exceeded");
     }
-    if (olen) std::memcpy(h_out, hb + o_out, olen);
+    if (fell) {
+        for (uint32_t k = 0; k < psy::kRawMarkerBytes; ++k) h_out[k] = psy::raw_marker_byte(k);
+        std::memcpy(h_out + psy::kRawMarkerBytes, src, len);
+        c->host_rf_count.store(1);
+    } else if (olen) {
+        std::memcpy(h_out, hb + o_out, olen);
+    }
     h_out_off[1] = olen;
     return TDT_OK;
 }
@@ -2298,6 +2409,7 @@ int host_path(tdt_ctx *c, bool encode, const uint8_t *h_in, const uint64_t *h_in
               uint8_t *h_out, uint64_t out_cap, uint64_t *h_out_off, int32_t *h_status,
               const uint8_t *const *msgs = nullptr, const uint64_t *sizes = nullptr) {
     if (!c) return set_err(TDT_E_ARG, "null context");
+    if (encode) c->host_rf_count.store(0);  // (TDT_STAT_HOST_RAW_FALLBACKS: of the most recent host encode call)
     if (n_msgs == 0) {
         if (h_out_off) h_out_off[0] = 0;
         return TDT_OK;
@@ -2511,6 +2623,7 @@ int tdt_ctx_create(int device, const tdt_config *cfg, tdt_ctx **out) {
     x->small_main = flag("PSYNE_TDT_SMALL_MAIN");
     x->no_two_phase = flag("PSYNE_TDT_NO_TWO_PHASE");
     x->raw_fallback = flag("PSYNE_TDT_RAW_FALLBACK");
+    x->host_raw_fallback = flag("PSYNE_TDT_HOST_RAW_FALLBACK");
     x->no_one = flag("PSYNE_TDT_NO_ONE");
     x->one_wave = flag("PSYNE_TDT_ONE_WAVE");
     x->dout_sdma = flag("PSYNE_TDT_DOUT_SDMA");
@@ -2600,6 +2713,11 @@ int tdt_ctx_set_option(tdt_ctx *ctx, int option, uint64_t value) {
         ctx->pool.reset();
         return TDT_OK;
     }
+    if (option == TDT_OPT_HOST_RAW_FALLBACK) {  // (read by the host calls, under hmu)
+        std::lock_guard<std::mutex> hl(ctx->hmu);
+        ctx->host_raw_fallback = value != 0;
+        return TDT_OK;
+    }
     std::lock_guard<std::mutex> lk(ctx->mu);
     switch (option) {
         case TDT_OPT_LARGE_MIN: ctx->large_min = value; return TDT_OK;
@@ -2617,6 +2735,10 @@ int tdt_ctx_set_option(tdt_ctx *ctx, int option, uint64_t value) {
 
 int tdt_ctx_get_stat(tdt_ctx *ctx, int stat, uint64_t *value) {
     if (!ctx || !value) return set_err(TDT_E_ARG, "null context or value");
+    if (stat == TDT_STAT_HOST_RAW_FALLBACKS) {  // (host calls block: final when the call returned)
+        *value = ctx->host_rf_count.load();
+        return TDT_OK;
+    }
     std::lock_guard<std::mutex> lk(ctx->mu);
     if (stat == TDT_STAT_PACK_SCRATCH_BYTES) {
         *value = ctx->cp_bytes;
@@ -2653,6 +2775,11 @@ uint64_t tdt_encode_bound(uint64_t n, int32_t word_size) {
 uint64_t tdt_ctx_encode_bound(const tdt_ctx *ctx, uint64_t n) {
     if (!ctx) return psy::encode_bound_of(n, 4u, false);
     return psy::encode_bound_of(n, (uint32_t)ctx->cfg.word_size, ctx->raw_fallback);
+}
+
+uint64_t tdt_ctx_host_encode_bound(const tdt_ctx *ctx, uint64_t n) {
+    if (!ctx) return psy::encode_bound_of(n, 4u, false);
+    return psy::encode_bound_of(n, (uint32_t)ctx->cfg.word_size, ctx->host_raw_fallback);
 }
 
 

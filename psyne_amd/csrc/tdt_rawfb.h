@@ -17,9 +17,14 @@
 //           zero-length entries and fall out of the walk).  The piece of a blob goes to the blob's
 //           OWN slot: blob bytes 0..3 are the marker, byte k >= 4 is message byte k - 4.
 //
+// The host calls have an option of their own (TDT_OPT_HOST_RAW_FALLBACK) with the same rule and a
+// cheaper mechanism: the host pipeline's gather takes a flagged blob straight from the chunk's input on
+// its way to host memory (host_raw_flag_kernel, host_raw_gather_kernel in tdt_api.hip), so nothing of the
+// copy pass above runs there.  It shares the bound, raw_flagged and raw_span below.
+//
 // The bound, the decision and the segment arithmetic are plain host / device C++ here, so that a
-// host program can drive them over offset tables (tests/cpp/test_raw_fallback_segments.cpp); the
-// kernels are in tdt_rawfb.hip.
+// host program can drive them over offset tables (tests/cpp/test_raw_fallback_segments.cpp,
+// tests/cpp/test_host_raw_parts.cpp); the kernels are in tdt_rawfb.hip.
 #pragma once
 #include <stdint.h>
 
@@ -64,9 +69,10 @@ struct RawSeg {
     uint32_t marker_at, marker_n;
     uint64_t src_off, dst_off, len;
 };
-PSY_PACK_HD RawSeg raw_segment(uint64_t o0, uint64_t o1, PackPiece pc) {
-    const PackSeg s = pack_segment(o0, o1, pc);
-    const uint64_t b = s.src_off, e = b + s.len;  // the blob's own coordinates
+// Bytes [b, e) of a raw blob, in the blob's own coordinates (b <= e <= n + 4).  The host pipeline's
+// gather (TDT_OPT_HOST_RAW_FALLBACK, tdt_api.hip) calls it with a wave's part of the blob: part p of P
+// of a blob of l = n + 4 bytes is raw_span(l * p / P, l * (p + 1) / P).
+PSY_PACK_HD RawSeg raw_span(uint64_t b, uint64_t e) {
     RawSeg r{0u, 0u, 0u, 0u, 0u};
     if (b < kRawMarkerBytes) {
         r.marker_at = (uint32_t)b;
@@ -79,6 +85,10 @@ PSY_PACK_HD RawSeg raw_segment(uint64_t o0, uint64_t o1, PackPiece pc) {
         r.len = e - pb;
     }
     return r;
+}
+PSY_PACK_HD RawSeg raw_segment(uint64_t o0, uint64_t o1, PackPiece pc) {
+    const PackSeg s = pack_segment(o0, o1, pc);
+    return raw_span(s.src_off, s.src_off + s.len);
 }
 PSY_PACK_HD uint8_t raw_marker_byte(uint32_t k) { return (uint8_t)(kRawMarker >> (8u * k)); }
 

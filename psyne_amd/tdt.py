@@ -105,10 +105,13 @@ def _ptr(t) -> int:
 class TdtCodec:
     """Batched TDT codec bound to one HIP device."""
 
-    def __init__(self, config: TDTConfig | None = None, device: int = 0, lib=None, raw_fallback: bool = False):
+    def __init__(self, config: TDTConfig | None = None, device: int = 0, lib=None, raw_fallback: bool = False,
+                 host_raw_fallback: bool = False):
         """raw_fallback=True sets TDT_OPT_RAW_FALLBACK: the batch encodes store a message whose TDT blob
         would be longer than the message plus 4 bytes as its UNCP blob (marker + the raw bytes), so a blob
-        never exceeds n + 4 bytes, and the bounds, slots and allocations below follow."""
+        never exceeds n + 4 bytes, and the bounds, slots and allocations below follow.
+        host_raw_fallback=True sets TDT_OPT_HOST_RAW_FALLBACK: the same rule for encode_host (the host
+        pipeline and its one-message path), whose bound is host_encode_bound.  The two are independent."""
         self.config = config or TDTConfig()
         self.device = device
         self._lib = lib if lib is not None else _lib.load()  # `lib`: diagnostic builds only
@@ -118,6 +121,22 @@ class TdtCodec:
         self._h = h
         if raw_fallback:
             self.set_option(_lib.TDT_OPT_RAW_FALLBACK, 1)
+        if host_raw_fallback:
+            self.set_option(_lib.TDT_OPT_HOST_RAW_FALLBACK, 1)
+
+    @property
+    def host_raw_fallback(self) -> bool:
+        """Whether the context runs with TDT_OPT_HOST_RAW_FALLBACK, however it was set (asked of the
+        context, as raw_fallback is)."""
+        return self.host_encode_bound(0) == 4
+
+    def host_encode_bound(self, n: int) -> int:
+        """tdt_ctx_host_encode_bound: what encode_host may write for an n-byte message — n + 4 under
+        host_raw_fallback, else the TDT bound at this codec's word_size."""
+        f = getattr(self._lib, "tdt_ctx_host_encode_bound", None)
+        if f is None:  # (an older build chosen for an A/B run, which has no host raw fallback either)
+            return int(self._lib.tdt_encode_bound(n, self.config.word_size))
+        return int(f(self._h, n))
 
     @property
     def raw_fallback(self) -> bool:
@@ -687,8 +706,10 @@ class TdtCodec:
         data = np.ascontiguousarray(data, dtype=np.uint8)
         offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
         n = offsets.size - 1
-        # (the host calls ignore TDT_OPT_RAW_FALLBACK: their blobs reach the TDT bound)
-        cap = int(self._tdt_bounds(np.diff(offsets.astype(np.int64)), self.config.word_size).sum()) if n else 0
+        # (the host calls ignore TDT_OPT_RAW_FALLBACK: their blobs reach the TDT bound, unless the host
+        # option bounds them by n + 4 — tdt_ctx_host_encode_bound)
+        sizes = np.diff(offsets.astype(np.int64))
+        cap = int((sizes + 4 if self.host_raw_fallback else self._tdt_bounds(sizes, self.config.word_size)).sum()) if n else 0
         out = np.empty(max(cap, 1), np.uint8)
         out_off = np.zeros(n + 1, np.uint64)
         st = np.zeros(max(n, 1), np.int32)
@@ -715,9 +736,12 @@ class TDTCompressionProtocol:
     C ABI's host path (H2D, kernel, D2H).  Errors raise RuntimeError with the reference's
     messages ("TDT: Invalid encoded data size", "Invalid TDT magic number")."""
 
-    def __init__(self, config: TDTConfig | None = None, device: int = 0):
+    def __init__(self, config: TDTConfig | None = None, device: int = 0, host_raw_fallback: bool = False):
+        """host_raw_fallback=True: encode returns "UNCP" + the message where the TDT blob would be longer
+        (TDT_OPT_HOST_RAW_FALLBACK); such a message updates the ratio and time metrics no more than one
+        the policy routes to UNCP does."""
         self.config_ = config or TDTConfig()
-        self.codec = TdtCodec(self.config_, device)
+        self.codec = TdtCodec(self.config_, device, host_raw_fallback=host_raw_fallback)
         self._bandwidth = 100.0   # :352
         self._latency = 1.0       # :353
         self._cpu = 0.5           # :354
