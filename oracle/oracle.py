@@ -183,6 +183,11 @@ class Reference:
                                            C.POINTER(C.c_double), C.POINTER(C.c_int)]
         L.tdt_ref_bench.restype = C.c_double
         L.tdt_ref_bench.argtypes = [_u8p, _u64p, C.c_uint32, C.c_float, C.c_int, C.c_int, C.c_int, _u64p]
+        self.has_policy = hasattr(L, "tdt_ref_policy")
+        if self.has_policy:
+            L.tdt_ref_policy.restype = C.c_int
+            L.tdt_ref_policy.argtypes = [_u8p, C.c_size_t, C.c_float, C.c_int, C.c_double, C.c_double, C.c_size_t,
+                                         C.c_double, C.c_double, _i32p, _u8p, C.c_size_t, C.POINTER(C.c_size_t)]
         self.has_pinned = hasattr(L, "tdt_ref_bench_pinned")
         if self.has_pinned:
             L.tdt_ref_bench_pinned.restype = C.c_double
@@ -228,6 +233,23 @@ class Reference:
     def should_transform(self, n, word_size=4, bandwidth=10.0, cpu=0.5, min_tensor_size=1024) -> bool:
         d = np.zeros(max(n, 1), np.uint8)
         return bool(self.lib.tdt_ref_should_transform(_ptr(d), n, word_size, bandwidth, cpu, min_tensor_size))
+
+    def policy(self, data, word_size=4, bandwidth=10.0, cpu=0.5, min_tensor_size=1024,
+               bandwidth_threshold_mbps=100.0, cpu_usage_threshold=0.8, sample_fraction=1.0) -> tuple[bool, bytes]:
+        """(should_transform's answer, encode's blob) of one object configured with the two thresholds too."""
+        if not self.has_policy:
+            raise RuntimeError("oracle/_ref/libtdt_ref.so predates tdt_ref_policy: make -C oracle ref")
+        d = _bytes(data)
+        cap = encode_bound(d.size, max(word_size, 1)) + 64
+        out = np.empty(cap, np.uint8)
+        olen, verdict = C.c_size_t(0), C.c_int32(0)
+        dp = _ptr(d) if d.size else _ptr(np.zeros(1, np.uint8))
+        st = self.lib.tdt_ref_policy(dp, d.size, sample_fraction, word_size, bandwidth, cpu, min_tensor_size,
+                                     bandwidth_threshold_mbps, cpu_usage_threshold, C.byref(verdict), _ptr(out), cap,
+                                     C.byref(olen))
+        if st:
+            raise RuntimeError("ref policy status %d" % st)
+        return bool(verdict.value), out[: olen.value].tobytes()
 
     def bench(self, data: np.ndarray, offsets: np.ndarray, sample_fraction=0.3, word_size=4,
               threads=1, reps=1, cpus=None) -> tuple[float, int]:

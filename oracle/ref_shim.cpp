@@ -83,6 +83,27 @@ int tdt_ref_should_transform(const uint8_t *data, size_t n, int word_size,
     return p.should_transform(const_cast<uint8_t *>(data), n) ? 1 : 0;
 }
 
+// The routing decision under a full configuration: the two thresholds as well as the width and
+// min_tensor_size (tests/golden/make_policy_matrix.py).  *verdict is should_transform's answer, the
+// blob what encode makes of the message on the same object.  Returns 0, or -2 if cap is too small.
+int tdt_ref_policy(const uint8_t *data, size_t n, float sample_fraction, int word_size,
+                   double bandwidth_mbps, double cpu_usage, size_t min_tensor_size,
+                   double bandwidth_threshold_mbps, double cpu_usage_threshold, int *verdict,
+                   uint8_t *out, size_t cap, size_t *out_len) {
+    TDTConfig c = make_cfg(sample_fraction, word_size, min_tensor_size);
+    c.bandwidth_threshold_mbps = bandwidth_threshold_mbps;
+    c.cpu_usage_threshold = cpu_usage_threshold;
+    TDTCompressionProtocol p(c);
+    p.update_network_metrics(bandwidth_mbps, 1.0);
+    p.update_system_metrics(cpu_usage);
+    *verdict = p.should_transform(const_cast<uint8_t *>(data), n) ? 1 : 0;
+    std::vector<uint8_t> blob = p.encode(const_cast<uint8_t *>(data), n);
+    *out_len = blob.size();
+    if (blob.size() > cap) return -2;
+    std::memcpy(out, blob.data(), blob.size());
+    return 0;
+}
+
 // Decode one blob.  Returns 0, -1 on a reference exception (message via
 // tdt_ref_last_error), -2 if cap is too small.  Callers must not pass blobs on which
 // the reference has undefined behaviour (truncated headers/streams, bad mapping).

@@ -83,6 +83,8 @@ HOST_RAW_TEST_SRC = ROOT / "tests" / "cpp" / "test_host_raw_fallback.cpp"  # TDT
 HOST_RAW_TEST_BIN = ROOT / "tests" / "cpp" / "test_host_raw_fallback"
 HOST_RAW_PARTS_SRC = ROOT / "tests" / "cpp" / "test_host_raw_parts.cpp"  # the raw gather's part arithmetic (host only)
 HOST_RAW_PARTS_BIN = ROOT / "tests" / "cpp" / "test_host_raw_parts"
+POLICY_ROWS_SRC = ROOT / "tests" / "cpp" / "test_policy_rows.cpp"  # should_transform of the C++ drop-in class on the routing record's rows
+POLICY_ROWS_BIN = ROOT / "tests" / "cpp" / "test_policy_rows"
 SELFTEST_SRC = ROOT / "tests" / "native" / "selftest.hip"
 SELFTEST_LIB = ROOT / "tests" / "native" / "libtdt_selftest.so"
 
@@ -119,6 +121,14 @@ def build_tests(verbose: bool = False):
             [HOST_RAW_TEST_SRC.stat().st_mtime, LIB.stat().st_mtime] + [h.stat().st_mtime for h in hdrs]):
         cmd = ["g++", "-std=c++20", "-O2", "-I", str(ROOT / "include"), str(HOST_RAW_TEST_SRC), "-o",
                str(HOST_RAW_TEST_BIN), "-L", str(PKG), "-lpsyne_tdt", "-pthread", "-Wl,-rpath," + str(PKG),
+               "-Wl,-rpath,$ORIGIN/../../psyne_amd"]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        subprocess.check_call(cmd)
+    if not POLICY_ROWS_BIN.exists() or POLICY_ROWS_BIN.stat().st_mtime < max(
+            POLICY_ROWS_SRC.stat().st_mtime, LIB.stat().st_mtime, hdrs[0].stat().st_mtime):
+        cmd = ["g++", "-std=c++20", "-O2", "-I", str(ROOT / "include"), str(POLICY_ROWS_SRC), "-o",
+               str(POLICY_ROWS_BIN), "-L", str(PKG), "-lpsyne_tdt", "-pthread", "-Wl,-rpath," + str(PKG),
                "-Wl,-rpath,$ORIGIN/../../psyne_amd"]
         if verbose:
             print(" ".join(cmd), flush=True)

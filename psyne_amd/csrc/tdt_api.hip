@@ -2012,6 +2012,8 @@ int host_encode(tdt_ctx *c, const uint8_t *h_in, const uint64_t *h_in_off, uint3
     // scan of the final lengths and the gather that takes a flagged blob from the chunk's input
     const bool raw = c->host_raw_fallback;
     if (raw) lb = false;
+    // generic word sizes have no one-pass kernel (encode_common refuses them): their chunks are slotted
+    if (psy::anyws_generic(ws)) lb = false;
     uint64_t fallen = 0;
     std::vector<Chunk> ch;
     const uint64_t cb = host_chunk_bytes(h_in_off, n_msgs);
