@@ -35,7 +35,6 @@ SIZES = (1024, 1040, 5000, 8192, 8208, 20000, 65536, 70001)
 BIG = 140000
 FAMILIES = ("exact", "short", "long", "zero_odd", "half_odd", "alt_empty")
 MAXRUNS = (1, 2, 3, 8, 255)
-E_UNSUPPORTED = 6  # the library's status for a word size above 64 (the oracle decodes such a blob)
 
 Case = namedtuple("Case", "name ws family blob")
 

@@ -12,7 +12,6 @@ marked oracle-only: the oracle decodes lazily, the other two would expand 4 GiB.
 """
 from __future__ import annotations
 
-import hashlib
 import json
 import pathlib
 import sys
@@ -22,12 +21,9 @@ sys.path.insert(0, str(ROOT))
 from oracle.oracle import Oracle  # noqa: E402
 from tests import anyws_dec_tiled_cases as tc  # noqa: E402
 from tests.decode_cases import numpy_decode  # noqa: E402
+from tests.support import digest  # noqa: E402
 
 OUT = pathlib.Path(__file__).resolve().parent / "anyws_dec_tiled.json"
-
-
-def digest(b: bytes) -> str:
-    return hashlib.sha256(b).hexdigest()[:16]
 
 
 def main():

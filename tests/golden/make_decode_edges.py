@@ -14,7 +14,6 @@ three disagree; it must stay empty (a disagreement is a finding to write up, not
 """
 from __future__ import annotations
 
-import hashlib
 import json
 import pathlib
 import sys
@@ -23,12 +22,9 @@ ROOT = pathlib.Path(__file__).resolve().parents[2]
 sys.path.insert(0, str(ROOT))
 from oracle.oracle import Oracle, Reference  # noqa: E402
 from tests import decode_edge_cases as ec  # noqa: E402
+from tests.support import digest  # noqa: E402
 
 OUT = pathlib.Path(__file__).resolve().parent / "decode_edges.json"
-
-
-def digest(b: bytes) -> str:
-    return hashlib.sha256(b).hexdigest()[:16]
 
 
 def main():

@@ -18,7 +18,6 @@ and above the library's bound ("lib_status" = TDT_E_UNSUPPORTED).
 """
 from __future__ import annotations
 
-import hashlib
 import json
 import pathlib
 import sys
@@ -27,12 +26,9 @@ ROOT = pathlib.Path(__file__).resolve().parents[2]
 sys.path.insert(0, str(ROOT))
 from oracle.oracle import Oracle, Reference  # noqa: E402
 from tests import decode_cases as dc  # noqa: E402
+from tests.support import E_UNSUPPORTED, digest  # noqa: E402
 
 OUT = pathlib.Path(__file__).resolve().parent / "decode_fuzz.json"
-
-
-def digest(b: bytes) -> str:
-    return hashlib.sha256(b).hexdigest()[:16]
 
 
 def main():
@@ -53,7 +49,7 @@ def main():
             assert st != 0, c.name
             rec["ref"] = "ub"
         if is65:
-            rec["lib_status"] = dc.E_UNSUPPORTED
+            rec["lib_status"] = E_UNSUPPORTED
         if st == 0:
             rec["out"] = digest(out)
         records.append(rec)

@@ -17,7 +17,6 @@ PREMISE_CAP of a width's cases dropped stops the script too.
 """
 from __future__ import annotations
 
-import hashlib
 import json
 import pathlib
 import sys
@@ -28,13 +27,10 @@ ROOT = pathlib.Path(__file__).resolve().parents[2]
 sys.path.insert(0, str(ROOT))
 from oracle.oracle import Oracle, Reference  # noqa: E402
 from tests import encode_run_cases as ec  # noqa: E402
+from tests.support import digest  # noqa: E402
 
 OUT = pathlib.Path(__file__).resolve().parent / "encode_runs.json"
 PREMISE_CAP = 0.02
-
-
-def digest(b: bytes) -> str:
-    return hashlib.sha256(b).hexdigest()[:16]
 
 
 def main():

@@ -20,7 +20,6 @@ alone.  The script stops unless the CPU oracle gives the same answer and the sam
 hold (policy_cases.check_blob_lengths)."""
 from __future__ import annotations
 
-import hashlib
 import json
 import pathlib
 import sys
@@ -29,12 +28,9 @@ ROOT = pathlib.Path(__file__).resolve().parents[2]
 sys.path.insert(0, str(ROOT))
 from oracle.oracle import Oracle, Reference  # noqa: E402
 from tests import policy_cases as pc  # noqa: E402
+from tests.support import digest  # noqa: E402
 
 OUT = pathlib.Path(__file__).resolve().parent / "policy_matrix.json"
-
-
-def digest(b: bytes) -> str:
-    return hashlib.sha256(b).hexdigest()[:16]
 
 
 def main():

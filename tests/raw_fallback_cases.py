@@ -18,11 +18,12 @@ Kinds (one of each in every batch, interleaved, so that a fallback's neighbours 
                  the same trio under the single-stream mapping (every position in stream 0), where
                  E = 24 + 4 ws + 2 P for P runs of the message's bytes.
 """
-import hashlib
 import json
 import pathlib
 
 import numpy as np
+
+from tests.support import digest
 
 UNCP = b"PCNU"  # 0x554E4350, little-endian
 GOLDEN = pathlib.Path(__file__).resolve().parent / "golden" / "raw_fallback.json"
@@ -201,10 +202,10 @@ def seed_of(ws, n):
     return 20270000 + 1000 * ws + n % 997
 
 
-def digest(case):
+def case_digest(case):
     return dict(n=int(case["x"].size), plain_len=len(case["plain"]), falls=bool(case["falls"]),
-                x=hashlib.sha256(case["x"].tobytes()).hexdigest()[:16],
-                want=hashlib.sha256(case["want"]).hexdigest()[:16])
+                x=digest(case["x"].tobytes()),
+                want=digest(case["want"]))
 
 
 def all_configs():
@@ -224,10 +225,10 @@ def golden_table(orc):
     table = {}
     for ws, n, _ in all_configs():
         for c in batch(orc, ws, n, seed_of(ws, n)):
-            table[c["name"]] = digest(c)
+            table[c["name"]] = case_digest(c)
     for ws, n in MAPPED_TRIOS:
         for c in mapped_trio(orc, ws, n):
-            table[c["name"]] = digest(c)
+            table[c["name"]] = case_digest(c)
     return table
 
 

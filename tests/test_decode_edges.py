@@ -3,7 +3,6 @@
 reference exists): the generator still builds the recorded blobs, the CPU oracle still gives the
 recorded bytes with status 0, and a plain numpy decoder agrees with it.  Pins the yardstick the GPU
 tests of those blobs (tests/test_gpu_decode_edges.py) compare with."""
-import hashlib
 import json
 
 import pytest
@@ -11,10 +10,7 @@ import pytest
 from oracle.oracle import Oracle, Reference
 from tests import decode_edge_cases as ec
 from tests.golden_cases import GOLDEN
-
-
-def digest(b: bytes) -> str:
-    return hashlib.sha256(b).hexdigest()[:16]
+from tests.support import digest
 
 
 @pytest.fixture(scope="module")

@@ -3,7 +3,6 @@
 reference exists): the generator still builds the recorded blobs, the CPU oracle still gives the
 recorded statuses and bytes, and a plain numpy decoder agrees with it.  Pins the yardstick the
 GPU tests of those blobs (tests/test_gpu_decode_fuzz.py) compare with."""
-import hashlib
 import json
 
 import pytest
@@ -11,10 +10,7 @@ import pytest
 from oracle.oracle import Oracle, Reference
 from tests import decode_cases as dc
 from tests.golden_cases import GOLDEN
-
-
-def digest(b: bytes) -> str:
-    return hashlib.sha256(b).hexdigest()[:16]
+from tests.support import E_UNSUPPORTED, digest
 
 
 @pytest.fixture(scope="module")
@@ -53,7 +49,7 @@ def test_oracle_reproduces_every_status_and_output(record, decoded):
         assert (st["magic"], st["ws0"], st["map_eq_ns"], st["map_negative"]) == (2, 7, 4, 4), ws
         assert st["msize_short"] in (3, 4) and st["len0_past_end"] == 3 and st["cut_last_byte"] == 3, ws
         assert st["ws65"] == 0, ws
-    assert all(r.get("lib_status") == dc.E_UNSUPPORTED for r in record if r["name"].endswith("_ws65"))
+    assert all(r.get("lib_status") == E_UNSUPPORTED for r in record if r["name"].endswith("_ws65"))
 
 
 def test_numpy_decoder_equals_oracle(decoded):

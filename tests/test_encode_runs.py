@@ -5,7 +5,6 @@ recorded blobs, a plain numpy run-length encoder agrees with it, the encode emul
 (tools/emulate_encode.py) agrees with it on the new edges, and the cap-exclusion rule of pass A1,
 restated for every tuned width and stream split, implies what the kernel relies on.  Pins the
 yardstick the GPU tests of those messages (tests/test_gpu_encode_runs.py) compare with."""
-import hashlib
 import json
 import struct
 
@@ -15,10 +14,7 @@ import pytest
 from oracle.oracle import Oracle, Reference
 from tests import encode_run_cases as ec
 from tests.golden_cases import GOLDEN
-
-
-def digest(b: bytes) -> str:
-    return hashlib.sha256(b).hexdigest()[:16]
+from tests.support import digest
 
 
 @pytest.fixture(scope="module")

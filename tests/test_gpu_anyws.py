@@ -5,75 +5,20 @@ compared with the CPU oracle byte for byte and status for status."""
 import numpy as np
 import pytest
 
-from oracle.oracle import Oracle
 from tests.anyws_cases import WIDTHS, from_streams, intended_mapping, kernel_chunk, load_anyws, low_pattern
+from tests.support import E_CAPACITY, E_CONFIG, E_UNSUPPORTED, offsets_of
 
 torch = pytest.importorskip("torch")
+from tests.gpu_support import decode_slotted, encode_slotted, make_codec, orc  # noqa: E402, F401
+
 pytestmark = pytest.mark.gpu
 
 PHASES = ((0, 0), (3, 3), (5, 9), (16, 0))  # input / output byte phases (as test_gpu_parity's copy test)
-E_CAPACITY, E_UNSUPPORTED, E_CONFIG = 5, 6, 8
-
-
-@pytest.fixture(scope="module")
-def orc():
-    return Oracle()
 
 
 @pytest.fixture(scope="module")
 def cases():
     return load_anyws()
-
-
-def make_codec(ws):
-    from psyne_amd import TDTConfig, TdtCodec
-    codec = TdtCodec(TDTConfig(sample_fraction=1.0, word_size=ws))
-    codec.set_metrics(10.0, 1.0, 0.5)  # bandwidth < 100 Mbps: compression on
-    return codec
-
-
-def offsets_of(parts):
-    off = np.zeros(len(parts) + 1, np.int64)
-    off[1:] = np.cumsum([len(p) for p in parts])
-    return off
-
-
-def at_phase(buf: np.ndarray, phase: int, pad: int = 64):
-    """buf on the GPU at `phase` bytes past a 256-byte aligned address, with a guard after it."""
-    t = torch.full((phase + buf.size + pad,), 0xA5, dtype=torch.uint8, device="cuda")
-    v = t[phase:phase + max(buf.size, 1)]
-    if buf.size:
-        v[:buf.size] = torch.from_numpy(np.array(buf, dtype=np.uint8)).cuda()  # (a writable copy)
-    return t, v
-
-
-def encode_slotted(codec, msgs, pi=0, po=0, slots=None):
-    """(blobs, statuses, lengths) of a slotted encode with input / output at byte phases pi / po."""
-    data = np.concatenate([np.asarray(m, np.uint8) for m in msgs]) if msgs else np.zeros(0, np.uint8)
-    off = torch.from_numpy(offsets_of(msgs)).cuda()
-    _, d = at_phase(data, pi)
-    sl = codec.encode_slots(off) if slots is None else torch.from_numpy(np.asarray(slots, np.int64)).cuda()
-    total = int(sl[-1].item())
-    raw = torch.full((po + total + 64,), 0xA5, dtype=torch.uint8, device="cuda")
-    out, _, lens, st = codec.encode_into(d, off, slots=sl, out=raw[po:po + max(total, 1)])
-    torch.cuda.synchronize()
-    assert int((raw[:po] != 0xA5).sum()) == 0 and int((raw[po + total:] != 0xA5).sum()) == 0
-    o, s, l, t = out.cpu().numpy(), sl.cpu().numpy(), lens.cpu().numpy(), st.cpu().numpy()
-    return [o[s[i]:s[i] + l[i]].tobytes() for i in range(len(msgs))], list(t[:len(msgs)]), list(l[:len(msgs)])
-
-
-def decode_slotted(codec, blobs, pi=0, po=0, slots=None):
-    data = np.frombuffer(b"".join(blobs), np.uint8)
-    off = torch.from_numpy(offsets_of(blobs)).cuda()
-    _, d = at_phase(data, pi)
-    sl = codec.decode_slots(d, off) if slots is None else torch.from_numpy(np.asarray(slots, np.int64)).cuda()
-    total = int(sl[-1].item())
-    raw = torch.full((po + total + 64,), 0xA5, dtype=torch.uint8, device="cuda")
-    out, _, lens, st = codec.decode_into(d, off, slots=sl, out=raw[po:po + max(total, 1)])
-    torch.cuda.synchronize()
-    assert int((raw[:po] != 0xA5).sum()) == 0 and int((raw[po + total:] != 0xA5).sum()) == 0
-    o, s, l, t = out.cpu().numpy(), sl.cpu().numpy(), lens.cpu().numpy(), st.cpu().numpy()
-    return [o[s[i]:s[i] + l[i]].tobytes() for i in range(len(blobs))], list(t[:len(blobs)]), list(l[:len(blobs)])
 
 
 def test_context_creation():

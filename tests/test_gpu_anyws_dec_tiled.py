@@ -10,28 +10,21 @@ import struct
 import numpy as np
 import pytest
 
-from oracle.oracle import Oracle
 from tests import anyws_dec_tiled_cases as tc
 from tests import anyws_tiled_cases as enc_cases
 from tests import decode_cases as dc
-from tests.test_gpu_decode_fuzz import (FILL, GAP, GUARD, TAIL, Expect, compare, guarded_output, i64, packed_input, report,
-                                        run_slotted)
-from tests.test_gpu_mixed_ws import canaries_intact, guarded
+from tests.support import E_CAPACITY, report
 
 torch = pytest.importorskip("torch")
+from tests.gpu_support import _gpu, canaries_intact, guarded, i64, orc  # noqa: E402, F401
+from tests.decode_check import (Expect, FILL, GAP, GUARD, TAIL, compare, guarded_output, packed_input,  # noqa: E402
+                                run_slotted)
+
 pytestmark = pytest.mark.gpu
 
-E_CAPACITY = 5
 OPT_LARGE_MIN, OPT_TILE_CAP, OPT_NO_TWO_PHASE, OPT_ANY_DEC_TILED = 1, 2, 5, 9
 TILE = tc.kernel_tile()
 SWITCH = (1, 0)  # TDT_OPT_ANY_DEC_TILED: the tile pipeline, then the one-workgroup kernel
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _gpu():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    from psyne_amd import _lib
-    _lib.load()
 
 
 def make_codec(tiled, large_min=TILE, ws=4):
@@ -47,11 +40,6 @@ def expect_of(orc, name, ws, blob):
     st, out = orc.decode(blob)
     assert st == 0, name
     return Expect((name, ws, "tiled", blob), 0, out)
-
-
-@pytest.fixture(scope="module")
-def orc():
-    return Oracle()
 
 
 @pytest.fixture(scope="module")

@@ -6,23 +6,19 @@ messages of two to five tiles run the plan, histogram, mapping, count, scan and 
 import numpy as np
 import pytest
 
-from oracle.oracle import Oracle, encode_bound
+from oracle.oracle import encode_bound
 from tests import anyws_tiled_cases as tc
-from tests.test_gpu_anyws import decode_slotted, encode_slotted, offsets_of
-from tests.test_gpu_mixed_ws import canaries_intact, guarded, i32, i64, mask_of, own, ptrs
+from tests.support import E_CAPACITY, bits_of, mask_of, offsets_of
 
 torch = pytest.importorskip("torch")
+from tests.gpu_support import (canaries_intact, decode_slotted, encode_slotted, guarded, i32, i64,  # noqa: E402, F401
+                               orc, own, ptrs, u64)
+
 pytestmark = pytest.mark.gpu
 
-E_CAPACITY = 5
 OPT_LARGE_MIN, OPT_TILE_CAP, OPT_PACK_SIZES_FIRST, OPT_ANY_TILED = 1, 2, 7, 8
 TILE = tc.kernel_tile()
 SWITCH = (1, 0)  # TDT_OPT_ANY_TILED: the tile pipeline, then the one-workgroup kernel
-
-
-@pytest.fixture(scope="module")
-def orc():
-    return Oracle()
 
 
 def make_codec(ws, tiled, large_min=TILE, bandwidth=10.0):
@@ -32,14 +28,6 @@ def make_codec(ws, tiled, large_min=TILE, bandwidth=10.0):
     codec.set_option(OPT_LARGE_MIN, large_min)
     codec.set_option(OPT_ANY_TILED, tiled)
     return codec
-
-
-def u64(values):
-    return torch.from_numpy(np.array([int(v) for v in values], dtype=np.uint64).view(np.int64)).cuda()
-
-
-def bits_of(mapping):
-    return sum(int(m) << p for p, m in enumerate(mapping))
 
 
 def plain(orc, m, ws, **kw):

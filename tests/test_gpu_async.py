@@ -13,30 +13,19 @@ import time
 
 import numpy as np
 import pytest
+from tests.support import gradient
 
 torch = pytest.importorskip("torch")
+from tests.gpu_support import make_codec  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-
-
-def _codec():
-    from psyne_amd import TDTConfig, TdtCodec
-    c = TdtCodec(TDTConfig(sample_fraction=1.0))
-    c.set_metrics(10.0, 1.0, 0.5)
-    return c
-
-
-def _gradient(rng, n):
-    x = rng.normal(0, 0.01, n // 4).astype(np.float32)
-    x[rng.random(x.size) < 0.7] = 0
-    return x.view(np.uint8)
 
 
 def _mixed(seed):
     rng = np.random.default_rng(seed)
     sizes = [1 << 20, 300 * 1024, 64, 1024, 2048, 4096, 65536, 100000, 1 << 19, 3, 0, 8192 + 4]
     sizes += [int(s) for s in 64 * rng.integers(1, 64, 200)]
-    msgs = [_gradient(rng, s) if s % 4 == 0 and s >= 64 else rng.integers(0, 256, s, dtype=np.uint8) for s in sizes]
+    msgs = [gradient(rng, s) if s % 4 == 0 and s >= 64 else rng.integers(0, 256, s, dtype=np.uint8) for s in sizes]
     off = np.zeros(len(msgs) + 1, np.int64)
     off[1:] = np.cumsum([m.size for m in msgs])
     return np.concatenate(msgs), off
@@ -84,7 +73,7 @@ class _Slotted:
 
 
 def test_slotted_calls_never_wait():
-    codec = _codec()
+    codec = make_codec()
     n, mb = 32768, 65536  # 2 GiB of C3-style messages
     g = torch.Generator(device="cuda")
     g.manual_seed(5)
@@ -116,7 +105,7 @@ def test_slotted_graph_replay_equals_eager():
     data_h, off_h = _mixed(31)
     data = torch.from_numpy(data_h).cuda()
     off = torch.from_numpy(off_h).cuda()
-    codec = _codec()
+    codec = make_codec()
     s = _Slotted(codec, data, off)
     s.run()
     torch.cuda.synchronize()
@@ -143,7 +132,7 @@ def test_capture_on_cold_context_is_refused():
     data_h, off_h = _mixed(32)
     data = torch.from_numpy(data_h).cuda()
     off = torch.from_numpy(off_h).cuda()
-    s = _Slotted(_codec(), data, off)
+    s = _Slotted(make_codec(), data, off)
     torch.cuda.synchronize()
     gr = torch.cuda.CUDAGraph()
     with pytest.raises(TdtError) as ei:
@@ -159,11 +148,11 @@ def test_batches_of_other_shapes_on_a_warm_context():
     as a round-trip mismatch)."""
     from oracle.oracle import Oracle
     orc = Oracle()
-    codec = _codec()
+    codec = make_codec()
     rng = np.random.default_rng(33)
     shapes = [[65536] * 8, [1024] * 3000 + [65536] * 40 + [1 << 20] * 6, [2048] * 50, [600 * 1024] * 12 + [512] * 10]
     for k, sizes in enumerate(shapes):
-        msgs = [_gradient(rng, sz) for sz in sizes]
+        msgs = [gradient(rng, sz) for sz in sizes]
         off_h = np.zeros(len(msgs) + 1, np.int64)
         off_h[1:] = np.cumsum(sizes)
         data_h = np.concatenate(msgs)
@@ -188,7 +177,7 @@ def test_graph_replay_after_workspace_growth():
     data_h, off_h = _mixed(34)
     data = torch.from_numpy(data_h).cuda()
     off = torch.from_numpy(off_h).cuda()
-    codec = _codec()
+    codec = make_codec()
     s = _Slotted(codec, data, off)
     s.run()
     torch.cuda.synchronize()
@@ -199,7 +188,7 @@ def test_graph_replay_after_workspace_growth():
     # a batch with 1,100 messages of 300 KiB (the starting budget holds 1,024 large messages),
     # twice: the second call grows the large-message and plan workspaces from the first's counts
     rng = np.random.default_rng(35)
-    big = [_gradient(rng, 300 * 1024) for _ in range(1100)]
+    big = [gradient(rng, 300 * 1024) for _ in range(1100)]
     boff = np.zeros(len(big) + 1, np.int64)
     boff[1:] = np.cumsum([m.size for m in big])
     bdata = torch.from_numpy(np.concatenate(big)).cuda()

@@ -11,33 +11,18 @@ import numpy as np
 import pytest
 
 from oracle.oracle import Oracle
+from tests.support import gradient
 
 torch = pytest.importorskip("torch")
+from tests.gpu_support import _gpu, make_codec  # noqa: E402, F401
+
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _gpu():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-
-
-def _codec():
-    from psyne_amd import TDTConfig, TdtCodec
-    c = TdtCodec(TDTConfig(sample_fraction=1.0))
-    c.set_metrics(10.0, 1.0, 0.5)
-    return c
-
-
-def _gradient(rng, n):
-    x = rng.normal(0, 0.01, n // 4).astype(np.float32)
-    x[rng.random(n // 4) < 0.7] = 0
-    return x.view(np.uint8)
 
 
 def _batch(seed):
     rng = np.random.default_rng(seed)
     sizes = [64, 1024, 4096, 65536, 100 * 1024, 300 * 1024, 4, 0, 2048, 1 << 20, 64 * 3, 70000 * 4]
-    msgs = [(_gradient(rng, s) if s % 4 == 0 and s >= 64 else rng.integers(0, 256, s, dtype=np.uint8))
+    msgs = [(gradient(rng, s) if s % 4 == 0 and s >= 64 else rng.integers(0, 256, s, dtype=np.uint8))
             for s in sizes]
     off = np.zeros(len(msgs) + 1, np.int64)
     off[1:] = np.cumsum([m.size for m in msgs])
@@ -59,7 +44,7 @@ def _both(codec, fn):
 
 @pytest.mark.parametrize("seed", [1, 2])
 def test_two_phase_matches_lookback_and_oracle(seed):
-    codec = _codec()
+    codec = make_codec()
     msgs, data, off = _batch(seed)
     d = torch.from_numpy(data).cuda()
     o = torch.from_numpy(off).cuda()
@@ -96,7 +81,7 @@ def test_two_phase_matches_lookback_and_oracle(seed):
 def test_two_phase_capacity_semantics():
     """out_cap below the total: the same statuses (TDT_E_CAPACITY for blobs past the end),
     offsets (the full prefix sum) and fitting bytes on both paths."""
-    codec = _codec()
+    codec = make_codec()
     msgs, data, off = _batch(3)
     d = torch.from_numpy(data).cuda()
     o = torch.from_numpy(off).cuda()
@@ -122,7 +107,7 @@ def test_two_phase_capacity_semantics():
 def test_compacted_under_graph_capture():
     """Under hipGraph stream capture the compacted API takes the one-pass look-back kernels
     (the two-phase path reads back on the host); the replayed graph gives the eager bytes."""
-    codec = _codec()
+    codec = make_codec()
     msgs, data, off = _batch(4)
     d = torch.from_numpy(data).cuda()
     o = torch.from_numpy(off).cuda()
@@ -165,7 +150,7 @@ def test_lookback_resident_only_kernel(variant):
     sizes = list(rng.integers(1024, 4097, 240) * 16)
     if variant == "odd_size":
         sizes[100] += 4  # a partial 16-byte group
-    msgs = [_gradient(rng, int(s)) for s in sizes]
+    msgs = [gradient(rng, int(s)) for s in sizes]
     lead = 4 if variant == "unaligned" else 0
     off = np.zeros(len(msgs) + 1, np.int64)
     off[0] = lead
@@ -173,7 +158,7 @@ def test_lookback_resident_only_kernel(variant):
     data = np.zeros(int(off[-1]), np.uint8)
     for i, m in enumerate(msgs):
         data[off[i]:off[i + 1]] = m
-    codec = _codec()
+    codec = make_codec()
     d = torch.from_numpy(data).cuda()
     o = torch.from_numpy(off).cuda()
     out, eoff, st = codec.encode_batch(d, o)

@@ -12,11 +12,13 @@ import numpy as np
 import pytest
 
 from oracle.oracle import Oracle, encode_bound
+from tests.support import CANARY, gradient, offsets, phased_slots
 
 torch = pytest.importorskip("torch")
+from tests.gpu_support import _gpu, dev, i64  # noqa: E402, F401
+
 pytestmark = pytest.mark.gpu
 
-CANARY = 0xA5
 # below, at and above one, two, ... five 16-byte chunks, and around a wave's and the 4 KiB boundary
 EDGES = [255, 256, 257, 4095, 4096, 4097]
 LENGTHS = list(range(81)) + EDGES + list(range(80, -1, -1)) + EDGES + [13, 29, 47, 61, 5, 77, 3, 19, 1, 0]
@@ -24,30 +26,11 @@ BIG = 70000 * 4  # one message above 64 KiB: the two-phase compaction, the host 
 ALL16 = set(range(16))
 
 
-@pytest.fixture(scope="module", autouse=True)
-def _gpu():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    from psyne_amd import _lib
-    _lib.load()
-
-
 def make_codec(policy=True):
     from psyne_amd import TDTConfig, TdtCodec
     c = TdtCodec(TDTConfig(sample_fraction=1.0))
     c.set_metrics(10.0 if policy else 1e6, 1.0, 0.5)  # (a bandwidth above the threshold: every message stays UNCP)
     return c
-
-
-def gradient(rng, n):
-    x = rng.normal(0, 0.01, n // 4).astype(np.float32)
-    x[rng.random(n // 4) < 0.7] = 0
-    return x.view(np.uint8)
-
-
-def offsets(lengths):
-    off = np.zeros(len(lengths) + 1, np.int64)
-    off[1:] = np.cumsum(np.asarray(lengths, dtype=np.int64))
-    return off
 
 
 @pytest.fixture(scope="module")
@@ -65,14 +48,6 @@ def ref():
     return {"msgs": msgs, "uncp": uncp, "mixed": mixed, "blobs": blobs}
 
 
-def dev(a):
-    return torch.from_numpy(np.array(a)).cuda()  # (a writable copy: some inputs are views of bytes)
-
-
-def i64(values):
-    return torch.tensor([int(v) for v in values], dtype=torch.int64, device="cuda")
-
-
 def canary_buffer(nbytes):
     t = torch.full((nbytes,), CANARY, dtype=torch.uint8, device="cuda")
     assert t.data_ptr() % 16 == 0
@@ -85,19 +60,6 @@ def image(nbytes, places, parts):
     for p, b in zip(places, parts):
         want[p:p + len(b)] = np.frombuffer(bytes(b), np.uint8)
     return want
-
-
-def phased_slots(sizes, lead, step=5):
-    """Slot i of sizes[i] bytes starting (lead + step i) mod 16 bytes past a 16-byte boundary (step is
-    odd: sixteen consecutive slots take sixteen residues), 16 or more bytes after the slot before:
-    (slot table of n + 1 entries, its end).  The table's slots reach up to the next one's start, so
-    the gap belongs to the slot and must stay untouched all the same."""
-    at, table = 64, []
-    for i, s in enumerate(sizes):
-        at += (lead + step * i - at) % 16
-        table.append(at)
-        at += s + 16
-    return np.asarray(table + [at], np.int64), at + 64
 
 
 # ------------------------------------------------------------------ 1: UNCP passthrough, slotted

@@ -16,18 +16,14 @@ import pytest
 
 from oracle.oracle import Oracle
 from tests import decode_edge_cases as ec
-from tests.test_gpu_decode_fuzz import (FILL, GUARD, TAIL, Expect, check_sizes, compare, guarded_output, i64,
-                                        make_codec, packed_input, report, run_slotted)
+from tests.support import report
 
 torch = pytest.importorskip("torch")
+from tests.gpu_support import _gpu, i64, make_codec  # noqa: E402, F401
+from tests.decode_check import (Expect, FILL, GUARD, TAIL, check_sizes, compare, guarded_output,  # noqa: E402
+                                packed_input, run_slotted)
+
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _gpu():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    from psyne_amd import _lib
-    _lib.load()
 
 
 class EdgeExpect(Expect):

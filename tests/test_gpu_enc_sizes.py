@@ -12,14 +12,14 @@ import pytest
 from oracle.oracle import encode_bound
 from tests import mapping_band_cases as mb
 from tests.anyws_cases import low_pattern
-# the shapes of the scattered tests: their sizes, leads, helpers and the shared batch
-from tests.test_gpu_mixed_ws import (CANARY, SIZES, WIDTHS, _gpu, address_order, batch, i32, i64, make_codec,  # noqa: F401
-                                     mask_of, oracle_blob, orc, own, ptrs, records, run_vw)
+from tests.support import CANARY, E_ARG, E_CAPACITY, E_CAPTURE, E_CONFIG, E_UNSUPPORTED, address_order, mask_of, offsets
 
 torch = pytest.importorskip("torch")
+from tests.gpu_support import _gpu, i32, i64, make_codec, orc, own, packed_blobs, ptrs  # noqa: E402, F401
+from tests.mixed_ws_cases import WIDTHS, batch, oracle_blob, records, run_vw  # noqa: E402, F401
+
 pytestmark = pytest.mark.gpu
 
-E_CAPACITY, E_UNSUPPORTED, E_CONFIG, E_ARG, E_CAPTURE = 5, 6, 8, 11, 12
 OPT_LARGE_MIN, OPT_TILE_CAP, OPT_PACK_SIZES_FIRST = 1, 2, 7
 
 
@@ -37,10 +37,6 @@ def sizes_v(codec, tensors, widths=None, mask=0):
                                     word_sizes=None if widths is None else i32(widths), width_mask=mask)
     torch.cuda.synchronize()
     return enc.cpu().numpy().tolist(), st.cpu().numpy().tolist()
-
-
-def cumsum0(lengths):
-    return np.concatenate([[0], np.cumsum(np.asarray(lengths, dtype=np.int64))])
 
 
 # ------------------------------------------------------------------------------- 1: every class, every width
@@ -68,7 +64,7 @@ def test_sizes_one_width_scattered_and_contiguous(batch, w):
     assert (enc, st) == (want, [0] * len(idx))
     # the same messages back to back in one buffer (so at other alignments)
     data = torch.from_numpy(np.concatenate([batch["msgs"][i] for i in idx])).cuda()
-    off = torch.from_numpy(cumsum0([len(batch["msgs"][i]) for i in idx])).cuda()
+    off = torch.from_numpy(offsets([len(batch["msgs"][i]) for i in idx])).cuda()
     enc, st = codec.encoded_sizes(data, off)
     torch.cuda.synchronize()
     assert enc.cpu().numpy().tolist() == want and st.cpu().numpy().tolist() == [0] * len(idx)
@@ -338,18 +334,13 @@ def canaries_around(t, view):
     return bool((h[:b] == CANARY).all() and (h[b + view.numel():] == CANARY).all())
 
 
-def packed_blobs(out, off):
-    oh, off = out.cpu().numpy(), off.cpu().numpy()
-    return [oh[off[k]:off[k + 1]].tobytes() for k in range(off.size - 1)], off
-
-
 @pytest.mark.parametrize("w", [4, 12])
 def test_sizes_first_vp_one_width(batch, w):
     idx = [i for i, x in enumerate(batch["ws"]) if x == w]
     n = len(idx)
     tensors = [batch["tensors"][i] for i in idx]
     sizes = [t.numel() for t in tensors]
-    off_want = cumsum0([len(batch["blobs"][i]) for i in idx])
+    off_want = offsets([len(batch["blobs"][i]) for i in idx])
     cap = int(off_want[-1])  # exactly what the blobs need
     t, out = inside(cap)
     codec = make_codec(w)
@@ -433,7 +424,7 @@ def test_sizes_first_vp_out_cap_cuts_the_batch(batch, where):
     n = len(idx)
     tensors = [batch["tensors"][i] for i in idx]
     sizes = [t.numel() for t in tensors]
-    off_want = cumsum0([len(batch["blobs"][i]) for i in idx])
+    off_want = offsets([len(batch["blobs"][i]) for i in idx])
     want = np.frombuffer(b"".join(batch["blobs"][i] for i in idx), np.uint8)
     k = n // 2
     cap = {"at a blob's end": int(off_want[k + 1]), "one before": int(off_want[k + 1]) - 1,
@@ -536,7 +527,7 @@ def test_encode_tensors_packed_exact(orc):
     assert out.numel() == int(off[-1]) == sum(len(b) for b in want)
     assert st.cpu().numpy().tolist() == [0] * len(tensors)
     got, offh = packed_blobs(out, off)
-    assert offh.tolist() == cumsum0([len(b) for b in want]).tolist()
+    assert offh.tolist() == offsets([len(b) for b in want]).tolist()
     assert got == want
     fresh = [torch.full_like(t, 1) for t in tensors]
     dl, ds = codec.decode_tensors(out, off, off[1:] - off[:-1], fresh)

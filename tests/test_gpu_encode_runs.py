@@ -17,19 +17,15 @@ import pytest
 from oracle.oracle import Oracle
 from tests import encode_run_cases as ec
 from tests.golden_cases import GOLDEN
+from tests.support import report
 
 torch = pytest.importorskip("torch")
+from tests.gpu_support import _gpu, i32, i64, make_codec  # noqa: E402, F401
+
 pytestmark = pytest.mark.gpu
 
 GUARD, FILL, TAIL, GAP = 0xA5, 0xFF, 4096, 16
 VW_WIDTHS = (1, 2, 4, 8, 16, 3, 12)  # one encode_vw call takes at most 8 widths
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _gpu():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    from psyne_amd import _lib
-    _lib.load()
 
 
 class Expect:
@@ -58,21 +54,6 @@ def of_width(batch, ws):
     exp = [e for e in batch if e.ws == ws]
     assert exp
     return exp
-
-
-def make_codec(ws, hint=None, options=()):
-    from psyne_amd import TDTConfig, TdtCodec
-    c = TdtCodec(TDTConfig(sample_fraction=1.0, word_size=ws))
-    c.set_metrics(10.0, 1.0, 0.5)
-    if hint is not None:
-        c.set_size_hint(hint)
-    for opt, value in options:
-        c.set_option(opt, value)
-    return c
-
-
-def report(bad):
-    assert not bad, "%d mismatches, the first: %s" % (len(bad), "; ".join(bad[:8]))
 
 
 def prefix(values):
@@ -239,12 +220,6 @@ def test_route_b_slotted(batch, ws):
 
 
 # ------------------------------------------------------------------ D: scattered
-def i64(values):
-    return torch.tensor([int(v) for v in values], dtype=torch.int64, device="cuda")
-
-
-def i32(values):
-    return torch.tensor([int(v) for v in values], dtype=torch.int32, device="cuda")
 
 
 @pytest.fixture(scope="module")
@@ -265,7 +240,7 @@ def mixed(batch):
     return [exp[i] for i in np.random.default_rng(ec.SEED).permutation(len(exp))]
 
 
-def mask_of(widths):
+def width_mask(widths):
     from psyne_amd import TdtCodec
     return TdtCodec.width_mask(widths)
 
@@ -299,7 +274,7 @@ def test_route_d_encode_vw(batch, scattered):
     outs = [torch.full((64 + e.size + 64,), GUARD, dtype=torch.uint8, device="cuda") for e in exp]
     codec = make_codec(4)
     ln, st = codec.encode_vw(i64(scattered[e.name].data_ptr() for e in exp), i64(e.n for e in exp),
-                             i32(e.ws for e in exp), mask_of(VW_WIDTHS), i64(t.data_ptr() + 64 for t in outs),
+                             i32(e.ws for e in exp), width_mask(VW_WIDTHS), i64(t.data_ptr() + 64 for t in outs),
                              i64(e.size for e in exp))
     torch.cuda.synchronize()
     check_scattered(exp, outs, ln.cpu().numpy(), st.cpu().numpy(), "encode_vw", bad)
@@ -319,7 +294,7 @@ def test_route_d_encode_vp(batch, scattered, sizes_first):
     whole, out = guarded_output(int(want_off[-1]))
     codec = make_codec(4, options=[(TDT_OPT_PACK_SIZES_FIRST, sizes_first)])
     off, st = codec.encode_vp(i64(scattered[e.name].data_ptr() for e in exp), i64(e.n for e in exp),
-                              sum(e.n for e in exp), out, word_sizes=i32(e.ws for e in exp), width_mask=mask_of(VW_WIDTHS))
+                              sum(e.n for e in exp), out, word_sizes=i32(e.ws for e in exp), width_mask=width_mask(VW_WIDTHS))
     torch.cuda.synchronize()
     h, off, st = whole.cpu().numpy(), off.cpu().numpy(), st.cpu().numpy()[:n]
     if not np.array_equal(off, want_off):
@@ -362,7 +337,7 @@ def test_route_e_encoded_sizes_mixed(batch, scattered):
     exp = mixed(batch)
     codec = make_codec(4)
     sz, st = codec.encoded_sizes_v(i64(scattered[e.name].data_ptr() for e in exp), i64(e.n for e in exp),
-                                   word_sizes=i32(e.ws for e in exp), width_mask=mask_of(VW_WIDTHS))
+                                   word_sizes=i32(e.ws for e in exp), width_mask=width_mask(VW_WIDTHS))
     torch.cuda.synchronize()
     sz, st = sz.cpu().numpy(), st.cpu().numpy()
     bad = ["%s: size %d status %d, expected %d" % (e.name, sz[i], st[i], e.size) for i, e in enumerate(exp)

@@ -13,14 +13,15 @@ import numpy as np
 import pytest
 
 from tests import raw_fallback_cases as rc
-from tests.test_gpu_mixed_ws import CANARY, _gpu, orc  # noqa: F401
+from tests.support import CANARY, E_CAPACITY
 
 torch = pytest.importorskip("torch")
+from tests.gpu_support import _gpu, orc  # noqa: E402, F401
+
 pytestmark = pytest.mark.gpu
 
 ROOT = pathlib.Path(__file__).resolve().parents[1]
 CPP_BIN = ROOT / "tests" / "cpp" / "test_host_raw_fallback"
-E_CAPACITY = 5
 OPT_LARGE_MIN, OPT_RAW_FALLBACK, OPT_HOST_RAW_FALLBACK = 1, 10, 11
 GUARD = 64
 

@@ -5,23 +5,25 @@ own size pass decided).  Expected bytes are the CPU oracle's (Oracle.encode(mapp
 digests of tests/golden/encode_runs.json, or what the existing routes give; there is no tolerance.
 Outputs lie between 0xA5 guard bytes that must stay intact, and the codec's device invariant flags
 must stay 0."""
-import hashlib
 import json
 
 import numpy as np
 import pytest
 
-from oracle.oracle import Oracle, encode_bound
+from oracle.oracle import encode_bound
 from tests import encode_run_cases as ec
 from tests import mapping_band_cases as mb
 from tests.golden_cases import GOLDEN
-from tests.test_gpu_mixed_ws import (CANARY, LEADS, SIZES, WIDTHS, _gpu, address_order, batch, canaries_intact,  # noqa: F401
-                                     guarded, i32, i64, make_codec, mask_of, oracle_blob, orc, own, ptrs, records, run_vw)
+from tests.support import (CANARY, E_ARG, E_BAD_MAPPING, E_CAPACITY, E_CAPTURE, E_CONFIG, E_UNSUPPORTED, address_order,
+                           bits_of, digest, mask_of)
 
 torch = pytest.importorskip("torch")
+from tests.gpu_support import (_gpu, canaries_intact, guarded, i32, i64, make_codec, orc, own,  # noqa: E402, F401
+                               packed_blobs, ptrs, u64)
+from tests.mixed_ws_cases import WIDTHS, batch, oracle_blob, records, run_vw  # noqa: E402, F401
+
 pytestmark = pytest.mark.gpu
 
-E_BAD_MAPPING, E_CAPACITY, E_UNSUPPORTED, E_CONFIG, E_ARG, E_CAPTURE = 4, 5, 6, 8, 11, 12
 OPT_LARGE_MIN, OPT_TILE_CAP, OPT_PACK_SIZES_FIRST = 1, 2, 7
 KINDS = ("analysed", "complement", "zeros", "ones", "random")
 
@@ -29,15 +31,6 @@ KINDS = ("analysed", "complement", "zeros", "ones", "random")
 def compresses(n, ws):
     """should_transform under the tests' metrics and compress_tdt's size guard: not the UNCP route."""
     return n >= 1024 and n % 4 == 0 and n % ws == 0
-
-
-def bits_of(mapping):
-    return sum(int(m) << p for p, m in enumerate(mapping))
-
-
-def u64(values):
-    """Mapping words as the int64 tensor the calls take (bit 63 is the sign there)."""
-    return torch.from_numpy(np.array([int(v) for v in values], dtype=np.uint64).view(np.int64)).cuda()
 
 
 def mapped_blob(orc, m, w, mapping):
@@ -204,8 +197,6 @@ def test_mappings_v_on_the_near_ties(bands):
 
 
 # ------------------------------------------------------------------------------- 4: run arithmetic under a given mapping
-def digest(b: bytes) -> str:
-    return hashlib.sha256(b).hexdigest()[:16]
 
 
 @pytest.fixture(scope="module")
@@ -417,9 +408,6 @@ def test_null_mapping_and_empty_batch():
 
 
 # ------------------------------------------------------------------------------- 7: packed
-def packed_blobs(out, off):
-    h, o = out.cpu().numpy(), off.cpu().numpy()
-    return [h[o[k]:o[k + 1]].tobytes() for k in range(len(o) - 1)], o
 
 
 def test_encode_vp_mapped_is_the_concatenation(batch, mapped):

@@ -8,21 +8,12 @@ import numpy as np
 import pytest
 
 from oracle.oracle import Oracle
+from tests.support import gradient
 
 torch = pytest.importorskip("torch")
+from tests.gpu_support import _gpu, make_codec  # noqa: E402, F401
+
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _gpu():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-
-
-def codec_for(ws=4):
-    from psyne_amd import TDTConfig, TdtCodec
-    c = TdtCodec(TDTConfig(sample_fraction=1.0, word_size=ws))
-    c.set_metrics(10.0, 1.0, 0.5)
-    return c
 
 
 def runs_message(rng, n, mean_run, alphabet=4):
@@ -37,12 +28,6 @@ def runs_message(rng, n, mean_run, alphabet=4):
     return out
 
 
-def gradient(rng, n):
-    x = rng.normal(0, 0.01, n // 4).astype(np.float32)
-    x[rng.random(x.size) < 0.7] = 0
-    return x.view(np.uint8)
-
-
 def check_batch(msgs, ws=4, lead=0, codec=None):
     off = np.zeros(len(msgs) + 1, np.int64)
     off[0] = lead
@@ -51,7 +36,7 @@ def check_batch(msgs, ws=4, lead=0, codec=None):
     buf = np.zeros(int(off[-1]), np.uint8)
     for i, m in enumerate(msgs):
         buf[off[i]:off[i + 1]] = m
-    codec = codec or codec_for(ws)
+    codec = codec or make_codec(ws)
     d, o = torch.from_numpy(buf).cuda(), torch.from_numpy(off).cuda()
     out, slots, lens, st = codec.encode_into(d, o)
     torch.cuda.synchronize()
@@ -129,7 +114,7 @@ def test_tile_budget_fallback():
     """A tile budget of 64 tiles (4 MiB): the first large messages take the tiled path, the
     rest the whole-message kernel — the blobs are the same either way."""
     from psyne_amd._lib import TDT_OPT_TILE_CAP
-    codec = codec_for(4)
+    codec = make_codec(4)
     codec.set_option(TDT_OPT_TILE_CAP, 64)
     rng = np.random.default_rng(17)
     msgs = [runs_message(rng, int(rng.integers(5, 20)) * 65536 + 4 * k, 280) for k in range(12)]
@@ -215,7 +200,7 @@ def test_compacted_offsets_past_4gib():
     broadcast (a sign-extended low half faulted here).  Offsets equal the scan of the slotted
     lengths, sampled blobs (first, around 2 / 4 GiB, last) equal the oracle's, and the round
     trip is exact."""
-    codec = codec_for(4)
+    codec = make_codec(4)
     n, mb = 98304, 65536  # 6 GiB in, ~4.8 GiB of blobs
     g = torch.Generator(device="cuda")
     g.manual_seed(41)
@@ -264,7 +249,7 @@ def test_count_list_history_on_warm_context():
     empty (gradients: the speculation holds), long (runs data: every tile) and mixed — every
     blob equals the oracle's each time."""
     rng = np.random.default_rng(31)
-    codec = codec_for(4)
+    codec = make_codec(4)
     grads = [gradient(rng, 1 << 20) for _ in range(6)]
     runs = [runs_message(rng, (1 << 20) + 4 * 77, 300) for _ in range(5)]
     for batch in (grads, runs, grads, grads + runs[:2] + [np.zeros(3 << 20, np.uint8)], runs):

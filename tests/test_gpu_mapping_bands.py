@@ -26,23 +26,18 @@ import pytest
 
 from oracle.oracle import Oracle, encode_bound
 from tests import mapping_band_cases as mb
+from tests.support import E_ARG, offsets_of
 
 torch = pytest.importorskip("torch")
+from tests.gpu_support import _gpu, on_gpu  # noqa: E402, F401
+
 pytestmark = pytest.mark.gpu
 
-E_ARG = 11
 VW_WIDTHS = (2, 4, 8, 16, 3, 12)
 VW_SIZES = {True: (4096, 32784, 65552), False: (4092, 32784, 65556)}  # tuned, generic
 LEADS = (0, 1, 4, 8)
 HOST_SIZES = (4096, 65536, 131088)
 TILE_SHARE = 4096  # a message is tiled above max(large_min, batch bytes / 4096) (encode plan, tdt_encode.h)
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _gpu():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    from psyne_amd import _lib
-    _lib.load()
 
 
 def expected():
@@ -75,16 +70,6 @@ def make_codec(ws, hint=None, large_min=None):
     if large_min is not None:
         c.set_option(TDT_OPT_LARGE_MIN, large_min)
     return c
-
-
-def offsets_of(parts):
-    off = np.zeros(len(parts) + 1, np.int64)
-    off[1:] = np.cumsum([len(p) for p in parts])
-    return off
-
-
-def on_gpu(msgs):
-    return torch.from_numpy(np.concatenate(msgs)).cuda(), torch.from_numpy(offsets_of(msgs)).cuda()
 
 
 def differing(sub, blobs, lengths, statuses):

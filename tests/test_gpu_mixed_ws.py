@@ -5,153 +5,14 @@ and against encode_v on the width's sub-batch."""
 import numpy as np
 import pytest
 
-from oracle.oracle import Oracle, encode_bound
-from tests.anyws_cases import from_streams, low_pattern
+from oracle.oracle import encode_bound
+from tests.support import CANARY, E_ARG, E_CAPACITY, E_CAPTURE, E_CONFIG, E_UNSUPPORTED, mask_of
 
 torch = pytest.importorskip("torch")
+from tests.gpu_support import _gpu, canaries_intact, guarded, i32, i64, make_codec, orc, own, ptrs  # noqa: E402, F401
+from tests.mixed_ws_cases import batch, oracle_blob, records, run_vw  # noqa: E402, F401
+
 pytestmark = pytest.mark.gpu
-
-E_CAPACITY, E_UNSUPPORTED, E_CONFIG, E_ARG, E_CAPTURE = 5, 6, 8, 11, 12
-CANARY = 0xA5
-WIDTHS = [1, 2, 4, 8, 16, 3, 12]
-# the smallest sizes that reach the UNCP copy (0, 3, 64, 1000: below min_tensor), the one-wave
-# (<= 4 KiB), 256-lane (<= 32 KiB), resident 512-lane (<= 64 KiB, aligned) and streaming classes and,
-# in so small a batch, the tiles (> 256 KiB).  4104, 32784, 65544 and 100008 are multiples of 12;
-# 4104 is no multiple of 16 (the per-message n % ws fallback)
-SIZES = [0, 3, 64, 1000, 1024, 4096, 4104, 4112, 32768, 32784, 65536, 65544, 65552, 100000, 100008, 262208]
-LEADS = {4112: 1, 32784: 4, 65552: 8, 100000: 15}  # views this many bytes into their allocation
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _gpu():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    from psyne_amd import _lib
-    _lib.load()
-
-
-@pytest.fixture(scope="module")
-def orc():
-    return Oracle()
-
-
-def make_codec(ws=4):
-    from psyne_amd import TDTConfig, TdtCodec
-    c = TdtCodec(TDTConfig(sample_fraction=1.0, word_size=ws))
-    c.set_metrics(10.0, 1.0, 0.5)
-    return c
-
-
-def mask_of(widths):
-    m = 0
-    for w in set(widths):
-        m |= 1 << (w - 1)
-    return m
-
-
-def records(rng, ws, n):
-    """n bytes of ws-byte records whose byte positions differ in entropy (both streams populated
-    from width 2 up); sizes that hold no whole number of records, and width 1, get few-valued bytes."""
-    if ws > 1 and n >= ws and n % ws == 0:
-        wc = n // ws
-        return from_streams(ws, wc, low_pattern(wc * ws, rng), rng)
-    return rng.integers(0, 4, n, dtype=np.uint8)
-
-
-def own(data, lead=0):
-    """`data` in a device allocation of its own, `lead` bytes into it."""
-    data = np.frombuffer(bytes(data), np.uint8) if not isinstance(data, np.ndarray) else data
-    t = torch.empty(lead + data.size + 16, dtype=torch.uint8, device="cuda")
-    v = t[lead:lead + data.size]
-    if data.size:
-        v.copy_(torch.from_numpy(np.ascontiguousarray(data)))
-    return v
-
-
-def guarded(cap):
-    """A `cap`-byte output inside a larger allocation, 64 canary bytes on either side."""
-    t = torch.full((64 + cap + 64,), CANARY, dtype=torch.uint8, device="cuda")
-    return t, t[64:64 + cap]
-
-
-def canaries_intact(t, cap):
-    h = t.cpu().numpy()
-    return bool((h[:64] == CANARY).all() and (h[64 + cap:] == CANARY).all())
-
-
-def i64(values):
-    return torch.tensor([int(v) for v in values], dtype=torch.int64, device="cuda")
-
-
-def i32(values):
-    return torch.tensor([int(v) for v in values], dtype=torch.int32, device="cuda")
-
-
-def ptrs(tensors):
-    return i64(t.data_ptr() if t.numel() else 0 for t in tensors)
-
-
-def oracle_blob(orc, m, w):
-    return orc.encode(m, cfg=orc.config(sample_fraction=1.0, word_size=w))
-
-
-def encode_v_sub(ws, tensors, caps):
-    """encode_v on a context of width ws: (blobs as bytes, lengths, statuses)."""
-    outs = [torch.zeros(c, dtype=torch.uint8, device="cuda") for c in caps]
-    codec = make_codec(ws)
-    ln, st = codec.encode_v(ptrs(tensors), i64(t.numel() for t in tensors), ptrs(outs), i64(caps))
-    torch.cuda.synchronize()
-    ln, st = ln.cpu().numpy()[: len(tensors)], st.cpu().numpy()[: len(tensors)]
-    assert codec.error_flags() == 0
-    return [o[: ln[k]].cpu().numpy().tobytes() for k, o in enumerate(outs)], ln, st
-
-
-@pytest.fixture(scope="module")
-def batch(orc):
-    """Every size at every width, the widths interleaved message by message; the oracle's blobs; and
-    per width what encode_v on a context of that width gives for the width's sub-batch."""
-    rng = np.random.default_rng(20261)
-    ws, msgs, leads = [], [], []
-    for k, n in enumerate(SIZES):
-        for j, w in enumerate(WIDTHS):
-            ws.append(w)
-            msgs.append(records(rng, w, n))
-            leads.append(LEADS.get(n, 0) if (j + k) % 2 == 0 else 0)
-    ws += [2, 8]
-    msgs += [np.full(32768, 0x3C, np.uint8), rng.integers(0, 256, 65536, dtype=np.uint8)]  # constant, uniform random
-    leads += [0, 0]
-    blobs = [oracle_blob(orc, m, w) for m, w in zip(msgs, ws)]
-    tensors = [own(m, lead) for m, lead in zip(msgs, leads)]
-    caps = [encode_bound(len(m), w) for m, w in zip(msgs, ws)]
-    sub = {}
-    for w in WIDTHS:
-        idx = [i for i, x in enumerate(ws) if x == w]
-        b, ln, st = encode_v_sub(w, [tensors[i] for i in idx], [caps[i] for i in idx])
-        for k, i in enumerate(idx):
-            sub[i] = (b[k], int(ln[k]), int(st[k]))
-    return dict(ws=ws, msgs=msgs, blobs=blobs, tensors=tensors, caps=caps, sub=sub, runs={})
-
-
-def address_order(tensors, order):
-    idx = sorted(range(len(tensors)), key=lambda i: tensors[i].data_ptr())
-    if order == "shuffled":
-        np.random.default_rng(7).shuffle(idx)
-    return idx
-
-
-def run_vw(batch, order):
-    """One encode_vw call over the whole batch in the given address order (kept for the round trip)."""
-    if order not in batch["runs"]:
-        idx = address_order(batch["tensors"], order)
-        tensors = [batch["tensors"][i] for i in idx]
-        caps = [batch["caps"][i] for i in idx]
-        outs = [torch.zeros(c, dtype=torch.uint8, device="cuda") for c in caps]
-        codec = make_codec(4)
-        ln, st = codec.encode_vw(ptrs(tensors), i64(t.numel() for t in tensors), i32(batch["ws"][i] for i in idx),
-                                 mask_of(WIDTHS), ptrs(outs), i64(caps))
-        torch.cuda.synchronize()
-        flags = codec.error_flags()
-        batch["runs"][order] = (idx, outs, ln.cpu().numpy(), st.cpu().numpy(), flags)
-    return batch["runs"][order]
 
 
 # ------------------------------------------------------------------------------- 1: every class, every width

@@ -10,14 +10,15 @@ import numpy as np
 import pytest
 
 from oracle.oracle import encode_bound
-# the shapes of the scattered tests: their sizes, leads, helpers and the shared batch
-from tests.test_gpu_mixed_ws import (CANARY, WIDTHS, _gpu, address_order, batch, canaries_intact, guarded, i32,  # noqa: F401
-                                     i64, make_codec, mask_of, oracle_blob, orc, own, ptrs, records, run_vw)
+from tests.support import CANARY, E_ARG, E_CAPACITY, E_CAPTURE, E_CONFIG, E_UNSUPPORTED, address_order, mask_of, offsets
 
 torch = pytest.importorskip("torch")
+from tests.gpu_support import (_gpu, canaries_intact, guarded, i32, i64, make_codec, orc, own,  # noqa: E402, F401
+                               packed_blobs, ptrs)
+from tests.mixed_ws_cases import WIDTHS, batch, oracle_blob, records, run_vw  # noqa: E402, F401
+
 pytestmark = pytest.mark.gpu
 
-E_CAPACITY, E_UNSUPPORTED, E_CONFIG, E_ARG, E_CAPTURE = 5, 6, 8, 11, 12
 ROOT = pathlib.Path(__file__).resolve().parents[1]
 # the piece of the packed output one workgroup copies: taken from the build, not restated here
 P = int(re.search(r"kPackPiece\s*=\s*(\d+)\s*;", (ROOT / "psyne_amd" / "csrc" / "tdt_pack.h").read_text()).group(1))
@@ -52,10 +53,6 @@ def blobs():
     return host, dev
 
 
-def cumsum0(lengths):
-    return np.concatenate([[0], np.cumsum(np.asarray(lengths, dtype=np.int64))])
-
-
 # ------------------------------------------------------------------------------- 1: pack_v against numpy
 @pytest.mark.parametrize("order", ["ascending", "shuffled"])
 @pytest.mark.parametrize("phase", [0, 1, 8])
@@ -69,7 +66,7 @@ def test_pack_v_equals_concatenation(blobs, phase, order):
     st = torch.full((len(idx),), 77, dtype=torch.int32, device="cuda")
     codec.pack_v(ptrs([dev[i] for i in idx]), i64(host[i].size for i in idx), out, out_offsets=off, status=st)
     torch.cuda.synchronize()
-    assert off.cpu().numpy().tolist() == cumsum0([host[i].size for i in idx]).tolist()
+    assert off.cpu().numpy().tolist() == offsets([host[i].size for i in idx]).tolist()
     assert int(st.abs().sum()) == 0
     assert np.array_equal(out.cpu().numpy(), want)
     assert canaries_around(t, out)
@@ -95,7 +92,7 @@ def test_pack_v_capacity(blobs, where):
     host, dev = blobs
     n = len(LENGTHS)
     host, dev = host[:n], dev[:n]
-    off_want = cumsum0([m.size for m in host])
+    off_want = offsets([m.size for m in host])
     want = np.concatenate(host)
     # inside the blob of several pieces (and inside its second piece); at the end of the P-byte blob
     cap = {"inside a blob": int(off_want[9]) + P + 100, "at a blob's end": int(off_want[8]), "zero": 0}[where]
@@ -112,9 +109,6 @@ def test_pack_v_capacity(blobs, where):
 
 
 # ------------------------------------------------------------------------------- 3: encode_vp, one width
-def packed_blobs(out, off):
-    oh, off = out.cpu().numpy(), off.cpu().numpy()
-    return [oh[off[k]:off[k + 1]].tobytes() for k in range(off.size - 1)], off
 
 
 @pytest.mark.parametrize("w", [4, 12])
@@ -219,7 +213,7 @@ def test_encode_vp_out_cap_cuts_the_batch(batch, where):
     idx = [i for i, x in enumerate(batch["ws"]) if x == 4]
     tensors = [batch["tensors"][i] for i in idx]
     sizes = [t.numel() for t in tensors]
-    off_want = cumsum0([len(batch["blobs"][i]) for i in idx])
+    off_want = offsets([len(batch["blobs"][i]) for i in idx])
     want = np.frombuffer(b"".join(batch["blobs"][i] for i in idx), np.uint8)
     k = len(idx) // 2
     cap = int(off_want[k + 1]) if where == "at a blob's end" else int(off_want[k] + off_want[k + 1]) // 2
@@ -255,7 +249,7 @@ def test_encode_vp_understated_total_is_clamped(batch):
     off, st = codec.encode_vp(ptrs(tensors), i64(sizes), half, out)
     torch.cuda.synchronize()
     got, offh = packed_blobs(out, off)
-    assert offh.tolist() == cumsum0(lens).tolist()
+    assert offh.tolist() == offsets(lens).tolist()
     assert st.cpu().numpy()[:n].tolist() == [0 if ok else E_CAPACITY for ok in inside]
     for k, i in enumerate(idx):
         assert got[k] == (batch["blobs"][i] if inside[k] else b""), "message %d" % i
@@ -350,7 +344,7 @@ def test_encode_tensors_packed(orc):
     assert off.numel() == len(tensors) + 1 and off.is_cuda
     assert int(st.abs().sum()) == 0
     got, offh = packed_blobs(out, off)
-    assert offh.tolist() == cumsum0([len(b) for b in want]).tolist()
+    assert offh.tolist() == offsets([len(b) for b in want]).tolist()
     assert got == want
     fresh = [torch.full_like(t, 1) for t in tensors]
     dl, ds = codec.decode_tensors(out, off, off[1:] - off[:-1], fresh)  # the docstring's round trip
@@ -374,6 +368,6 @@ def test_encode_tensors_packed(orc):
     torch.cuda.synchronize()
     assert int(sst.abs().sum()) == 0
     oh, sl, lh = outs.cpu().numpy(), slots.cpu().numpy(), ln.cpu().numpy()
-    assert sl.tolist() == cumsum0([encode_bound(r.size, t.element_size()) for r, t in zip(raw, tensors)]).tolist()
+    assert sl.tolist() == offsets([encode_bound(r.size, t.element_size()) for r, t in zip(raw, tensors)]).tolist()
     assert [oh[sl[i]:sl[i] + lh[i]].tobytes() for i in range(len(tensors))] == want
     assert codec.error_flags() == 0

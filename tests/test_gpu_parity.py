@@ -9,23 +9,12 @@ import numpy as np
 import pytest
 
 from oracle.oracle import Oracle
+from tests.support import E_CAPACITY
 
 torch = pytest.importorskip("torch")
+from tests.gpu_support import _gpu, orc  # noqa: E402, F401
+
 pytestmark = pytest.mark.gpu
-
-E_CAPACITY, E_UNSUPPORTED = 5, 6
-
-
-@pytest.fixture(scope="module")
-def orc():
-    return Oracle()
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _gpu():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    from psyne_amd import _lib
-    _lib.load()  # the HIP library must be the thing under test
 
 
 def make_codec(ws=4, min_tensor=1024, bw=10.0, cpu=0.5, hint=None):

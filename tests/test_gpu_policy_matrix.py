@@ -44,11 +44,13 @@ import pytest
 from oracle.oracle import Oracle, encode_bound
 from tests import policy_cases as pc
 from tests.golden_cases import GOLDEN
+from tests.support import CANARY, offsets_of, phased_slots
 
 torch = pytest.importorskip("torch")
+from tests.gpu_support import _gpu, i64, on_gpu  # noqa: E402, F401
+
 pytestmark = pytest.mark.gpu
 
-CANARY = 0xA5
 UNCP = b"PCNU"
 LARGE_MIN = 65536
 TILE_SHARE = 4096  # a message is tiled above max(large_min, batch bytes / 4096) (encode plan, tdt_encode.h)
@@ -58,19 +60,12 @@ FLIP_WIDTHS = (4, 12)
 FLIPS = ((10.0, 0.5), (1000.0, 0.5), (10.0, 0.5), (10.0, 0.9), (10.0, 0.5))  # on, off, on, off (cpu), on
 
 
-@pytest.fixture(scope="module", autouse=True)
-def _gpu():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    from psyne_amd import _lib
-    _lib.load()
-
-
 def oracle_config(orc, ws, min_tensor, bt, ct):
     return orc.config(word_size=ws, sample_fraction=1.0, bandwidth_threshold_mbps=bt, cpu_usage_threshold=ct,
                       min_tensor_size=min_tensor)
 
 
-def bits_of(blob, ws) -> int:
+def blob_bits(blob, ws) -> int:
     """The mapping word of a blob: bit p = the stream of byte position p; 0 for a raw one."""
     if blob[:4] == UNCP:
         return 0
@@ -84,7 +79,7 @@ class Item:
     def __init__(self, name, ws, n, key, metrics, message, blob):
         self.name, self.ws, self.n, self.key, self.metrics, self.message, self.blob = name, ws, n, key, metrics, message, blob
         self.raw = blob[:4] == UNCP
-        self.bits = bits_of(blob, ws)
+        self.bits = blob_bits(blob, ws)
 
     def want(self, fallback=False) -> bytes:
         if fallback and len(self.blob) > self.n + 4:
@@ -146,35 +141,10 @@ def over_groups(sub, call, options=(), hint=None, **kw):
     return bad
 
 
-def offsets_of(parts):
-    off = np.zeros(len(parts) + 1, np.int64)
-    off[1:] = np.cumsum([len(p) for p in parts])
-    return off
-
-
-def on_gpu(msgs):
-    return torch.from_numpy(np.concatenate(msgs)).cuda(), torch.from_numpy(offsets_of(msgs)).cuda()
-
-
-def i64(values):
-    return torch.tensor([int(v) for v in values], dtype=torch.int64, device="cuda")
-
-
 def differing(sub, blobs, lengths, statuses, fallback=False):
     """Names of the cases whose blob, length or status is not the oracle's."""
     return [c.name for c, b, n, s in zip(sub, blobs, lengths, statuses)
             if int(s) != 0 or int(n) != len(c.want(fallback)) or b != c.want(fallback)]
-
-
-def phased_slots(sizes, lead=0, step=5):
-    """Slot i of sizes[i] bytes starting (lead + step i) mod 16 bytes past a 16-byte boundary, 16 or
-    more bytes behind the slot before (tests/test_gpu_copy_routes.py): (table of n + 1 entries, end)."""
-    at, table = 64, []
-    for i, s in enumerate(sizes):
-        at += (lead + step * i - at) % 16
-        table.append(at)
-        at += s + 16
-    return np.asarray(table + [at], np.int64), at + 64
 
 
 def tiled_by_rule(sub, large_min):

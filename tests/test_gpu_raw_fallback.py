@@ -11,12 +11,13 @@ import numpy as np
 import pytest
 
 from tests import raw_fallback_cases as rc
-from tests.test_gpu_mixed_ws import CANARY, _gpu, i32, i64, mask_of, orc, own, ptrs  # noqa: F401
+from tests.support import CANARY, E_CAPACITY, E_CAPTURE, E_UNSUPPORTED, mask_of
 
 torch = pytest.importorskip("torch")
+from tests.gpu_support import _gpu, guarded, i32, i64, orc, own, ptrs, u64  # noqa: E402, F401
+
 pytestmark = pytest.mark.gpu
 
-E_CAPACITY, E_UNSUPPORTED, E_CAPTURE = 5, 6, 12
 OPT_LARGE_MIN, OPT_NO_TWO_PHASE, OPT_PACK_SIZES_FIRST, OPT_ANY_TILED, OPT_RAW_FALLBACK = 1, 5, 7, 8, 10
 LEADS = (0, 1, 4)  # pointer offsets of the messages and of the blobs
 
@@ -51,12 +52,6 @@ def cases(orc):
             made[(ws, n)] = b
         return made[(ws, n)]
     return get
-
-
-def guarded(cap, lead=0):
-    """A `cap`-byte output `lead` bytes off a 64-byte boundary, canaries on either side."""
-    t = torch.full((64 + lead + cap + 64,), CANARY, dtype=torch.uint8, device="cuda")
-    return t, t[64 + lead:64 + lead + cap]
 
 
 def outputs(caps):
@@ -345,8 +340,6 @@ def test_encode_tensors_packed_exact(cases):
 
 
 # ------------------------------------------------------------------------------- 4: known mappings
-def u64(values):
-    return torch.from_numpy(np.array([int(v) for v in values], dtype=np.uint64).view(np.int64)).cuda()
 
 
 @pytest.mark.parametrize("ws,n", [(4, 1024), (4, 65536), (12, 12288)])

@@ -9,24 +9,14 @@ import numpy as np
 import pytest
 
 from oracle.oracle import Oracle, encode_bound
-from tests.test_gpu_mixed_ws import i32, i64, make_codec, mask_of
+from tests.support import E_CAPTURE, gradient, mask_of, offsets_of
 
 torch = pytest.importorskip("torch")
+from tests.gpu_support import _gpu, i32, i64, make_codec  # noqa: E402, F401
+
 pytestmark = pytest.mark.gpu
 
-E_CAPTURE = 12
 ORDER = ("small", "large", "small")
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _gpu():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-
-
-def _gradient(rng, n):
-    x = rng.normal(0, 0.01, n // 4).astype(np.float32)
-    x[rng.random(n // 4) < 0.7] = 0
-    return x.view(np.uint8)
 
 
 class _Ref:
@@ -36,9 +26,9 @@ class _Ref:
         rng = np.random.default_rng(20264)
         self.orc = Oracle()
         self.msgs = {
-            "small": [_gradient(rng, 2048) for _ in range(4)],
+            "small": [gradient(rng, 2048) for _ in range(4)],
             # 600 x 2 KiB and one 100 KiB message: the compacted encode takes its two phases
-            "large": [_gradient(rng, 2048) for _ in range(600)] + [_gradient(rng, 100 * 1024)],
+            "large": [gradient(rng, 2048) for _ in range(600)] + [gradient(rng, 100 * 1024)],
             # one message more than a single 8,192-message scan chunk holds: the chunk sums are needed
             "tiny": [rng.integers(0, 256, 64, dtype=np.uint8) for _ in range(8200)],
         }
@@ -63,9 +53,7 @@ def ref():
 def _concat(parts):
     """(bytes back to back, offsets) of a list of byte strings / uint8 arrays"""
     arrs = [np.frombuffer(p, np.uint8) if isinstance(p, (bytes, bytearray)) else p for p in parts]
-    off = np.zeros(len(arrs) + 1, np.int64)
-    off[1:] = np.cumsum([a.size for a in arrs])
-    return np.concatenate(arrs), off
+    return np.concatenate(arrs), offsets_of(arrs)
 
 
 def _split(buf, off):

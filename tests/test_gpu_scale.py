@@ -9,19 +9,9 @@ import pytest
 from oracle.oracle import Oracle
 
 torch = pytest.importorskip("torch")
+from tests.gpu_support import _gpu, make_codec  # noqa: E402, F401
+
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _gpu():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-
-
-def make_codec():
-    from psyne_amd import TDTConfig, TdtCodec
-    c = TdtCodec(TDTConfig(sample_fraction=1.0))
-    c.set_metrics(10.0, 1.0, 0.5)  # bandwidth < 100 Mbps: compression on
-    return c
 
 
 def valid_mask(slot, lens, total):

@@ -5,13 +5,14 @@ length as the slotted calls give on the packed batch."""
 import numpy as np
 import pytest
 
-from oracle.oracle import Oracle, encode_bound
+from oracle.oracle import encode_bound
+from tests.support import CANARY, E_CAPACITY, E_CAPTURE, E_MAGIC, E_TRUNCATED, address_order, gradient
 
 torch = pytest.importorskip("torch")
+from tests.gpu_support import _gpu, canaries_intact, guarded, i64, make_codec, orc, own, ptrs  # noqa: E402, F401
+
 pytestmark = pytest.mark.gpu
 
-E_SHORT, E_MAGIC, E_TRUNCATED, E_CAPACITY, E_CAPTURE = 1, 2, 3, 5, 12
-CANARY = 0xA5
 # the smallest sizes that reach every encode class: UNCP copies (0, 3, 64 and 1000 are below
 # min_tensor), one-wave teams (<= 4 KiB), 256-lane teams (<= 32 KiB), 512-lane resident teams
 # (<= 64 KiB, aligned), the streaming list (longer, or unaligned) and, in so small a batch, tiles
@@ -20,62 +21,8 @@ SIZES = [0, 3, 64, 1000, 1024, 4096, 4112, 32768, 32784, 65536, 65552, 100000, 2
 LEADS = [(4112, 1), (32784, 4), (65552, 8), (100000, 15)]  # views this many bytes into an allocation
 
 
-@pytest.fixture(scope="module", autouse=True)
-def _gpu():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    from psyne_amd import _lib
-    _lib.load()
-
-
-@pytest.fixture(scope="module")
-def orc():
-    return Oracle()
-
-
-def make_codec(ws=4):
-    from psyne_amd import TDTConfig, TdtCodec
-    c = TdtCodec(TDTConfig(sample_fraction=1.0, word_size=ws))
-    c.set_metrics(10.0, 1.0, 0.5)
-    return c
-
-
-def grad(rng, nbytes):
-    x = rng.normal(0, 0.01, nbytes // 4).astype(np.float32)
-    x[rng.random(x.size) < 0.7] = 0
-    return x.view(np.uint8)
-
-
 def message(rng, n):
-    return grad(rng, n) if n % 4 == 0 and n >= 64 else rng.integers(0, 256, n, dtype=np.uint8)
-
-
-def own(data, lead=0):
-    """`data` in a device allocation of its own, `lead` bytes into it."""
-    data = np.frombuffer(bytes(data), np.uint8) if not isinstance(data, np.ndarray) else data
-    t = torch.empty(lead + data.size + 16, dtype=torch.uint8, device="cuda")
-    v = t[lead:lead + data.size]
-    if data.size:
-        v.copy_(torch.from_numpy(np.ascontiguousarray(data)))
-    return v
-
-
-def guarded(cap):
-    """A `cap`-byte output inside a larger allocation, 64 canary bytes on either side."""
-    t = torch.full((64 + cap + 64,), CANARY, dtype=torch.uint8, device="cuda")
-    return t, t[64:64 + cap]
-
-
-def canaries_intact(t, cap):
-    h = t.cpu().numpy()
-    return bool((h[:64] == CANARY).all() and (h[64 + cap:] == CANARY).all())
-
-
-def i64(values):
-    return torch.tensor([int(v) for v in values], dtype=torch.int64, device="cuda")
-
-
-def ptrs(tensors):
-    return i64(t.data_ptr() if t.numel() else 0 for t in tensors)
+    return gradient(rng, n) if n % 4 == 0 and n >= 64 else rng.integers(0, 256, n, dtype=np.uint8)
 
 
 def pack(chunks):
@@ -110,15 +57,6 @@ def batch(orc):
                 packed_st=st.cpu().numpy()[: len(msgs)])
 
 
-def address_order(tensors, order):
-    idx = sorted(range(len(tensors)), key=lambda i: tensors[i].data_ptr())
-    if order == "descending":
-        idx.reverse()
-    elif order == "shuffled":
-        np.random.default_rng(7).shuffle(idx)
-    return idx
-
-
 # ------------------------------------------------------------------------------- 1: encode classes
 @pytest.mark.parametrize("order", ["ascending", "descending", "shuffled"])
 def test_encode_v_every_class(batch, order):
@@ -140,7 +78,7 @@ def test_encode_v_every_class(batch, order):
 # ------------------------------------------------------------------------------- 2: headline shape
 def test_encode_v_headline_shape(orc):
     rng = np.random.default_rng(3)
-    msgs = [grad(rng, 65536) for _ in range(256)]
+    msgs = [gradient(rng, 65536) for _ in range(256)]
     tensors = [own(m) for m in msgs]
     cap = encode_bound(65536, 4)
     outs = [torch.zeros(cap, dtype=torch.uint8, device="cuda") for _ in msgs]
@@ -216,7 +154,7 @@ def dbatch(orc, batch):
     blobs = list(batch["blobs"])
     cfg = orc.config(sample_fraction=1.0)
     for n in (160 * 1024, 288 * 1024):  # decoding to > 128 KiB (dispatched first) and > 256 KiB (tiled)
-        msgs.append(grad(rng, n))
+        msgs.append(gradient(rng, n))
         blobs.append(orc.encode(msgs[-1], cfg=cfg, bandwidth=10.0))
     m12 = rng.integers(0, 4, 6000, dtype=np.uint8)  # a word-size-12 blob inside the word-size-4 context
     msgs.append(m12)

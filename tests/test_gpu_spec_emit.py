@@ -8,20 +8,16 @@ import struct
 import numpy as np
 import pytest
 
-from oracle.oracle import Oracle
+from tests.support import E_CAPACITY, gradient
 
 torch = pytest.importorskip("torch")
+from tests.gpu_support import orc  # noqa: E402, F401
+
 pytestmark = pytest.mark.gpu
 
-E_CAPACITY = 5
 KIB = 1024
 SPEC = (1, 1, 1, 0)
 SIZES = (32 * KIB + 16, 64 * KIB - 16, 64 * KIB)
-
-
-@pytest.fixture(scope="module")
-def orc():
-    return Oracle()
 
 
 @pytest.fixture(scope="module")
@@ -33,13 +29,6 @@ def codec():
     c.set_metrics(10.0, 1.0, 0.5)
     c.set_size_hint(65536)
     return c
-
-
-def gradient(rng, nbytes):
-    """bench.py's payload: float32, 70 % exact zeros, else N(0, 0.01)."""
-    x = rng.normal(0.0, 0.01, nbytes // 4).astype(np.float32)
-    x[rng.random(x.size) < 0.7] = 0.0
-    return x.view(np.uint8).copy()
 
 
 def planes(rng, nbytes, random_positions):
@@ -89,7 +78,7 @@ def mixed(orc):
     others = [(0, 1), (0,), (3,), (1, 2, 3), ()]
     msgs = []
     for k, n in enumerate(SIZES * 2):
-        msgs.append(gradient(rng, n))
+        msgs.append(gradient(rng, n).copy())
         msgs.append(planes(rng, n, others[k % len(others)]))
     return msgs, [orc.encode(m) for m in msgs]
 
@@ -111,7 +100,7 @@ def capped(orc):
     rng = np.random.default_rng(0xCA9)
     msgs = []
     for stretch in (255, 256, 257, 600):
-        m = gradient(rng, 64 * KIB).view(np.uint32)
+        m = gradient(rng, 64 * KIB).copy().view(np.uint32)
         m[300:300 + stretch] = 0
         b = 4 * (8 * KIB // 4)
         m[b - stretch // 2:b - stretch // 2 + stretch] = 0
@@ -129,7 +118,7 @@ def test_cap_on_speculated_mapping(codec, capped):
 
 def test_capacity_on_speculated_mapping(codec, orc):
     rng = np.random.default_rng(0xCAFE)
-    msgs = [gradient(rng, 64 * KIB) for _ in range(3)]
+    msgs = [gradient(rng, 64 * KIB).copy() for _ in range(3)]
     want = [orc.encode(m) for m in msgs]
     assert all(mapping_of(w) == SPEC for w in want)
     buf, off = pack(msgs)
@@ -151,7 +140,7 @@ def test_capacity_on_speculated_mapping(codec, orc):
 
 def test_caller_mapping_speculated(codec, orc):
     rng = np.random.default_rng(0x3A9)
-    msgs = [gradient(rng, 64 * KIB), rng.integers(0, 256, 64 * KIB, dtype=np.uint8), gradient(rng, 64 * KIB)]
+    msgs = [gradient(rng, 64 * KIB).copy(), rng.integers(0, 256, 64 * KIB, dtype=np.uint8), gradient(rng, 64 * KIB).copy()]
     want = [orc.encode(m, mapping=SPEC) for m in msgs]
     assert all(mapping_of(w) == SPEC for w in want)
     buf, off = pack(msgs)

@@ -3,27 +3,18 @@ psy::mapbits_ok and its neighbours (psyne_amd/csrc/tdt_mapbits.h) checked by tes
 a program of its own, built with AddressSanitizer and UBSan and run directly — the Python helpers
 mapbits_of / mapping_of, and the three entry points' presence in the header, the ctypes table and the
 library, with a null context refused."""
-import pathlib
 import re
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = pathlib.Path(__file__).resolve().parent.parent
-SRC = ROOT / "tests" / "cpp" / "test_mapbits.cpp"
-CXX = shutil.which("g++") or shutil.which("clang++")
+from tests.support import CXX, ROOT, run_host_cpp
+
 NEW = ("tdt_mappings_v", "tdt_encode_mapped_v", "tdt_encode_mapped_vp")
 
 
 @pytest.mark.skipif(CXX is None, reason="no host C++ compiler")
 def test_mapbits_driver(tmp_path):
-    exe = tmp_path / "test_mapbits"
-    subprocess.check_call([CXX, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=undefined", str(SRC), "-o", str(exe)], timeout=600)
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert re.search(r"mapbits: 0 failures", r.stdout), r.stdout
+    run_host_cpp("test_mapbits.cpp", tmp_path, r"mapbits: 0 failures")
 
 
 def test_helpers_round_trip_every_width():

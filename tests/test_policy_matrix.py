@@ -3,7 +3,6 @@ written by tests/golden/make_policy_matrix.py where the compiled reference exist
 every term on both sides in every message class, the CPU oracle answers and encodes what the reference
 did, and the record's verdicts are the formula, restated once below.  Pins the yardstick the GPU routes
 (tests/test_gpu_policy_matrix.py) compare with."""
-import hashlib
 import json
 
 import pytest
@@ -11,10 +10,7 @@ import pytest
 from oracle.oracle import Oracle, Reference
 from tests import policy_cases as pc
 from tests.golden_cases import GOLDEN
-
-
-def digest(b: bytes) -> str:
-    return hashlib.sha256(b).hexdigest()[:16]
+from tests.support import digest
 
 
 @pytest.fixture(scope="module")

@@ -1,23 +1,11 @@
 """The arithmetic of the raw fallback's copy, bound and decision (psyne_amd/csrc/tdt_rawfb.h): plain
 host C++, checked by tests/cpp/test_raw_fallback_segments.cpp — a program of its own, built with
 AddressSanitizer and UBSan and run directly."""
-import pathlib
-import re
-import shutil
-import subprocess
-
 import pytest
 
-ROOT = pathlib.Path(__file__).resolve().parent.parent
-SRC = ROOT / "tests" / "cpp" / "test_raw_fallback_segments.cpp"
-CXX = shutil.which("g++") or shutil.which("clang++")
+from tests.support import CXX, run_host_cpp
 
 
 @pytest.mark.skipif(CXX is None, reason="no host C++ compiler")
 def test_raw_fallback_segments(tmp_path):
-    exe = tmp_path / "test_raw_fallback_segments"
-    subprocess.check_call([CXX, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=undefined", str(SRC), "-o", str(exe)], timeout=600)
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert re.search(r"raw fallback segments: 0 failures", r.stdout), r.stdout
+    run_host_cpp("test_raw_fallback_segments.cpp", tmp_path, r"raw fallback segments: 0 failures")
