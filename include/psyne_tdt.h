@@ -83,6 +83,15 @@ extern "C" {
 #define TDT_E_ARG 11          /* invalid argument */
 #define TDT_E_CAPTURE 12      /* a workspace must grow while the stream is captured: make one eager
                                  call of the batch on this context before capturing it */
+#define TDT_E_ELEMENT 13      /* tdt_decode_accumulate_v: destination not aligned to its element, or the
+                                 decoded size is not a whole number of elements */
+
+/* Element codes of tdt_decode_accumulate_v */
+#define TDT_ELEM_STORE 0      /* plain decode of this message (as tdt_decode_batch_v) */
+#define TDT_ELEM_F32 1
+#define TDT_ELEM_F16 2
+#define TDT_ELEM_BF16 3
+#define TDT_ELEM_F64 4
 
 /* TDTConfig (:31-43).  Fields the reference declares but never reads
  * (auto_detect_clusters, max_clusters, enable_simd) are omitted. */
@@ -206,6 +215,27 @@ int tdt_encode_batch_v(tdt_ctx *ctx, const uint8_t *const *d_msgs, const uint64_
 int tdt_decode_batch_v(tdt_ctx *ctx, const uint8_t *const *d_blobs, const uint64_t *d_blob_len, uint32_t n_msgs,
                        uint8_t *const *d_outs, const uint64_t *d_out_cap, uint64_t *d_out_len, int32_t *d_status,
                        void *hip_stream);
+/* DECODE-ACCUMULATE — tdt_decode_batch_v whose decoded bytes are ADDED to the destinations (a rank
+ * that receives a peer's gradients sums them into its own, without a scratch copy and a second
+ * pass).  Message i has element code d_elem[i] (device memory, n_msgs bytes; NULL: `elem` for
+ * every message), a TDT_ELEM_* value: for a type T, d_outs[i][k] = d_outs[i][k] + decoded[k] over the
+ * elements of the decoded message, one IEEE add each (round to nearest even, subnormals kept);
+ * TDT_ELEM_STORE decodes that message plainly, so one call serves a list of sums and stores.
+ *   Decoded zeros (a stream that ran out of pairs, the bytes past the last whole word) are added like
+ *     any value: -0.0 under them becomes +0.0, as with a decode followed by an add.
+ *   Statuses: those of tdt_decode_batch_v (TDT_E_CAPACITY against the decoded size; only the first
+ *     decoded-size bytes of a larger destination are touched), and TDT_E_ELEMENT when d_outs[i] is
+ *     not a multiple of sizeof(T) or the decoded size is not; TDT_E_UNSUPPORTED for a blob of a
+ *     generic word size (not 1, 2, 4, 8, 16) with a code other than TDT_ELEM_STORE (with it the blob
+ *     decodes as in tdt_decode_batch_v); TDT_E_ARG for a code outside 0..4 (per message from d_elem,
+ *     the call's return value from `elem`).  A message whose status is not TDT_OK has length 0 and
+ *     its destination is untouched, byte for byte.
+ *   Addressing and context rules: those of tdt_decode_batch_v (blobs at any alignment, UNCP and TDT
+ *     blobs mixed, asynchronous, nothing read back, capturable once one eager call of the batch size
+ *     has grown the workspace). */
+int tdt_decode_accumulate_v(tdt_ctx *ctx, const uint8_t *const *d_blobs, const uint64_t *d_blob_len, uint32_t n_msgs,
+                            uint8_t *const *d_outs, const uint64_t *d_out_cap, const uint8_t *d_elem, int elem,
+                            uint64_t *d_out_len, int32_t *d_status, void *hip_stream);
 /* MIXED WORD SIZES — tdt_encode_batch_v with one record width per message (a mixed-precision
  * gradient list: bf16 / fp16 tensors at width 2 beside fp32 ones at 4 and fp64 / int64 ones at 8).
  * d_word_size[i] (device memory, n_msgs entries) is message i's width; the context's own word_size

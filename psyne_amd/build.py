@@ -28,8 +28,11 @@ PACK_SRC = CSRC / "tdt_pack.hip"  # the pack kernel of tdt_pack_v / tdt_encode_b
 SOURCES.append(PACK_SRC)
 RAWFB_SRC = CSRC / "tdt_rawfb.hip"  # the raw fallback's kernels (TDT_OPT_RAW_FALLBACK)
 SOURCES.append(RAWFB_SRC)
+DEC_ACC_SRC = CSRC / "tdt_dec_acc.hip"  # the decode-accumulate instances (tdt_decode_accumulate_v)
+# (its fp32 adds stay scalar v_add_f32: no packed fp32 forms in this object)
+DEC_ACC_FLAGS = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 # every source and header under csrc/ (tdt_api.hip includes the headers, directly or not)
-DEPS = SOURCES + [ENC_WS_SRC, ENC_SIZES_WS_SRC, ENC_MAPPED_WS_SRC] + sorted(CSRC.glob("*.h")) + [ROOT / "include" / "psyne_tdt.h"]
+DEPS = SOURCES + [DEC_ACC_SRC, ENC_WS_SRC, ENC_SIZES_WS_SRC, ENC_MAPPED_WS_SRC] + sorted(CSRC.glob("*.h")) + [ROOT / "include" / "psyne_tdt.h"]
 OBJ_DIR = PKG / "build"
 
 
@@ -41,7 +44,7 @@ def needs_build() -> bool:
 
 
 def build(force: bool = False, verbose: bool = False) -> pathlib.Path:
-    """Compile tdt_api.hip, tdt_anyws.hip, tdt_pack.hip, tdt_rawfb.hip and one tdt_enc_ws.hip, tdt_enc_sizes_ws.hip and
+    """Compile tdt_api.hip, tdt_anyws.hip, tdt_pack.hip, tdt_rawfb.hip, tdt_dec_acc.hip and one tdt_enc_ws.hip, tdt_enc_sizes_ws.hip and
     tdt_enc_mapped_ws.hip object per word size in parallel (the encode kernels dominate the compile time), then
     link libpsyne_tdt.so."""
     if force or needs_build():
@@ -49,6 +52,8 @@ def build(force: bool = False, verbose: bool = False) -> pathlib.Path:
         base = [HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-I", str(ROOT / "include")]
         jobs = [(base + ["-c", str(src), "-o", str(OBJ_DIR / (src.stem + ".o"))], OBJ_DIR / (src.stem + ".o"))
                 for src in SOURCES]
+        o = OBJ_DIR / (DEC_ACC_SRC.stem + ".o")
+        jobs.append((base + DEC_ACC_FLAGS + ["-c", str(DEC_ACC_SRC), "-o", str(o)], o))
         for ws in WORD_SIZES:
             o = OBJ_DIR / f"tdt_enc_ws{ws}.o"
             jobs.append((base + [f"-DPSY_INST_WS={ws}", "-c", str(ENC_WS_SRC), "-o", str(o)], o))

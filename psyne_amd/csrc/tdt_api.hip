@@ -58,6 +58,9 @@ PSY_ENC_EXT_WS(2)
 PSY_ENC_EXT_WS(4)
 PSY_ENC_EXT_WS(8)
 PSY_ENC_EXT_WS(16)
+// (the decode-accumulate instances: tdt_dec_acc.hip)
+#define PSY_DEC_ACC_EXT(...) extern template __global__ void __VA_ARGS__(psy::DecodeArgs);
+PSY_DEC_ACC_INSTANCES(PSY_DEC_ACC_EXT)
 #endif
 
 // The generic-word-size kernels live in tdt_anyws.hip; the diagnostic single-file builds leave
@@ -481,24 +484,9 @@ __global__ __launch_bounds__(256) void tdt_encode_copy_sizes_kernel(psy::EncodeA
     }
 }
 
-// decode: payload of a UNCP blob into its slot
-template <bool PAIR = false>
-__global__ __launch_bounds__(256) void tdt_decode_copy_kernel(psy::DecodeArgs a) {
-    const uint32_t n = __builtin_amdgcn_readfirstlane(*a.list_count);
-    const uint32_t q = threadIdx.x >> 4, l = threadIdx.x & 15u;
-    for (uint32_t i = blockIdx.x * 16u + q; i < n; i += gridDim.x * 16u) {
-        const uint32_t msg = a.list[i];
-        const uint64_t boff = a.in_off[msg];
-        const uint64_t len = a.in_len ? a.in_len[msg] : a.in_off[msg + 1] - boff;  // >= 4 (the plan)
-        const uint64_t ob = a.slot_off[psy::table_at<PAIR>(msg, 0)], osize = len - 4;
-        const bool fits = osize <= a.slot_off[psy::table_at<PAIR>(msg, 1)] - ob;
-        if (l == 0) {
-            if (a.out_len) a.out_len[msg] = fits ? osize : 0;
-            if (a.status) a.status[msg] = fits ? psy::ST_OK : psy::ST_CAPACITY;
-        }
-        if (fits) psy::copy_shifted<1, false>(a.out + ob, a.in + boff + 4, osize, l, kCopyListLanes);
-    }
-}
+// decode: payload of a UNCP blob into its slot — psy::tdt_decode_copy_kernel (tdt_decode.h), the same
+// sixteen lanes per entry
+static_assert(kCopyListLanes == psy::kDecCopyLanes, "one lane count for the encode and decode copy lists");
 
 // ---------------------------------------------------------------------------------------
 // Slotted encode (the hot path): a plan kernel sorts the messages into classes — large
@@ -1468,7 +1456,10 @@ int ensure_dlarge(PlanWS &w) {
 }
 
 // PAIR: a scattered batch (`v`): its slot table first, then the same classes through the PAIR instances
-template <bool PAIR = false>
+// ACC (PAIR only): decode-accumulate — the same plan, lists, grids, side stream, large-blob pipeline
+// and count history through the ACC instances of every kernel that writes decoded bytes; the
+// deferred launch sees only the generic-width blobs whose element code is TDT_ELEM_STORE
+template <bool PAIR = false, bool ACC = false>
 int launch_decode_slotted(tdt_ctx *c, PlanWS &pw, psy::DecodeArgs a, hipStream_t s, const Scatter *v = nullptr) {
     using namespace psy;  // (counter, list and kernel names)
     const uint32_t n = a.n_msgs;
@@ -1534,32 +1525,32 @@ int launch_decode_slotted(tdt_ctx *c, PlanWS &pw, psy::DecodeArgs a, hipStream_t
     }
     if (large_on) {
         const uint32_t gl = std::max(1u, std::min(lcap, 1024u));
-        hipLaunchKernelGGL(tdt_decode_lprep_kernel<PAIR>, dim3(gl), dim3(256), 0, ts, a);
+        hipLaunchKernelGGL((tdt_decode_lprep_kernel<PAIR, ACC>), dim3(gl), dim3(256), 0, ts, a);
         hipLaunchKernelGGL(tdt_decode_lblock_kernel, dim3(std::max(1u, std::min((bcap + 3) / 4, ovf / 4))), dim3(256), 0,
                            ts, a);
         hipLaunchKernelGGL(tdt_decode_lscan_kernel, dim3(gl, 2), dim3(64), 0, ts, a);
         // (the tile entries are large-blob records, not a list; no main launch before any count is known)
-        cls(nullptr, DC_TILES, guess(H, DC_TILES, tcap, 0), tcap, 64, ovf, ts, tdt_decode_ltile_kernel<0>,
-            tdt_decode_ltile_kernel<1>);
+        cls(nullptr, DC_TILES, guess(H, DC_TILES, tcap, 0), tcap, 64, ovf, ts, tdt_decode_ltile_kernel<0, ACC>,
+            tdt_decode_ltile_kernel<1, ACC>);
     }
     // the main list (one wave per blob), its kernels taking the big list's blobs first
     a.blist = list(DL_BIG);
     a.blist_count = cnt32 + lo32(DC_BIG);
     cls(list(DL_MAIN), DC_MAIN, (uint32_t)std::min<uint64_t>(n, (uint64_t)guess(H, DC_MAIN, n, n) + guess(H, DC_BIG, n, n)),
-        n, 64, ovf, s, tdt_decode_kernel<0, kDecWR, 0, PAIR>, tdt_decode_kernel<0, kDecWR, 1, PAIR>);
+        n, 64, ovf, s, tdt_decode_kernel<0, kDecWR, 0, PAIR, ACC>, tdt_decode_kernel<0, kDecWR, 1, PAIR, ACC>);
     a.blist = nullptr;
     const hipStream_t ss = forked && !c->small_main ? pw.side : s;
     // passthrough copies beside the main list
     if (copy_on) {
         a.list = list(DL_COPY);
         a.list_count = cnt32 + lo32(DC_UNCP);
-        hipLaunchKernelGGL(tdt_decode_copy_kernel<PAIR>, dim3(std::max(1u, std::min((uint32_t)c->cus * c->copy_wgs, (n + 15) / 16))),
+        hipLaunchKernelGGL((tdt_decode_copy_kernel<PAIR, ACC>), dim3(std::max(1u, std::min((uint32_t)c->cus * c->copy_wgs, (n + 15) / 16))),
                            dim3(256), 0, ss, a);
     }
     // small blobs: one-round windows (a third less LDS per wave: more blobs in flight per CU)
     if (small_on)
-        cls(list(DL_SMALL), DC_SMALL, guess(H, DC_SMALL, n, n), n, 64, ovf, ss, tdt_decode_kernel<0, 1, 0, PAIR>,
-            tdt_decode_kernel<0, 1, 1, PAIR>);
+        cls(list(DL_SMALL), DC_SMALL, guess(H, DC_SMALL, n, n), n, 64, ovf, ss, tdt_decode_kernel<0, 1, 0, PAIR, ACC>,
+            tdt_decode_kernel<0, 1, 1, PAIR, ACC>);
     if (forked && (st = join_side(pw, s))) return st;
     // the deferred blobs (generic word sizes): near-empty when no kernel above listed one.  (A
     // fixed grid: the plan's count snapshot is taken before the class kernels append to the list,
@@ -1567,7 +1558,7 @@ int launch_decode_slotted(tdt_ctx *c, PlanWS &pw, psy::DecodeArgs a, hipStream_t
     return decode_deferred(c, &pw == &c->pw, a, s, PAIR, cnt + DC_BYTES);
 }
 
-int decode_common(tdt_ctx *c, bool sizes_only, psy::DecodeArgs a, const Where &w) {
+int decode_common(tdt_ctx *c, bool sizes_only, psy::DecodeArgs a, const Where &w, bool acc = false) {
     const Scatter *v = w.v;
     const uint32_t n_msgs = a.n_msgs;
     if (!c) return set_err(TDT_E_ARG, "null context");
@@ -1588,7 +1579,8 @@ int decode_common(tdt_ctx *c, bool sizes_only, psy::DecodeArgs a, const Where &w
     if (sizes_only) {
         hipLaunchKernelGGL(psy::tdt_decode_sizes_kernel, dim3((n_msgs + 255) / 256), dim3(256), 0, s, a);
     } else if (slotted) {
-        st = v ? launch_decode_slotted<true>(c, w.pws ? *w.pws : c->pw, a, s, v)
+        st = v ? (acc ? launch_decode_slotted<true, true>(c, w.pws ? *w.pws : c->pw, a, s, v)
+                      : launch_decode_slotted<true>(c, w.pws ? *w.pws : c->pw, a, s, v))
                : launch_decode_slotted(c, w.pws ? *w.pws : c->pw, a, s);
         if (st) return st;
     } else {
@@ -3297,6 +3289,24 @@ int tdt_decode_batch_v(tdt_ctx *ctx, const uint8_t *const *d_blobs, const uint64
     return decode_common(ctx, false, a, w);
 }
 
+int tdt_decode_accumulate_v(tdt_ctx *ctx, const uint8_t *const *d_blobs, const uint64_t *d_blob_len, uint32_t n_msgs,
+                            uint8_t *const *d_outs, const uint64_t *d_out_cap, const uint8_t *d_elem, int elem,
+                            uint64_t *d_out_len, int32_t *d_status, void *stream) {
+    if (!d_elem && (elem < TDT_ELEM_STORE || elem > TDT_ELEM_F64)) return set_err(TDT_E_ARG, "unknown element code");
+    const Scatter v = scatter_of(d_blobs, d_blob_len, d_outs, d_out_cap);
+    psy::DecodeArgs a{};  // (as tdt_decode_batch_v)
+    a.in_off = v.ptr;
+    a.in_len = d_blob_len;
+    a.n_msgs = n_msgs;
+    a.status = d_status;
+    a.out_len = d_out_len;
+    a.elem_codes = d_elem;
+    a.elem = (uint32_t)elem;
+    Where w(stream);
+    w.v = &v;
+    return decode_common(ctx, false, a, w, true);
+}
+
 int tdt_decoded_sizes_v(tdt_ctx *ctx, const uint8_t *const *d_blobs, const uint64_t *d_blob_len, uint32_t n_msgs,
                         uint64_t *d_sizes, int32_t *d_status, void *stream) {
     if (n_msgs && !d_blob_len) return set_err(TDT_E_ARG, "null blob lengths");
@@ -3460,6 +3470,7 @@ const char *tdt_status_string(int status) {
         case TDT_E_HIP: return "TDT: HIP runtime error";
         case TDT_E_CAPTURE: return "TDT: workspace growth needed under stream capture";
         case TDT_E_ARG: return "TDT: invalid argument";
+        case TDT_E_ELEMENT: return "TDT: destination or decoded size does not hold whole aligned elements";
     }
     return "TDT: unknown status";
 }

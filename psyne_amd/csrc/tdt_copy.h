@@ -118,5 +118,28 @@ __device__ __forceinline__ void copy_shifted(uint8_t *dst, const uint8_t *src, u
         });
 }
 
+// The accumulating copy (decode-accumulate of an UNCP blob): dst[k] += src[k] as elements of code e
+// (tdt_device.h).  dst is element-aligned and len a whole number of elements, so the head and the
+// tail are whole elements: byte(i) accumulates the element that starts at i and does nothing at the
+// other bytes of it; store adds a chunk to the 16 bytes at its place.  src stays at any alignment
+// (an UNCP payload is 4 bytes off its blob's start): its head and tail elements are read as bytes.
+template <int U>
+__device__ __forceinline__ void acc_copy_shifted(uint8_t *dst, const uint8_t *src, uint64_t len, uint64_t t, uint64_t T,
+                                                 uint32_t e) {
+    const uint32_t es = elem_size(e);
+    copy_shifted_with<U>(
+        dst, src, len, t, T,
+        [=](uint64_t i) {
+            if (i & (es - 1)) return;
+            const uint8_t *s = src + i;
+            const uint32_t lo = es == 2 ? (uint32_t)s[0] | ((uint32_t)s[1] << 8) : ld_u32_bytes(s);
+            acc_elem(dst + i, lo, es == 8 ? ld_u32_bytes(s + 4) : 0u, e);
+        },
+        [](const uint32_t *q) { return gload<uint32_t>(q); },
+        [=](CopyWords *p, CopyWords w) {
+            st16_nt(p, acc4(acc_ld16(p), make_uint4(w.x, w.y, w.z, w.w), e));
+        });
+}
+
 }  // namespace psy
 #endif

@@ -22,6 +22,7 @@
 //      when stream segments are dword-sized) and scatters them into word order with
 //      v_perm_b32 selectors (recombine_byte_streams), one 16-byte store per lane.
 #pragma once
+#include "tdt_copy.h"
 #include "tdt_device.h"
 #include "tdt_encode.h"
 #include "tdt_plan.h"
@@ -67,7 +68,29 @@ struct DecodeArgs {
     // ids to dlist (length *dcount, one atomic each); a follow-up launch decodes the listed blobs
     uint32_t *dlist;
     uint32_t *dcount;
+    // decode-accumulate (the ACC instances; no other kernel reads these): message i's element code
+    // (TDT_ELEM_*), or, with a null array, one code for every message
+    const uint8_t *elem_codes;
+    uint32_t elem;
 };
+
+// blob_check's status of a decode-accumulate message whose destination is not aligned to its element
+// or whose decoded size is not a whole number of elements (TDT_E_ELEMENT)
+constexpr uint32_t ST_ELEMENT = 13;
+
+// Message msg's element code in an ACC instance (uniform over the wave)
+__device__ __forceinline__ uint32_t acc_code(const DecodeArgs &a, uint32_t msg) {
+    return (uint32_t)__builtin_amdgcn_readfirstlane((int)(a.elem_codes ? (uint32_t)a.elem_codes[msg] : a.elem));
+}
+// The status of an accumulating message that is st without its element: an unknown code is an
+// argument error, and a destination or a decoded size that does not hold whole aligned elements is
+// refused (the caller then writes length 0 and touches no byte of the destination)
+__device__ __forceinline__ uint32_t acc_status(uint32_t st, uint32_t e, const uint8_t *dst, uint64_t osize) {
+    if (st != ST_OK) return st;
+    if (e > kElemMax) return ST_ARG;
+    if (e != kElemStore && (((uintptr_t)dst | osize) & (elem_size(e) - 1u)) != 0) return ST_ELEMENT;
+    return ST_OK;
+}
 
 // blob_check's internal status of a valid blob whose word size (<= 64, not 1/2/4/8/16) the
 // kernels of this file do not decode: deferred to tdt_anyws.hip.  Never reported to the caller.
@@ -297,11 +320,15 @@ __device__ __forceinline__ uint32_t gload_blk(const uint32_t *p) {
 #endif
 }
 
-template <int WR_ = kDecWR>
+// ACC (decode-accumulate): with an element code `elem` other than kElemStore the round's groups are
+// added to the destination.  In a whole aligned round the lane's 16 destination bytes are loaded
+// when the round starts, so the trip to memory lies under the round's LDS work, and are consumed
+// at the store; every other group goes through acc16_any.
+template <int WR_ = kDecWR, bool ACC = false>
 __device__ __forceinline__ void decode_fast(const FastHdr &H, uint8_t *smem, const uint8_t *blob, const uint8_t *blim,
                                             uint8_t *dst, uint32_t ngroups, uint64_t wbytes, uint32_t g_lo = 0,
                                             uint32_t g_hi = 0, const uint32_t *b0 = nullptr, const uint32_t *s0 = nullptr,
-                                            const uint8_t *bc = nullptr, uint32_t bcl = 0) {
+                                            const uint8_t *bc = nullptr, uint32_t bcl = 0, uint32_t elem = 0) {
     using Lay = DecLayoutT<WR_>;
     constexpr uint32_t WR = WR_;
     const uint32_t lane = (uint32_t)lane_id();
@@ -572,6 +599,10 @@ __device__ __forceinline__ void decode_fast(const FastHdr &H, uint8_t *smem, con
             if (g0 >= g_hi) break;
             const uint32_t hoffb = fh + 2u * rl * 64u * fseg;
             uint8_t *const planes = smem + pl_base + rl * pl_step;
+            uint4 dcur = make_uint4(0, 0, 0, 0);
+            if constexpr (ACC) {
+                if (elem != kElemStore && dal16 && g0 + 64u <= wg16) dcur = acc_ld16(dst + 16ull * (g0 + lane));
+            }
             // lanes 8-15 of every 16 read their second half first: with 32-byte lane rows the
             // two ds_read_b128 are then bank-conflict-free (MI355X_MICROARCH.md §LDS groups)
 #ifndef PSY_DEC_NOSWAP
@@ -653,6 +684,9 @@ __device__ __forceinline__ void decode_fast(const FastHdr &H, uint8_t *smem, con
             const uint32_t g = g0 + lane;
             if (dal16 && g0 + 64u <= wg16) {
                 // a whole aligned round (uniform): one 16-byte store per lane, no per-lane tests
+                if constexpr (ACC) {
+                    if (elem != kElemStore) o = acc4(dcur, o, elem);
+                }
 #ifndef PSY_X_NOSTORE
                 st16_nt(dst + 16ull * g, o);
 #else
@@ -660,7 +694,8 @@ __device__ __forceinline__ void decode_fast(const FastHdr &H, uint8_t *smem, con
 #endif
             } else if (g < ngroups) {
                 const uint64_t vb64 = wbytes - 16ull * g;
-                st16_any(dst + 16ull * g, o, vb64 >= 16 ? 16 : (int)vb64);
+                if (ACC && elem != kElemStore) acc16_any(dst + 16ull * g, o, vb64 >= 16 ? 16 : (int)vb64, elem);
+                else st16_any(dst + 16ull * g, o, vb64 >= 16 ? 16 : (int)vb64);
             }
             // the planes' bytes are heads slots again: empty for the windows that follow (the
             // gather's reads precede these writes in the wave's LDS order)
@@ -933,8 +968,13 @@ __device__ __forceinline__ FastHdr parse_fast(const uint8_t *blob, uint64_t len,
 // One blob, one wave (LB: compacted output by look-back; else its slot).  PAIR: slot_off is a
 // (begin, end) pair table (table_at, tdt_plan.h) — the instances of the scattered batches
 // (tdt_decode_batch_v: in and out are null, in_off holds the blobs' addresses beside in_len).
-template <int LB, int WR = kDecWR, bool PAIR = false>
+// ACC: the decode-accumulate instances (slotted only).  The message's element code, uniform over the
+// wave, turns every store of a decoded byte into an add on its element; kElemStore keeps the plain
+// decode.  A message that is refused (acc_status, or a generic width with a code other than
+// kElemStore: those kernels have no accumulate form) leaves its destination untouched.
+template <int LB, int WR = kDecWR, bool PAIR = false, bool ACC = false>
 __device__ __forceinline__ void decode_one(const DecodeArgs &a, uint8_t *smem, uint32_t msg) {
+    static_assert(!ACC || !LB, "decode-accumulate is a slotted call");
     using Lay = DecLayoutT<WR>;
     uint32_t *misc = reinterpret_cast<uint32_t *>(smem + Lay::OFF_MISC);
     uint8_t *hdrc = smem + Lay::OFF_BLOB;
@@ -951,6 +991,8 @@ __device__ __forceinline__ void decode_one(const DecodeArgs &a, uint8_t *smem, u
     }
     const uint8_t *blob = a.in + boff;
     const uint8_t *blim = blob + len;
+    uint32_t elem = kElemStore;
+    if constexpr (ACC) elem = acc_code(a, msg);
 
     // ------------------------------------------------ blob cache: its first BLOBC bytes in LDS
     // (256 with the main list's windows; 2,112 with one-round windows: whole 1 KiB-message blobs)
@@ -1018,7 +1060,11 @@ __device__ __forceinline__ void decode_one(const DecodeArgs &a, uint8_t *smem, u
             ob = slot_b;
             fits = osize <= slot_e - ob;
         }
-        const uint32_t st = fits ? ST_OK : ST_CAPACITY;
+        uint32_t st = fits ? ST_OK : ST_CAPACITY;
+        if constexpr (ACC) {
+            st = acc_status(st, elem, a.out + ob, osize);
+            fits = st == ST_OK;
+        }
         if (lane == 0) {
             if constexpr (LB) {
                 a.out_off[msg] = ob;
@@ -1030,15 +1076,20 @@ __device__ __forceinline__ void decode_one(const DecodeArgs &a, uint8_t *smem, u
         }
         if (!fits) return;
         uint8_t *dst = a.out + ob;
+        const bool acc = ACC && elem != kElemStore;
         if (H.kind == 1) {
-            team_copy_g2g<64>(dst, blob + 4, len - 4);
+            if (acc) acc_copy_shifted<1>(dst, blob + 4, len - 4, (uint64_t)lane, 64, elem);
+            else team_copy_g2g<64>(dst, blob + 4, len - 4);
             return;
         }
         const uint64_t wbytes = (uint64_t)(H.orig / H.ws) * H.ws;
         // recombine :617 zero-initialises; bytes past the last whole word stay zero
-        if (H.orig > wbytes) team_zero<64>(dst + wbytes, H.orig - wbytes);
-        decode_fast<WR>(H, smem, blob, blim, dst, (uint32_t)((wbytes + 15) / 16), wbytes, 0, 0, nullptr, nullptr,
-                        WR == 1 ? hdrc : nullptr, WR == 1 ? hcl : 0u);
+        if (H.orig > wbytes) {
+            if (acc) team_acc_zero<64>(dst + wbytes, H.orig - wbytes, elem);
+            else team_zero<64>(dst + wbytes, H.orig - wbytes);
+        }
+        decode_fast<WR, ACC>(H, smem, blob, blim, dst, (uint32_t)((wbytes + 15) / 16), wbytes, 0, 0, nullptr, nullptr,
+                             WR == 1 ? hdrc : nullptr, WR == 1 ? hcl : 0u, elem);
         return;
     }
     auto rd32 = [&](uint64_t off) -> uint32_t {
@@ -1141,6 +1192,14 @@ __device__ __forceinline__ void decode_one(const DecodeArgs &a, uint8_t *smem, u
         ob = slot_b;
         fits = osize <= slot_e - ob;
     }
+    if (ACC && st == ST_DEFER && elem != kElemStore) {
+        // the generic-width kernels only store: not listed, and nothing of its destination is touched
+        if (lane == 0) {
+            if (a.out_len) a.out_len[msg] = 0;
+            if (a.status) a.status[msg] = (int32_t)(elem > kElemMax ? (uint32_t)ST_ARG : (uint32_t)ST_UNSUPPORTED);
+        }
+        return;
+    }
     if (st == ST_DEFER) {
         // a generic word size: placed here (the look-back has published its size), decoded —
         // status, length and bytes — by the follow-up launch over dlist (tdt_anyws.hip)
@@ -1159,6 +1218,7 @@ __device__ __forceinline__ void decode_one(const DecodeArgs &a, uint8_t *smem, u
         return;
     }
     if (st == ST_OK && !fits) st = ST_CAPACITY;
+    if constexpr (ACC) st = acc_status(st, elem, a.out + ob, osize);
     if (lane == 0) {
         if constexpr (LB) {
             a.out_off[msg] = ob;
@@ -1171,8 +1231,10 @@ __device__ __forceinline__ void decode_one(const DecodeArgs &a, uint8_t *smem, u
     if (st != ST_OK) return;
     PSY_PROF_MARK(8);
     uint8_t *dst = a.out + ob;
+    const bool acc = ACC && elem != kElemStore;
     if (misc[D_UNCP]) {
-        team_copy_g2g<64>(dst, blob + 4, len - 4);
+        if (acc) acc_copy_shifted<1>(dst, blob + 4, len - 4, (uint64_t)lane, 64, elem);
+        else team_copy_g2g<64>(dst, blob + 4, len - 4);
         return;
     }
     const uint32_t orig = __builtin_amdgcn_readfirstlane(misc[D_ORIG]);
@@ -1180,7 +1242,10 @@ __device__ __forceinline__ void decode_one(const DecodeArgs &a, uint8_t *smem, u
     const uint64_t wc = orig / ws;
     const uint64_t wbytes = wc * ws;
     // recombine :617 zero-initialises; bytes past the last whole word stay zero
-    if (orig > wbytes) team_zero<64>(dst + wbytes, orig - wbytes);
+    if (orig > wbytes) {
+        if (acc) team_acc_zero<64>(dst + wbytes, orig - wbytes, elem);
+        else team_zero<64>(dst + wbytes, orig - wbytes);
+    }
     if (wc == 0) return;
     const uint32_t WPG = 16 / ws;
     const uint32_t nref = __builtin_amdgcn_readfirstlane(misc[D_NREF]);
@@ -1387,7 +1452,8 @@ __device__ __forceinline__ void decode_one(const DecodeArgs &a, uint8_t *smem, u
             const uint32_t g = g0 + (uint32_t)lane;
             if (g < ngroups) {
                 const uint64_t vb64 = wbytes - 16ull * g;
-                st16_any(dst + 16ull * g, o, vb64 >= 16 ? 16 : (int)vb64);
+                if (acc) acc16_any(dst + 16ull * g, o, vb64 >= 16 ? 16 : (int)vb64, elem);
+                else st16_any(dst + 16ull * g, o, vb64 >= 16 ? 16 : (int)vb64);
             }
             // the planes' bytes are heads slots again: empty for the windows that follow (the
             // gather's reads precede these writes in the wave's LDS order)
@@ -1543,9 +1609,12 @@ __global__ __launch_bounds__(1024) void tdt_decode_plan_kernel(DPlanArgs p) {
     }
 }
 
+#endif  // PSY_DEC_INST_TU
+
 // Prep: one workgroup per large blob; wave 0 parses and places it, then every thread writes
-// its block-slot and tile entries (kNone where no pass has work).
-template <bool PAIR = false>
+// its block-slot and tile entries (kNone where no pass has work).  ACC: a message acc_status
+// refuses is not tiled, so its tiles write nothing.
+template <bool PAIR = false, bool ACC = false>
 __global__ __launch_bounds__(256) void tdt_decode_lprep_kernel(DecodeArgs a) {
     __shared__ __attribute__((aligned(16))) uint8_t smem[DecLayout::BYTES];
     __shared__ uint32_t s_tiled, s_fast;
@@ -1576,17 +1645,26 @@ __global__ __launch_bounds__(256) void tdt_decode_lprep_kernel(DecodeArgs a) {
         uint32_t tiled = 0, fast = 0;
         if (H.kind != 0) {
             const uint64_t ob = a.slot_off[table_at<PAIR>(msg, 0)];
-            const bool fits = H.osize <= a.slot_off[table_at<PAIR>(msg, 1)] - ob;
+            bool fits = H.osize <= a.slot_off[table_at<PAIR>(msg, 1)] - ob;
+            uint32_t st = fits ? ST_OK : ST_CAPACITY, elem = kElemStore;
+            if constexpr (ACC) {
+                elem = acc_code(a, msg);
+                st = acc_status(st, elem, a.out + ob, H.osize);
+                fits = st == ST_OK;
+            }
             if (lane == 0) {
                 if (a.out_len) a.out_len[msg] = fits ? H.osize : 0;
-                if (a.status) a.status[msg] = fits ? ST_OK : ST_CAPACITY;
+                if (a.status) a.status[msg] = (int32_t)st;
             }
             if (fits) {
                 tiled = 1;
                 fast = H.kind == 2 ? 1u : 0u;
                 if (H.kind == 2) {
                     const uint64_t wbytes = (uint64_t)(H.orig / H.ws) * H.ws;
-                    if (H.orig > wbytes) team_zero<64>(a.out + ob + wbytes, H.orig - wbytes);
+                    if (H.orig > wbytes) {
+                        if (ACC && elem != kElemStore) team_acc_zero<64>(a.out + ob + wbytes, H.orig - wbytes, elem);
+                        else team_zero<64>(a.out + ob + wbytes, H.orig - wbytes);
+                    }
                 }
                 if (lane == 0) {
                     m->H = H;
@@ -1596,7 +1674,7 @@ __global__ __launch_bounds__(256) void tdt_decode_lprep_kernel(DecodeArgs a) {
                 }
             }
         } else {
-            decode_one<0, kDecWR, PAIR>(a, smem, msg);  // any other shape (or an error): one wave, whole
+            decode_one<0, kDecWR, PAIR, ACC>(a, smem, msg);  // any other shape (or an error): one wave, whole
         }
         if (lane == 0) {
             m->tiled = tiled;
@@ -1611,6 +1689,7 @@ __global__ __launch_bounds__(256) void tdt_decode_lprep_kernel(DecodeArgs a) {
     }
 }
 
+#ifndef PSY_DEC_INST_TU
 // Block pass: one wave per 512-pair block (8 pairs per lane): the block's count sum.
 __global__ __launch_bounds__(256) void tdt_decode_lblock_kernel(DecodeArgs a) {
     const uint32_t nslots = __builtin_amdgcn_readfirstlane(umin(a.pcnt[lo32(DC_BLOCKS)], a.bcap));
@@ -1669,6 +1748,7 @@ __global__ __launch_bounds__(64) void tdt_decode_lscan_kernel(DecodeArgs a) {
 
 // Tile pass: one wave per 32 KiB output tile (main launch: tiles [list_base, list_base + grid);
 // overflow launch, PS = 1: the tiles past it, grid-stride).
+template <bool ACC = false>
 __device__ __forceinline__ void decode_ltile(const DecodeArgs &a, uint8_t *smem, uint32_t slot) {
     const uint32_t j = a.tent[slot];
     if (j == kNone) return;
@@ -1680,11 +1760,15 @@ __device__ __forceinline__ void decode_ltile(const DecodeArgs &a, uint8_t *smem,
     const uint8_t *blob = a.in + boff;
     uint8_t *dst = a.out + m->ob;
     const FastHdr H = m->H;
+    uint32_t elem = kElemStore;
+    if constexpr (ACC) elem = acc_code(a, msg);  // (a code the prep pass accepted)
     if (H.kind == 1) {
         const uint64_t o0 = 16ull * kDecTileGroups * t;
         if (o0 < H.osize) {
             const uint64_t nb = H.osize - o0 < 16ull * kDecTileGroups ? H.osize - o0 : 16ull * kDecTileGroups;
-            team_copy_g2g<64>(dst + o0, blob + 4 + o0, nb);
+            // (a tile starts a multiple of 32 KiB into an element-aligned destination: whole elements)
+            if (ACC && elem != kElemStore) acc_copy_shifted<1>(dst + o0, blob + 4 + o0, nb, (uint64_t)lane_id(), 64, elem);
+            else team_copy_g2g<64>(dst + o0, blob + 4 + o0, nb);
         }
         return;
     }
@@ -1708,10 +1792,10 @@ __device__ __forceinline__ void decode_ltile(const DecodeArgs &a, uint8_t *smem,
             }
         }
     }
-    decode_fast(H, smem, blob, blob + len, dst, ngroups, wbytes, g_lo, g_hi, b0, s0);
+    decode_fast<kDecWR, ACC>(H, smem, blob, blob + len, dst, ngroups, wbytes, g_lo, g_hi, b0, s0, nullptr, 0u, elem);
 }
 
-template <int PS = 0>
+template <int PS = 0, bool ACC = false>
 __global__ __launch_bounds__(64) void tdt_decode_ltile_kernel(DecodeArgs a) {
     __shared__ __attribute__((aligned(16))) uint8_t smem[DecLayout::BYTES];
     const uint32_t nt = __builtin_amdgcn_readfirstlane(umin(a.pcnt[lo32(DC_TILES)], a.tcap));
@@ -1719,10 +1803,10 @@ __global__ __launch_bounds__(64) void tdt_decode_ltile_kernel(DecodeArgs a) {
     if constexpr (PS) {
         for (uint32_t i = i0; i < nt; i += gridDim.x) {
             if (i != i0) team_sync<1>();
-            decode_ltile(a, smem, i);
+            decode_ltile<ACC>(a, smem, i);
         }
     } else {
-        if (i0 < nt) decode_ltile(a, smem, i0);
+        if (i0 < nt) decode_ltile<ACC>(a, smem, i0);
     }
 }
 
@@ -1847,8 +1931,8 @@ __global__ __launch_bounds__(64 * NW) void tdt_decode_one_kernel(DecodeArgs a) {
 // them from the plan's list (or, without one, the workgroup id).
 // List entries are bounded by the plan's device-side count (main launch: one blob per wave over
 // [list_base, list_base + grid); overflow launch, PS = 1: the entries past it, grid-stride).
-template <int LB, int WR = kDecWR, int PS = 0, bool PAIR = false>
-__global__ __launch_bounds__(64, LB ? 6 : 8) void tdt_decode_kernel(DecodeArgs a) {
+template <int LB, int WR = kDecWR, int PS = 0, bool PAIR = false, bool ACC = false>
+__global__ __launch_bounds__(64, LB ? 6 : ACC ? 5 : 8) void tdt_decode_kernel(DecodeArgs a) {  // (ACC: out of scratch)
     static_assert(!PAIR || !LB, "scattered batches are slotted");
     __shared__ __attribute__((aligned(16))) uint8_t smem[DecLayoutT<WR>::BYTES];
     if constexpr (LB) {
@@ -1864,7 +1948,7 @@ __global__ __launch_bounds__(64, LB ? 6 : 8) void tdt_decode_kernel(DecodeArgs a
         if constexpr (PS) {
             for (uint32_t i = i0; i < cnt; i += gridDim.x) {
                 if (i != i0) team_sync<1>();
-                decode_one<LB, WR, PAIR>(a, smem, entry(i));
+                decode_one<LB, WR, PAIR, ACC>(a, smem, entry(i));
             }
         } else {
             // the list entries are read beside the counts, not after them (i0 < n_msgs = every
@@ -1872,9 +1956,54 @@ __global__ __launch_bounds__(64, LB ? 6 : 8) void tdt_decode_kernel(DecodeArgs a
             const uint32_t ic = i0 < a.n_msgs ? i0 : a.n_msgs - 1u;
             const uint32_t eb = a.blist ? a.blist[ic] : 0u, el = a.list[ic];
             if (i0 >= cnt) return;
-            decode_one<LB, WR, PAIR>(a, smem, i0 < nb ? eb : (nb == 0u ? el : a.list[i0 - nb]));
+            decode_one<LB, WR, PAIR, ACC>(a, smem, i0 < nb ? eb : (nb == 0u ? el : a.list[i0 - nb]));
         }
     }
 }
+
+// Passthrough copies (UNCP blobs below the tiled path's threshold): the payload into its slot.
+// Sixteen lanes per entry, 16 entries per 256-lane workgroup, grid-stride over the list (its length
+// is device data); the sixteen lanes run the shared copy (copy_shifted, tdt_copy.h), the ACC
+// instance its accumulating form.
+constexpr uint32_t kDecCopyLanes = 16;  // (q and l below: threadIdx.x >> 4, & 15)
+static_assert(kDecCopyLanes >= kCopyMinT, "copy_shifted: one byte store per lane covers the head and the tail");
+template <bool PAIR = false, bool ACC = false>
+__global__ __launch_bounds__(256) void tdt_decode_copy_kernel(DecodeArgs a) {
+    const uint32_t n = __builtin_amdgcn_readfirstlane(*a.list_count);
+    const uint32_t q = threadIdx.x >> 4, l = threadIdx.x & 15u;
+    for (uint32_t i = blockIdx.x * 16u + q; i < n; i += gridDim.x * 16u) {
+        const uint32_t msg = a.list[i];
+        const uint64_t boff = a.in_off[msg];
+        const uint64_t len = a.in_len ? a.in_len[msg] : a.in_off[msg + 1] - boff;  // >= 4 (the plan)
+        const uint64_t ob = a.slot_off[table_at<PAIR>(msg, 0)], osize = len - 4;
+        bool fits = osize <= a.slot_off[table_at<PAIR>(msg, 1)] - ob;
+        uint32_t st = fits ? ST_OK : ST_CAPACITY, elem = kElemStore;
+        if constexpr (ACC) {  // (sixteen entries per workgroup: the code is per lane group here, not per wave)
+            elem = a.elem_codes ? (uint32_t)a.elem_codes[msg] : a.elem;
+            st = acc_status(st, elem, a.out + ob, osize);
+            fits = st == ST_OK;
+        }
+        if (l == 0) {
+            if (a.out_len) a.out_len[msg] = fits ? osize : 0;
+            if (a.status) a.status[msg] = (int32_t)st;
+        }
+        if (!fits) continue;
+        if (ACC && elem != kElemStore) acc_copy_shifted<1>(a.out + ob, a.in + boff + 4, osize, l, kDecCopyLanes, elem);
+        else copy_shifted<1, false>(a.out + ob, a.in + boff + 4, osize, l, kDecCopyLanes);
+    }
+}
+
+// The decode-accumulate instances (scattered batches only), defined in tdt_dec_acc.hip and declared
+// where they are launched: the two one-wave classes with their overflow forms, the large-blob prep
+// and tile passes, and the copy list.
+#define PSY_DEC_ACC_INSTANCES(X)                                               \
+    X(psy::tdt_decode_kernel<0, psy::kDecWR, 0, true, true>)                   \
+    X(psy::tdt_decode_kernel<0, psy::kDecWR, 1, true, true>)                   \
+    X(psy::tdt_decode_kernel<0, 1, 0, true, true>)                             \
+    X(psy::tdt_decode_kernel<0, 1, 1, true, true>)                             \
+    X(psy::tdt_decode_lprep_kernel<true, true>)                                \
+    X(psy::tdt_decode_ltile_kernel<0, true>)                                   \
+    X(psy::tdt_decode_ltile_kernel<1, true>)                                   \
+    X(psy::tdt_decode_copy_kernel<true, true>)
 
 }  // namespace psy

@@ -656,6 +656,106 @@ __device__ __forceinline__ void team_zero(uint8_t *dst, uint64_t len) {
     for (uint64_t k = head + body + tid; k < len; k += TEAM) dst[k] = 0;
 }
 
+// ---------------------------------------------------------------------------------------
+// Decode-accumulate (tdt_decode_accumulate_v): the decoded bytes are ADDED to the destination as
+// elements of one type instead of stored.  The element code (TDT_ELEM_* of psyne_tdt.h) is uniform
+// over a wave, so every helper branches on it with a scalar branch; one IEEE add per element, round
+// to nearest even, subnormals kept.  Destinations are element-aligned and lengths whole elements
+// (the kernels refuse anything else before they touch a byte), and element sizes divide 16: an
+// element never straddles a 16-byte group.
+constexpr uint32_t kElemStore = 0, kElemF32 = 1, kElemF16 = 2, kElemBF16 = 3, kElemF64 = 4, kElemMax = 4;
+
+__device__ __forceinline__ uint32_t elem_size(uint32_t e) { return e == kElemF32 ? 4u : e == kElemF64 ? 8u : 2u; }
+
+typedef _Float16 psy_h2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint32_t add_f32(uint32_t a, uint32_t b) {
+    return __float_as_uint(__uint_as_float(a) + __uint_as_float(b));
+}
+__device__ __forceinline__ uint32_t add_h2(uint32_t a, uint32_t b) {  // v_pk_add_f16
+    return __builtin_bit_cast(uint32_t, __builtin_bit_cast(psy_h2, a) + __builtin_bit_cast(psy_h2, b));
+}
+// bf16 through fp32: widened by a shift, one fp32 add (exact to 24 bits >= 2·8 + 2, so the second
+// rounding below equals rounding the true sum once), then round to nearest even on the integer
+__device__ __forceinline__ uint32_t bf16_of_f32(uint32_t x) {
+    const uint32_t r = (x + 0x7fffu + ((x >> 16) & 1u)) >> 16;
+    return (x & 0x7fffffffu) > 0x7f800000u ? 0x7fc0u : r;  // (a NaN stays one)
+}
+__device__ __forceinline__ uint32_t add_bf2(uint32_t a, uint32_t b) {
+    const uint32_t lo = add_f32(a << 16, b << 16), hi = add_f32(a & 0xffff0000u, b & 0xffff0000u);
+    return bf16_of_f32(lo) | (bf16_of_f32(hi) << 16);
+}
+__device__ __forceinline__ uint2 add_f64(uint32_t alo, uint32_t ahi, uint32_t blo, uint32_t bhi) {
+    const double s = __hiloint2double((int)ahi, (int)alo) + __hiloint2double((int)bhi, (int)blo);
+    return make_uint2((uint32_t)__double2loint(s), (uint32_t)__double2hiint(s));
+}
+
+// The destination's 16 bytes of an aligned group (PSY_ACC_LDNT: a non-temporal load, the A/B of
+// DESIGN §5; the default is the plain load, the store is non-temporal as every output store)
+__device__ __forceinline__ uint4 acc_ld16(const void *p) {
+#ifdef PSY_ACC_LDNT
+    const psy_u32x4 d = __builtin_nontemporal_load((const __attribute__((address_space(1))) psy_u32x4 *)(p));
+#else
+    const psy_u32x4 d = gload<psy_u32x4>(p);
+#endif
+    return make_uint4(d.x, d.y, d.z, d.w);
+}
+
+// d + v over the four dwords of a 16-byte group (e: uniform, not kElemStore)
+__device__ __forceinline__ uint4 acc4(uint4 d, uint4 v, uint32_t e) {
+    if (e == kElemF32) return make_uint4(add_f32(d.x, v.x), add_f32(d.y, v.y), add_f32(d.z, v.z), add_f32(d.w, v.w));
+    if (e == kElemF16) return make_uint4(add_h2(d.x, v.x), add_h2(d.y, v.y), add_h2(d.z, v.z), add_h2(d.w, v.w));
+    if (e == kElemBF16) return make_uint4(add_bf2(d.x, v.x), add_bf2(d.y, v.y), add_bf2(d.z, v.z), add_bf2(d.w, v.w));
+    const uint2 a = add_f64(d.x, d.y, v.x, v.y), b = add_f64(d.z, d.w, v.z, v.w);
+    return make_uint4(a.x, a.y, b.x, b.y);
+}
+
+// The element at p (element-aligned) += the element whose bits are (lo, hi) (hi: f64 only)
+__device__ __forceinline__ void acc_elem(uint8_t *p, uint32_t lo, uint32_t hi, uint32_t e) {
+    if (e == kElemF32) {
+        uint32_t *q = reinterpret_cast<uint32_t *>(p);
+        *q = add_f32(*q, lo);
+    } else if (e == kElemF64) {
+        uint2 *q = reinterpret_cast<uint2 *>(p);
+        const uint2 d = *q;
+        *q = add_f64(d.x, d.y, lo, hi);
+    } else {
+        uint16_t *q = reinterpret_cast<uint16_t *>(p);
+        const uint32_t d = *q, v = lo & 0xffffu;
+        *q = (uint16_t)(e == kElemF16 ? add_h2(d, v) : add_bf2(d, v));
+    }
+}
+
+// st16_any's accumulating form: the first `valid` bytes of v (whole elements) are added to the
+// elements at p (element-aligned); a whole aligned group is one 16-byte load, add and store.
+__device__ __forceinline__ void acc16_any(uint8_t *p, uint4 v, int valid, uint32_t e) {
+    if (valid >= 16 && ((uintptr_t)p & 15) == 0) {
+        st16_nt(p, acc4(acc_ld16(p), v, e));
+        return;
+    }
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+    if (e == kElemF64) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+            if (8 * i < valid) acc_elem(p + 8 * i, w[2 * i], w[2 * i + 1], e);
+    } else if (e == kElemF32) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            if (4 * i < valid) acc_elem(p + 4 * i, w[i], 0u, e);
+    } else {
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+            if (2 * i < valid) acc_elem(p + 2 * i, w[i >> 1] >> (16 * (i & 1)), 0u, e);
+    }
+}
+
+// team_zero's accumulating form: + 0 on every element of [dst, dst + len) (fewer than 16 bytes: the
+// bytes past a blob's last whole word), so that -0.0 there becomes +0.0 as an add of zeros makes it
+template <int TEAM>
+__device__ __forceinline__ void team_acc_zero(uint8_t *dst, uint64_t len, uint32_t e) {
+    const uint64_t i = (uint64_t)threadIdx.x % TEAM * elem_size(e);
+    if (threadIdx.x % TEAM < 16 && i < len) acc_elem(dst + i, 0u, 0u, e);
+}
+
 // Bytes 0..3 of x that differ from the byte before them (prev-byte chain across dwords
 // given by `below`, whose top byte precedes byte 0 of x), as a 4-bit mask.
 __device__ __forceinline__ uint32_t neq_prev_mask4(uint32_t x, uint32_t below) {

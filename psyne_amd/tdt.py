@@ -386,6 +386,25 @@ class TdtCodec:
                                            _ptr(lengths), _ptr(status), self._stream(stream)))
         return lengths, status
 
+    def decode_accumulate_v(self, ptrs, in_lengths, out_ptrs, out_caps, elems=None, elem=0, lengths=None, status=None,
+                            stream=None):
+        """decode_v whose decoded bytes are added to the destinations: message i is summed into
+        out_ptrs[i] as elements of code elems[i] (a uint8 tensor on the GPU of TDT_ELEM_* values of
+        psyne_amd._lib; None: `elem` for every message), TDT_ELEM_STORE decoding it plainly.  A
+        message whose status is not 0 leaves its destination untouched.  Returns (lengths, status)."""
+        import torch
+        n = in_lengths.numel()
+        if elems is not None and (elems.dtype != torch.uint8 or elems.numel() < n):
+            raise ValueError("elems must be a uint8 tensor of one code per message")
+        if lengths is None:
+            lengths = torch.empty(max(n, 1), dtype=torch.int64, device=in_lengths.device)
+        if status is None:
+            status = torch.empty(max(n, 1), dtype=torch.int32, device=in_lengths.device)
+        check(self._lib.tdt_decode_accumulate_v(self._h, _ptr(ptrs), _ptr(in_lengths), n, _ptr(out_ptrs), _ptr(out_caps),
+                                                _ptr(elems) if elems is not None else None, int(elem), _ptr(lengths),
+                                                _ptr(status), self._stream(stream)))
+        return lengths, status
+
     def decoded_sizes_v(self, ptrs, in_lengths, stream=None):
         import torch
         n = in_lengths.numel()
@@ -654,15 +673,33 @@ class TdtCodec:
                                   mapbits=bits if n else None)
         return (*res, bits)
 
-    def decode_tensors(self, blobs, offsets, in_lengths, outs, stream=None):
+    def decode_tensors(self, blobs, offsets, in_lengths, outs, stream=None, accumulate=False):
         """Decode blob i = blobs[offsets[i]:offsets[i]+in_lengths[i]] into the preallocated
-        contiguous GPU tensor outs[i] (capacity: its byte size).  Returns (lengths, status)."""
+        contiguous GPU tensor outs[i] (capacity: its byte size).  Returns (lengths, status).
+
+        accumulate=True adds the decoded tensor to outs[i] instead (outs[i] += decoded, one IEEE add
+        per element, in the decode's own pass): outs must be float32, float16, bfloat16 or float64
+        tensors, each summed in its own type."""
         import torch
         optrs, osizes = self._tensor_table(outs)
         n = len(outs)
-        d = torch.from_numpy(np.concatenate([optrs, osizes])).to(blobs.device)
         ptrs = offsets[:n].to(torch.int64) + blobs.data_ptr()
-        return self.decode_v(ptrs, in_lengths, d[:n], d[n:], stream=stream)
+        if not accumulate:
+            d = torch.from_numpy(np.concatenate([optrs, osizes])).to(blobs.device)
+            return self.decode_v(ptrs, in_lengths, d[:n], d[n:], stream=stream)
+        from ._lib import TDT_ELEM_BF16, TDT_ELEM_F16, TDT_ELEM_F32, TDT_ELEM_F64
+        codes = {torch.float32: TDT_ELEM_F32, torch.float16: TDT_ELEM_F16, torch.bfloat16: TDT_ELEM_BF16,
+                 torch.float64: TDT_ELEM_F64}
+        for t in outs:
+            if t.dtype not in codes:
+                raise ValueError("decode_tensors(accumulate=True) sums float32, float16, bfloat16 and float64 "
+                                 "tensors, not %s" % t.dtype)
+        # one upload: the two int64 tables, then the codes as bytes
+        ec = np.zeros((n + 7) // 8 * 8, np.uint8)
+        ec[:n] = [codes[t.dtype] for t in outs]
+        d = torch.from_numpy(np.concatenate([optrs, osizes, ec.view(np.int64)])).to(blobs.device)
+        return self.decode_accumulate_v(ptrs, in_lengths, d[:n], d[n:2 * n], elems=d[2 * n:].view(torch.uint8),
+                                        stream=stream)
 
     def analyze_batch(self, data, offsets, stream=None):
         """Full-sample histograms (n, ws, 256), entropies (n, ws), mapping (n, ws), status."""

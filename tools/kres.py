@@ -52,6 +52,10 @@ def main(argv):
                 (csrc / "tdt_pack.hip", flags, tmp + "/pack.o")]
         if (csrc / "tdt_rawfb.hip").exists():  # (absent in a parent tree, as the mapped instances below)
             jobs.append((csrc / "tdt_rawfb.hip", flags, tmp + "/rawfb.o"))
+        if (csrc / "tdt_dec_acc.hip").exists():  # (the decode-accumulate instances, with build.py's flags for them)
+            sys.path.insert(0, str(ROOT))
+            from psyne_amd.build import DEC_ACC_FLAGS
+            jobs.append((csrc / "tdt_dec_acc.hip", flags + DEC_ACC_FLAGS, tmp + "/dec_acc.o"))
         jobs += [(csrc / "tdt_enc_ws.hip", flags + ["-DPSY_INST_WS=%d" % ws], tmp + "/ws%d.o" % ws) for ws in ws_list]
         jobs += [(csrc / "tdt_enc_sizes_ws.hip", flags + ["-DPSY_INST_WS=%d" % ws], tmp + "/sws%d.o" % ws) for ws in ws_list]
         if (csrc / "tdt_enc_mapped_ws.hip").exists():  # (absent in a parent tree this file is copied into for an A/B)
