@@ -85,6 +85,11 @@ extern "C" {
                                  call of the batch on this context before capturing it */
 #define TDT_E_ELEMENT 13      /* tdt_decode_accumulate_v: destination not aligned to its element, or the
                                  decoded size is not a whole number of elements */
+#define TDT_E_MISMATCH 14      /* tdt_decode_reduce_v: the peers' blobs of one destination decode to different sizes */
+
+/* tdt_decode_reduce_v */
+#define TDT_REDUCE_MAX_PEERS 8
+#define TDT_REDUCE_SET 1u      /* flags: dst = sum of the peers (default: dst = dst + sum) */
 
 /* Element codes of tdt_decode_accumulate_v */
 #define TDT_ELEM_STORE 0      /* plain decode of this message (as tdt_decode_batch_v) */
@@ -236,6 +241,40 @@ int tdt_decode_batch_v(tdt_ctx *ctx, const uint8_t *const *d_blobs, const uint64
 int tdt_decode_accumulate_v(tdt_ctx *ctx, const uint8_t *const *d_blobs, const uint64_t *d_blob_len, uint32_t n_msgs,
                             uint8_t *const *d_outs, const uint64_t *d_out_cap, const uint8_t *d_elem, int elem,
                             uint64_t *d_out_len, int32_t *d_status, void *hip_stream);
+/* DECODE-REDUCE — the blobs of n_peers peers for each destination, decoded and summed into it in ONE
+ * pass (after an all-gather of compressed gradients, on a parameter-server shard, at the root of a
+ * tree reduction): the destination is read and written once, not once per peer as with n_peers
+ * tdt_decode_accumulate_v calls.
+ *   Layout: destination i's blob from peer k is d_blobs[k * n_msgs + i], d_blob_len[k * n_msgs + i]
+ *     bytes (peer-major: peer k's slice is what tdt_decode_accumulate_v takes).  d_outs, d_out_cap,
+ *     d_elem (NULL: `elem` for every destination), d_out_len (may be NULL) and d_status hold one entry
+ *     per destination; d_peer_status (may be NULL) n_peers * n_msgs entries in the blobs' layout.
+ *   Arithmetic: for element type T, dst = ((dst + b0) + b1) + ... + b(K-1), each + one IEEE add in T
+ *     (round to nearest even, subnormals kept), in ascending peer order: the bits of K successive
+ *     tdt_decode_accumulate_v calls.  With TDT_REDUCE_SET in `flags` the chain starts from peer 0's
+ *     decoded bits as they are and the destination is never read.  Decoded zeros (a stream that ran
+ *     out of pairs, the bytes past the last whole word) take part like any value.
+ *   Element codes: TDT_ELEM_F32, F16, BF16, F64.  TDT_ELEM_STORE or an unknown code is TDT_E_ARG (per
+ *     destination from d_elem, the call's return value from `elem`); n_peers outside
+ *     1..TDT_REDUCE_MAX_PEERS returns TDT_E_ARG.
+ *   All or nothing per destination: every one of its blobs is checked (header, truncation, capacity
+ *     against the decoded size, element alignment and size as in tdt_decode_accumulate_v) before a
+ *     byte of it is written.  d_status[i] is TDT_OK, or the status of the lowest-numbered failing
+ *     peer; TDT_E_MISMATCH when every blob is valid but the decoded sizes differ; TDT_E_UNSUPPORTED
+ *     when a peer's blob has a generic word size (not 1, 2, 4, 8, 16).  A destination whose status is
+ *     not TDT_OK has length 0 and is untouched, byte for byte.  d_peer_status holds each blob's own
+ *     check.  Between the call's two kernels d_status may hold a value outside this list; it is final
+ *     when the stream has run the call.
+ *   The peers of one destination may differ in everything but the decoded size: mapping and stream
+ *     split, word size among 1, 2, 4, 8, 16, UNCP or TDT blob (a sender using the raw fallback writes
+ *     UNCP blobs).  Blobs and destinations at any alignment tdt_decode_accumulate_v accepts.
+ *   Asynchronous on the caller's stream, nothing read back, no workspace: capturable from the first
+ *     call.  One workgroup walks a destination, however long: send tensors of many MiB through
+ *     tdt_decode_accumulate_v, whose tiled pipeline spreads them over the chip. */
+int tdt_decode_reduce_v(tdt_ctx *ctx, const uint8_t *const *d_blobs, const uint64_t *d_blob_len, uint32_t n_msgs,
+                        uint32_t n_peers, uint8_t *const *d_outs, const uint64_t *d_out_cap, const uint8_t *d_elem,
+                        int elem, uint32_t flags, uint64_t *d_out_len, int32_t *d_status, int32_t *d_peer_status,
+                        void *hip_stream);
 /* MIXED WORD SIZES — tdt_encode_batch_v with one record width per message (a mixed-precision
  * gradient list: bf16 / fp16 tensors at width 2 beside fp32 ones at 4 and fp64 / int64 ones at 8).
  * d_word_size[i] (device memory, n_msgs entries) is message i's width; the context's own word_size

@@ -17,6 +17,9 @@ TDT_E_HIP, TDT_E_ARG, TDT_E_CAPTURE = 10, 11, 12
 TDT_E_ELEMENT = 13  # decode-accumulate: destination not aligned to its element, or not a whole number of elements
 # element codes of tdt_decode_accumulate_v (TDT_ELEM_STORE: a plain decode of that message)
 TDT_ELEM_STORE, TDT_ELEM_F32, TDT_ELEM_F16, TDT_ELEM_BF16, TDT_ELEM_F64 = 0, 1, 2, 3, 4
+TDT_E_MISMATCH = 14  # decode-reduce: the peers' blobs of one destination decode to different sizes
+TDT_REDUCE_MAX_PEERS = 8
+TDT_REDUCE_SET = 1  # tdt_decode_reduce_v flag: dst = sum of the peers (default: dst = dst + sum)
 TDT_OPT_LARGE_MIN, TDT_OPT_TILE_CAP, TDT_OPT_NO_SIDE_STREAM = 1, 2, 3
 TDT_OPT_SMALL_ON_CALLER_STREAM, TDT_OPT_NO_TWO_PHASE, TDT_OPT_COPY_THREADS = 4, 5, 6
 TDT_OPT_PACK_SIZES_FIRST = 7
@@ -78,6 +81,8 @@ SIGNATURES = {
                                        _vp, _vp]),
     "tdt_decode_batch_v": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp]),
     "tdt_decode_accumulate_v": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp]),
+    "tdt_decode_reduce_v": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, C.c_int, C.c_uint32, _vp, _vp,
+                                      _vp, _vp]),
     "tdt_decoded_sizes_v": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp]),
     "tdt_encode_slots": (C.c_int, [_vp, _vp, C.c_uint32, _vp, _vp]),
     "tdt_decode_slots": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp]),

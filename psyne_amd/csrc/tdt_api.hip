@@ -27,6 +27,10 @@
 #include "tdt_encode.h"
 #include "tdt_enc_lmap.h"
 #include "tdt_grow.h"
+#if defined(PSY_FAST_BUILD) || (defined(PSY_PROF) && PSY_PROF) || defined(PSY_SINGLE_TU)
+#define PSY_DEC_REDUCE_TU 1  // (diagnostic single-file builds: the decode-reduce kernels are defined here)
+#endif
+#include "tdt_dec_reduce.h"
 #include "tdt_pack.h"
 #include "tdt_plan.h"
 #include "tdt_rawfb.h"
@@ -61,6 +65,9 @@ PSY_ENC_EXT_WS(16)
 // (the decode-accumulate instances: tdt_dec_acc.hip)
 #define PSY_DEC_ACC_EXT(...) extern template __global__ void __VA_ARGS__(psy::DecodeArgs);
 PSY_DEC_ACC_INSTANCES(PSY_DEC_ACC_EXT)
+// (the decode-reduce kernels: tdt_dec_reduce.hip)
+#define PSY_DEC_REDUCE_EXT(...) extern template __global__ void __VA_ARGS__(psy::ReduceArgs);
+PSY_DEC_REDUCE_INSTANCES(PSY_DEC_REDUCE_EXT)
 #endif
 
 // The generic-word-size kernels live in tdt_anyws.hip; the diagnostic single-file builds leave
@@ -3307,6 +3314,42 @@ int tdt_decode_accumulate_v(tdt_ctx *ctx, const uint8_t *const *d_blobs, const u
     return decode_common(ctx, false, a, w, true);
 }
 
+int tdt_decode_reduce_v(tdt_ctx *ctx, const uint8_t *const *d_blobs, const uint64_t *d_blob_len, uint32_t n_msgs,
+                        uint32_t n_peers, uint8_t *const *d_outs, const uint64_t *d_out_cap, const uint8_t *d_elem, int elem,
+                        uint32_t flags, uint64_t *d_out_len, int32_t *d_status, int32_t *d_peer_status, void *stream) {
+    if (!ctx) return set_err(TDT_E_ARG, "null context");
+    if (n_peers < 1 || n_peers > TDT_REDUCE_MAX_PEERS) return set_err(TDT_E_ARG, "n_peers outside 1..TDT_REDUCE_MAX_PEERS");
+    if (!d_elem && (elem < TDT_ELEM_F32 || elem > TDT_ELEM_F64)) return set_err(TDT_E_ARG, "no element type to sum in");
+    if (flags & ~(uint32_t)TDT_REDUCE_SET) return set_err(TDT_E_ARG, "unknown flag");
+    if (n_msgs == 0) return TDT_OK;
+    if (!(d_blobs && d_blob_len && d_outs && d_out_cap && d_status)) return set_err(TDT_E_ARG, "null pointer, size or status array");
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t s = (hipStream_t)stream;
+    psy::ReduceArgs a{};
+    a.blobs = reinterpret_cast<const uint64_t *>(d_blobs);
+    a.blob_len = d_blob_len;
+    a.n_msgs = n_msgs;
+    a.n_peers = n_peers;
+    a.outs = reinterpret_cast<const uint64_t *>(d_outs);
+    a.out_cap = d_out_cap;
+    a.elem_codes = d_elem;
+    a.elem = (uint32_t)elem;
+    a.flags = flags;
+    a.out_len = d_out_len;
+    a.status = d_status;
+    a.peer_status = d_peer_status;
+    // one workgroup per destination, one wave per peer: the smallest team that holds the peers
+    if (n_peers <= 2) hipLaunchKernelGGL(psy::tdt_decode_reduce_kernel<2>, dim3(n_msgs), dim3(128), 0, s, a);
+    else if (n_peers <= 4) hipLaunchKernelGGL(psy::tdt_decode_reduce_kernel<4>, dim3(n_msgs), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(psy::tdt_decode_reduce_kernel<8>, dim3(n_msgs), dim3(512), 0, s, a);
+    HIPCHK(hipGetLastError());
+    // the destinations it left to the serial path (none, with psyne's encoder): 64 statuses per wave and step
+    const uint32_t sg = (n_msgs + 63u) / 64u;
+    hipLaunchKernelGGL(psy::tdt_decode_reduce_serial_kernel, dim3(sg < 1024u ? sg : 1024u), dim3(64), 0, s, a);
+    HIPCHK(hipGetLastError());
+    return TDT_OK;
+}
+
 int tdt_decoded_sizes_v(tdt_ctx *ctx, const uint8_t *const *d_blobs, const uint64_t *d_blob_len, uint32_t n_msgs,
                         uint64_t *d_sizes, int32_t *d_status, void *stream) {
     if (n_msgs && !d_blob_len) return set_err(TDT_E_ARG, "null blob lengths");
@@ -3468,6 +3511,7 @@ const char *tdt_status_string(int status) {
         case TDT_E_BAD_HEADER: return "TDT: word size 0";
         case TDT_E_CONFIG: return "TDT: invalid configuration";
         case TDT_E_HIP: return "TDT: HIP runtime error";
+        case TDT_E_MISMATCH: return "TDT: the peers' blobs of one destination decode to different sizes";
         case TDT_E_CAPTURE: return "TDT: workspace growth needed under stream capture";
         case TDT_E_ARG: return "TDT: invalid argument";
         case TDT_E_ELEMENT: return "TDT: destination or decoded size does not hold whole aligned elements";

@@ -1,0 +1,370 @@
+// tdt_dec_reduce.h — decode-reduce (tdt_decode_reduce_v): the blobs of up to 8 peers for one
+// destination are decoded and summed into it in one pass, dst = ((dst + b0) + b1) + ... in the
+// destination's element type (or, with TDT_REDUCE_SET, dst = (b0 + b1) + ...), the bits of that
+// many tdt_decode_accumulate_v calls in peer order.
+//
+// Work split: one workgroup per destination, one 64-lane wave per peer; NW, the
+// workgroup's wave count, is the smallest of 2, 4, 8 that holds the peers.  A wave without a peer
+// stages nothing but keeps the barrier schedule and takes its share of the sums.
+//
+//   header   wave k parses peer k's blob (parse_fast; blob_check for every other shape), checks it
+//            against the destination (capacity, element alignment and size: acc_status) and
+//            publishes (kind, status, decoded size) to LDS.  One workgroup barrier; every wave then
+//            reads all records and takes the same decision: refused (nothing is written), serial,
+//            or fused.
+//   fused    every peer is UNCP or a fast-path TDT blob.  The output is walked in the decoder's
+//            windows of kRedWR rounds of 64 16-byte groups.  Wave k runs decode_fast on its blob with
+//            a SINK: where a round's 16 recombined bytes per lane would be stored, they go to the
+//            wave's LDS slice (1 KiB per round), bytes past the blob's last whole word as zeros.  An
+//            UNCP wave fills its slice from blob + 4 (aligned dwords, funnel-shifted).  At the end of
+//            a window (RedSink::window): barrier A, every lane of the workgroup takes groups of the
+//            window, chains acc4 over the staged groups in peer order onto the destination group
+//            (loaded before the window's decode, so its trip to memory lies under it) and stores it
+//            once; barrier B frees the slices.  Destinations off 16 bytes and the last partial group
+//            take 2-byte loads and stores around the same chain.
+//   serial   some peer is valid but no fast-path blob (three or more referenced streams, odd
+//            segments, more than 16 stored streams): the workgroup marks the destination and leaves;
+//            a second launch on the same stream (tdt_decode_reduce_serial_kernel, below) runs the
+//            one-wave accumulate decode (decode_one, ACC) over its peers in order.  Correct and slow;
+//            psyne's encoder writes fast-path blobs.
+//
+// BARRIERS.  Every wave of a workgroup meets every workgroup barrier the same number of times:
+//   1. the header barrier is unconditional (tdt_decode_reduce_kernel, "header barrier");
+//   2. the refused / serial / fused decision is computed by every wave from the same LDS records
+//      with the same code (red_verdict) and held in scalar registers; the refused and the serial
+//      destination's workgroup returns there, all its waves at once;
+//   3. the fused path's barriers are all in RedSink::window, which every wave calls exactly once per
+//      window: from decode_fast's window loop (trip count: g_hi = the destination's common group
+//      count `gc`, never a peer's header, stream lengths or pair counts; a wave whose streams have
+//      ended keeps walking windows and stages zeros), from the UNCP loop and from the idle loop,
+//      both `for (win = 0; win < nwin; ++win)` with nwin computed from gc alone.  The three callers
+//      are selected by wave-uniform scalars (the wave index and the record's kind, through
+//      readfirstlane), and none of them leaves its loop early.
+//
+// A long destination is walked by its one workgroup: there is no tiled form, and a tensor of many
+// MiB runs on one CU.  Send such tensors through tdt_decode_accumulate_v, whose
+// tiled pipeline spreads them over the chip.
+#pragma once
+#include "tdt_decode.h"
+
+namespace psy {
+
+constexpr int kRedMaxPeers = 8;       // TDT_REDUCE_MAX_PEERS
+constexpr uint32_t kRedSet = 1u;      // TDT_REDUCE_SET
+constexpr uint32_t ST_MISMATCH = 14;  // TDT_E_MISMATCH
+// d_status between the two launches: a valid destination left to the serial kernel.  Never reported.
+constexpr uint32_t ST_RED_SERIAL = 0x101;
+constexpr int kRedWR = kDecWR;        // rounds per window: the decoder's own
+constexpr uint32_t kRedWinGroups = 64u * kRedWR;
+constexpr uint32_t kRedSlice = 1024u * kRedWR;  // a peer's staged window
+
+struct ReduceArgs {
+    const uint64_t *blobs;     // [n_peers][n_msgs] blob addresses (peer-major)
+    const uint64_t *blob_len;  // [n_peers][n_msgs]
+    uint32_t n_msgs, n_peers;
+    const uint64_t *outs;  // [n_msgs] destination addresses
+    const uint64_t *out_cap;
+    const uint8_t *elem_codes;  // [n_msgs], or null: `elem` for every destination
+    uint32_t elem, flags;
+    uint64_t *out_len;
+    int32_t *status;
+    int32_t *peer_status;  // [n_peers][n_msgs] or null
+};
+
+// LDS of a workgroup of NW waves: each wave's decode state (the decoder's own layout), the staged
+// windows and the peers' records.
+template <int NW>
+struct RedLayout {
+    static constexpr int DEC = (DecLayoutT<kRedWR>::BYTES + 15) / 16 * 16;
+    static constexpr int OFF_STAGE = NW * DEC;
+    static constexpr int OFF_REC = OFF_STAGE + NW * (int)kRedSlice;
+    static constexpr int BYTES = OFF_REC + 16 * kRedMaxPeers;  // a record: kind, status, size (u64)
+    static_assert(BYTES <= 80 * 1024, "two workgroups per CU at 8 waves");
+};
+
+// 16 bytes of an element-aligned destination that is not 16-byte aligned, or the partial last
+// group: dwords when 4-aligned and whole, else 2-byte accesses (every element size is a multiple of
+// 2 and `valid` a whole number of elements); bytes at and past `valid` read as zero and stay untouched
+__device__ __forceinline__ uint4 red_ld16(const uint8_t *p, uint32_t valid) {
+    if (valid >= 16u && ((uintptr_t)p & 3) == 0) {
+        const uint32_t *q = reinterpret_cast<const uint32_t *>(p);
+        return make_uint4(q[0], q[1], q[2], q[3]);
+    }
+    uint32_t w[4] = {0, 0, 0, 0};
+    const uint16_t *q = reinterpret_cast<const uint16_t *>(p);
+#pragma unroll
+    for (uint32_t i = 0; i < 8; ++i)
+        if (2u * i < valid) w[i >> 1] |= (uint32_t)q[i] << (16u * (i & 1u));
+    return make_uint4(w[0], w[1], w[2], w[3]);
+}
+__device__ __forceinline__ void red_st16(uint8_t *p, uint4 v, uint32_t valid) {
+    if (valid >= 16u && ((uintptr_t)p & 3) == 0) {
+        uint32_t *q = reinterpret_cast<uint32_t *>(p);
+        q[0] = v.x, q[1] = v.y, q[2] = v.z, q[3] = v.w;
+        return;
+    }
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+    uint16_t *q = reinterpret_cast<uint16_t *>(p);
+#pragma unroll
+    for (uint32_t i = 0; i < 8; ++i)
+        if (2u * i < valid) q[i] = (uint16_t)(w[i >> 1] >> (16u * (i & 1u)));
+}
+
+// decode_fast's sink of the fused path (and the UNCP and idle waves' window step).  All fields but
+// `tid` and `dpre` are uniform over the workgroup.
+template <int NW>
+struct RedSink {
+    static constexpr bool on = true;
+    static constexpr uint32_t T = 64u * NW;                       // lanes of the workgroup
+    static constexpr int NPF = (int)((kRedWinGroups + T - 1) / T);  // groups per lane and window
+    uint8_t *stage;  // the workgroup's staged windows; peer k's slice at k * kRedSlice
+    uint8_t *mine;   // this wave's slice
+    uint8_t *dst;
+    uint64_t osize;
+    uint32_t gc;  // the destination's 16-byte groups (the last may be partial)
+    uint32_t n_peers, elem, tid;
+    bool set, dal16;
+    uint4 dpre[NPF];  // the destination groups of the coming window (whole aligned groups, not under SET)
+
+    // group j of the window from this wave's blob (lane l of round rl: j = 64 rl + l)
+    __device__ __forceinline__ void put(uint32_t j, uint4 v) { *reinterpret_cast<uint4 *>(mine + 16u * j) = v; }
+
+    __device__ __forceinline__ bool whole(uint32_t g) const { return dal16 && 16ull * g + 16ull <= osize; }
+
+    // the destination loads of window `win`, issued before its decode
+    __device__ __forceinline__ void prefetch(uint32_t win) {
+        if (set) return;
+#pragma unroll
+        for (int q = 0; q < NPF; ++q) {
+            const uint32_t j = tid + (uint32_t)q * T, g = win * kRedWinGroups + j;
+            if (j < kRedWinGroups && g < gc && whole(g)) dpre[q] = acc_ld16(dst + 16ull * g);
+        }
+    }
+
+    // the end of window `win`: every wave of the workgroup calls this once per window
+    __device__ __forceinline__ void window(uint32_t win) {
+        __syncthreads();  // A: every peer's slice of this window is staged
+#pragma unroll
+        for (int q = 0; q < NPF; ++q) {
+            const uint32_t j = tid + (uint32_t)q * T, g = win * kRedWinGroups + j;
+            if (j < kRedWinGroups && g < gc) {
+                uint8_t *p = dst + 16ull * g;
+                const bool wh = whole(g);
+                const uint64_t left = osize - 16ull * g;
+                const uint32_t valid = left >= 16ull ? 16u : (uint32_t)left;
+                const uint4 *sv = reinterpret_cast<const uint4 *>(stage + 16u * j);
+                uint4 d = sv[0];
+                if (!set) d = acc4(wh ? dpre[q] : red_ld16(p, valid), d, elem);
+                for (uint32_t k = 1u; k < n_peers; ++k) d = acc4(d, sv[k * (kRedSlice / 16u)], elem);
+                if (wh) st16_nt(p, d);
+                else red_st16(p, d, valid);
+            }
+        }
+        __syncthreads();  // B: the slices may be written again
+        prefetch(win + 1u);
+    }
+};
+
+// What every wave concludes from the peers' records (the same code over the same LDS words)
+struct RedVerdict {
+    uint32_t st;  // the destination's status
+    bool fused;   // every peer is UNCP or a fast-path blob
+    uint64_t osize;
+};
+__device__ __forceinline__ RedVerdict red_verdict(const uint32_t *rec, uint32_t n_peers) {
+    RedVerdict v{ST_OK, true, 0};
+    v.osize = *reinterpret_cast<const uint64_t *>(rec + 2);
+    bool differ = false;
+    for (uint32_t k = 0; k < n_peers; ++k) {
+        const uint32_t kind = rec[4 * k], st = rec[4 * k + 1];
+        if (v.st == ST_OK && st != ST_OK) v.st = st;  // the lowest-numbered failing peer
+        if (kind == 0u) v.fused = false;
+        if (*reinterpret_cast<const uint64_t *>(rec + 4 * k + 2) != v.osize) differ = true;
+    }
+    if (v.st == ST_OK && differ) v.st = ST_MISMATCH;
+    // (the same in every lane and wave; kept in scalar registers, so the branches on them are scalar)
+    v.st = (uint32_t)__builtin_amdgcn_readfirstlane((int)v.st);
+    v.fused = __builtin_amdgcn_readfirstlane((int)v.fused) != 0;
+    v.osize = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v.osize) |
+              (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v.osize >> 32)) << 32;
+    return v;
+}
+
+template <int NW>
+__global__ __launch_bounds__(64 * NW) void tdt_decode_reduce_kernel(ReduceArgs a) {
+    using Lay = RedLayout<NW>;
+    using Dec = DecLayoutT<kRedWR>;
+    __shared__ __attribute__((aligned(16))) uint8_t smem[Lay::BYTES];
+    const uint32_t msg = blockIdx.x;
+    const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t lane = (uint32_t)lane_id();
+    const uint32_t n_peers = a.n_peers;
+    uint8_t *dec = smem + w * (uint32_t)Lay::DEC;
+    uint32_t *rec = reinterpret_cast<uint32_t *>(smem + Lay::OFF_REC);
+    const bool set = (a.flags & kRedSet) != 0u;
+    const uint32_t elem =
+        (uint32_t)__builtin_amdgcn_readfirstlane((int)(a.elem_codes ? (uint32_t)a.elem_codes[msg] : a.elem));
+    uint8_t *dst = reinterpret_cast<uint8_t *>(a.outs[msg]);
+    const uint64_t cap = a.out_cap[msg];
+
+    // ------------------------------------------------ header: wave k checks peer k's blob
+    const uint8_t *blob = nullptr, *blim = nullptr;
+    uint64_t len = 0;
+    FastHdr H{};
+    if (w < n_peers) {
+        const uint64_t bi = (uint64_t)w * a.n_msgs + msg;
+        blob = reinterpret_cast<const uint8_t *>(a.blobs[bi]);
+        len = a.blob_len[bi];
+        blim = blob + len;
+        uint8_t *hdrc = dec + Dec::OFF_HDR;
+        const uint32_t hcl = len < (uint64_t)kHdrCache ? (uint32_t)len : (uint32_t)kHdrCache;
+        {
+            static_assert(kHdrCache == 256, "one dword per lane");
+            const uint32_t o = lane * 4u;
+            uint32_t v = 0;
+            if (((uintptr_t)blob & 3) == 0 && o + 4u <= hcl) {
+                v = *reinterpret_cast<const uint32_t *>(blob + o);
+            } else {
+#pragma unroll
+                for (uint32_t i = 0; i < 4; ++i)
+                    if (o + i < hcl) v |= (uint32_t)blob[o + i] << (8u * i);
+            }
+            reinterpret_cast<uint32_t *>(hdrc)[lane] = v;
+        }
+        team_sync<1>();
+        H = parse_fast(blob, len, hdrc, hcl);
+        uint32_t st = ST_OK;
+        uint64_t osize = H.osize;
+        if (H.kind == 0u) {
+            // every other shape, errors included: the reference's checks (every lane the same words)
+            auto rd32 = [&](uint64_t off) -> uint32_t {
+                if (off + 4 <= hcl) return ld_u32_bytes(hdrc + off);
+                return ld_u32_bytes(blob + off);
+            };
+            uint32_t uncp;
+            st = blob_check(rd32, len, uncp, osize);
+        }
+        st = (uint32_t)__builtin_amdgcn_readfirstlane((int)st);
+        if (st == ST_DEFER) {  // a generic word size: no accumulate form
+            st = elem > kElemMax || elem == kElemStore ? (uint32_t)ST_ARG : (uint32_t)ST_UNSUPPORTED;
+        } else {
+            if (st == ST_OK && osize > cap) st = ST_CAPACITY;
+            if (st == ST_OK && (osize >> 35) != 0) st = ST_UNSUPPORTED;  // (group indices are 32 bits wide)
+            if (st == ST_OK && elem == kElemStore) st = ST_ARG;
+            st = acc_status(st, elem, dst, osize);
+        }
+        if (st != ST_OK) osize = 0;
+        if (lane == 0) {
+            rec[4 * w] = H.kind;
+            rec[4 * w + 1] = st;
+            *reinterpret_cast<uint64_t *>(rec + 4 * w + 2) = osize;
+            if (a.peer_status) a.peer_status[bi] = (int32_t)st;
+        }
+    }
+    __syncthreads();  // header barrier: every wave, once
+    const RedVerdict V = red_verdict(rec, n_peers);
+    if (w == 0 && lane == 0) {
+        // (a valid destination with a peer off the fast path: left to the serial kernel that follows)
+        a.status[msg] = (int32_t)(V.st == ST_OK && !V.fused ? ST_RED_SERIAL : V.st);
+        if (a.out_len) a.out_len[msg] = V.st == ST_OK ? V.osize : 0;
+    }
+    if (V.st != ST_OK || !V.fused) return;  // refused: nothing of the destination is read or written
+
+    // ------------------------------------------------ fused
+    const uint64_t osize = V.osize;
+    const uint32_t gc = (uint32_t)((osize + 15) / 16);
+    const uint32_t nwin = (gc + kRedWinGroups - 1) / kRedWinGroups;
+    RedSink<NW> S;
+    S.stage = smem + Lay::OFF_STAGE;
+    S.mine = S.stage + w * kRedSlice;
+    S.dst = dst;
+    S.osize = osize;
+    S.gc = gc;
+    S.n_peers = n_peers;
+    S.elem = elem;
+    S.tid = threadIdx.x;
+    S.set = set;
+    S.dal16 = ((uintptr_t)dst & 15) == 0;
+#pragma unroll
+    for (int q = 0; q < RedSink<NW>::NPF; ++q) S.dpre[q] = make_uint4(0, 0, 0, 0);
+    S.prefetch(0);
+    const uint32_t kind = (uint32_t)__builtin_amdgcn_readfirstlane((int)(w < n_peers ? H.kind : 0u));
+    if (kind == 2u) {
+        // window loop inside: gwin = 0, 64 WR, ... < gc, S.window(win) at the end of each
+        const uint64_t wbytes = (uint64_t)(H.orig / H.ws) * H.ws;
+        decode_fast<kRedWR, false, RedSink<NW>>(H, dec, blob, blim, nullptr, gc, wbytes, 0, gc, nullptr, nullptr, nullptr,
+                                                0u, 0u, &S);
+    } else if (kind == 1u) {
+        for (uint32_t win = 0; win < nwin; ++win) {
+#pragma unroll
+            for (uint32_t rl = 0; rl < (uint32_t)kRedWR; ++rl) {
+                const uint32_t g = win * kRedWinGroups + rl * 64u + lane;
+                uint4 v = make_uint4(0, 0, 0, 0);
+                if (g < gc) {
+                    const uint64_t left = osize - 16ull * g;
+                    v = ld16_span(blob + 4 + 16ull * g, left >= 16 ? 16 : (int)left, blim);
+                }
+                S.put(rl * 64u + lane, v);
+            }
+            S.window(win);
+        }
+    } else {
+        for (uint32_t win = 0; win < nwin; ++win) S.window(win);  // a wave without a peer
+    }
+}
+
+// The serial path: the destinations the kernel above marked ST_RED_SERIAL (every blob valid, the
+// sizes equal, some peer no fast-path blob).  One wave per block; a wave reads 64 statuses at a
+// time, and for each marked destination runs the one-wave accumulate decode (decode_one, ACC) over
+// the peers in order, adding straight into the destination; under TDT_REDUCE_SET peer 0 is stored.
+// Then the status becomes TDT_OK.  A launch of its own, so that the fused kernel keeps its registers:
+// with decode_one inlined beside decode_fast hipcc 7.2 either crashed (SimplifyCFG) or, behind a
+// call, gave the fused path the callee's 184 VGPRs and a stack.
+__global__ void tdt_decode_reduce_serial_kernel(ReduceArgs a);
+#ifdef PSY_DEC_REDUCE_TU
+// (behind a call: inlined into the loop below, hipcc 7.2's SimplifyCFG crashes on this instance)
+__device__ __noinline__ void red_decode_one(const DecodeArgs &d, uint8_t *smem) {
+    decode_one<0, kRedWR, true, true>(d, smem, 0);
+}
+__global__ __launch_bounds__(64) void tdt_decode_reduce_serial_kernel(ReduceArgs a) {
+    __shared__ __attribute__((aligned(16))) uint8_t smem[DecLayoutT<kRedWR>::BYTES];
+    __shared__ uint64_t tab[4];  // the one-message tables: blob, length, slot begin, slot end
+    const uint32_t lane = (uint32_t)lane_id();
+    const bool set = (a.flags & kRedSet) != 0u;
+    DecodeArgs d{};
+    d.n_msgs = 1;
+    d.in_off = tab;
+    d.in_len = tab + 1;
+    d.slot_off = tab + 2;
+    for (uint32_t base = blockIdx.x * 64u; base < a.n_msgs; base += gridDim.x * 64u) {
+        const uint32_t i = base + lane;
+        uint64_t pend = __ballot(i < a.n_msgs && a.status[i] == (int32_t)ST_RED_SERIAL);
+        while (pend) {
+            const uint32_t msg = base + (uint32_t)__builtin_ctzll(pend);
+            pend &= pend - 1;
+            const uint32_t elem =
+                (uint32_t)__builtin_amdgcn_readfirstlane((int)(a.elem_codes ? (uint32_t)a.elem_codes[msg] : a.elem));
+            for (uint32_t k = 0; k < a.n_peers; ++k) {
+                team_sync<1>();  // (the previous decode is done with the LDS)
+                if (lane == 0) {
+                    tab[0] = a.blobs[(uint64_t)k * a.n_msgs + msg];
+                    tab[1] = a.blob_len[(uint64_t)k * a.n_msgs + msg];
+                    tab[2] = a.outs[msg];
+                    tab[3] = a.outs[msg] + a.out_cap[msg];
+                }
+                team_sync<1>();
+                d.elem = set && k == 0 ? kElemStore : elem;
+                red_decode_one(d, smem);
+            }
+            if (lane == 0) a.status[msg] = (int32_t)ST_OK;
+        }
+    }
+}
+#endif
+
+#define PSY_DEC_REDUCE_INSTANCES(X)           \
+    X(psy::tdt_decode_reduce_kernel<2>)       \
+    X(psy::tdt_decode_reduce_kernel<4>)       \
+    X(psy::tdt_decode_reduce_kernel<8>)
+
+}  // namespace psy

@@ -324,11 +324,20 @@ __device__ __forceinline__ uint32_t gload_blk(const uint32_t *p) {
 // added to the destination.  In a whole aligned round the lane's 16 destination bytes are loaded
 // when the round starts, so the trip to memory lies under the round's LDS work, and are consumed
 // at the store; every other group goes through acc16_any.
-template <int WR_ = kDecWR, bool ACC = false>
+//
+// SINK (decode-reduce, tdt_dec_reduce.h): a type with `on` set takes each round's groups instead of
+// the destination — sink->put(group of the window, its 16 bytes), bytes at and past wbytes as zeros —
+// and is told when a window is complete (sink->window(win)); dst is then unused and g_hi may lie
+// past ngroups (those groups are zeros).  NoSink: the stores below, compiled as they were.
+struct NoSink {
+    static constexpr bool on = false;
+};
+template <int WR_ = kDecWR, bool ACC = false, class SINK = NoSink>
 __device__ __forceinline__ void decode_fast(const FastHdr &H, uint8_t *smem, const uint8_t *blob, const uint8_t *blim,
                                             uint8_t *dst, uint32_t ngroups, uint64_t wbytes, uint32_t g_lo = 0,
                                             uint32_t g_hi = 0, const uint32_t *b0 = nullptr, const uint32_t *s0 = nullptr,
-                                            const uint8_t *bc = nullptr, uint32_t bcl = 0, uint32_t elem = 0) {
+                                            const uint8_t *bc = nullptr, uint32_t bcl = 0, uint32_t elem = 0,
+                                            SINK *sink = nullptr) {
     using Lay = DecLayoutT<WR_>;
     constexpr uint32_t WR = WR_;
     const uint32_t lane = (uint32_t)lane_id();
@@ -682,7 +691,20 @@ __device__ __forceinline__ void decode_fast(const FastHdr &H, uint8_t *smem, con
                                perm(S[1], S[0], OA[3]) | perm(S[3], S[2], OB[3]));
             }
             const uint32_t g = g0 + lane;
-            if (dal16 && g0 + 64u <= wg16) {
+            if constexpr (SINK::on) {
+                if (g0 + 64u > wg16) {  // (uniform) the round holds the end of the whole words: zeros from there
+                    const uint64_t gb = 16ull * g;
+                    const uint32_t keep = gb >= wbytes ? 0u : (wbytes - gb >= 16ull ? 16u : (uint32_t)(wbytes - gb));
+                    uint32_t ow[4] = {o.x, o.y, o.z, o.w};
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const uint32_t kq = keep <= 4u * q ? 0u : (keep - 4u * q >= 4u ? 4u : keep - 4u * q);
+                        ow[q] &= kq >= 4u ? 0xffffffffu : ((1u << (8u * kq)) - 1u);
+                    }
+                    o = make_uint4(ow[0], ow[1], ow[2], ow[3]);
+                }
+                sink->put(rl * 64u + lane, o);
+            } else if (dal16 && g0 + 64u <= wg16) {
                 // a whole aligned round (uniform): one 16-byte store per lane, no per-lane tests
                 if constexpr (ACC) {
                     if (elem != kElemStore) o = acc4(dcur, o, elem);
@@ -702,6 +724,7 @@ __device__ __forceinline__ void decode_fast(const FastHdr &H, uint8_t *smem, con
             *reinterpret_cast<uint4 *>(planes + 16u * lane) = make_uint4(0, 0, 0, 0);
         }
         PSY_PROF_MARK(10);
+        if constexpr (SINK::on) sink->window(win);  // (once per window, whatever the blob held)
     }
 }
 

@@ -405,6 +405,36 @@ class TdtCodec:
                                                 _ptr(status), self._stream(stream)))
         return lengths, status
 
+    def decode_reduce_v(self, ptrs, in_lengths, n_peers, out_ptrs, out_caps, elems=None, elem=1, set=False, lengths=None,
+                        status=None, peer_status=None, stream=None):
+        """The blobs of n_peers peers summed into each destination in one pass: destination i's blob
+        from peer k is in_lengths[k * n + i] bytes at address ptrs[k * n + i] (n = out_ptrs.numel();
+        peer k's slice is what decode_accumulate_v takes), added in ascending peer order as elements
+        of code elems[i] (None: `elem`, TDT_ELEM_F32 by default) — the bits of n_peers
+        decode_accumulate_v calls.  set=True writes the peers' sum alone and never reads the
+        destination.  Every blob of a destination is checked before a byte of it is written: one
+        whose status is not 0 is untouched.  peer_status (an int32 tensor of n_peers * n entries)
+        receives each blob's own check.  Returns (lengths, status)."""
+        import torch
+        from ._lib import TDT_REDUCE_SET
+        n = out_ptrs.numel()
+        if in_lengths.numel() < int(n_peers) * n or ptrs.numel() < int(n_peers) * n:
+            raise ValueError("ptrs and in_lengths hold n_peers entries per destination")
+        if elems is not None and (elems.dtype != torch.uint8 or elems.numel() < n):
+            raise ValueError("elems must be a uint8 tensor of one code per destination")
+        if peer_status is not None and (peer_status.dtype != torch.int32 or peer_status.numel() < int(n_peers) * n):
+            raise ValueError("peer_status must be an int32 tensor of n_peers entries per destination")
+        if lengths is None:
+            lengths = torch.empty(max(n, 1), dtype=torch.int64, device=in_lengths.device)
+        if status is None:
+            status = torch.empty(max(n, 1), dtype=torch.int32, device=in_lengths.device)
+        check(self._lib.tdt_decode_reduce_v(self._h, _ptr(ptrs), _ptr(in_lengths), n, int(n_peers), _ptr(out_ptrs),
+                                            _ptr(out_caps), _ptr(elems) if elems is not None else None, int(elem),
+                                            TDT_REDUCE_SET if set else 0, _ptr(lengths), _ptr(status),
+                                            _ptr(peer_status) if peer_status is not None else None,
+                                            self._stream(stream)))
+        return lengths, status
+
     def decoded_sizes_v(self, ptrs, in_lengths, stream=None):
         import torch
         n = in_lengths.numel()
@@ -700,6 +730,30 @@ class TdtCodec:
         d = torch.from_numpy(np.concatenate([optrs, osizes, ec.view(np.int64)])).to(blobs.device)
         return self.decode_accumulate_v(ptrs, in_lengths, d[:n], d[n:2 * n], elems=d[2 * n:].view(torch.uint8),
                                         stream=stream)
+
+    def decode_reduce_tensors(self, peers, outs, set=False, stream=None):
+        """outs[i] += the sum over peers of their tensor i (set=True: outs[i] = that sum), in one pass
+        over each destination (decode_reduce_v).  peers: one (blobs, offsets, in_lengths) triple per
+        peer, each as decode_tensors takes it; outs: float32, float16, bfloat16 or float64 tensors,
+        each summed in its own type, in ascending peer order.  Returns (lengths, status)."""
+        import torch
+        from ._lib import TDT_ELEM_BF16, TDT_ELEM_F16, TDT_ELEM_F32, TDT_ELEM_F64
+        codes = {torch.float32: TDT_ELEM_F32, torch.float16: TDT_ELEM_F16, torch.bfloat16: TDT_ELEM_BF16,
+                 torch.float64: TDT_ELEM_F64}
+        for t in outs:
+            if t.dtype not in codes:
+                raise ValueError("decode_reduce_tensors sums float32, float16, bfloat16 and float64 tensors, not %s"
+                                 % t.dtype)
+        optrs, osizes = self._tensor_table(outs)
+        n = len(outs)
+        ec = np.zeros((n + 7) // 8 * 8, np.uint8)
+        ec[:n] = [codes[t.dtype] for t in outs]
+        dev = peers[0][0].device
+        d = torch.from_numpy(np.concatenate([optrs, osizes, ec.view(np.int64)])).to(dev)
+        ptrs = torch.cat([off[:n].to(torch.int64) + blobs.data_ptr() for blobs, off, _ in peers])
+        lens = torch.cat([ln[:n].to(torch.int64) for _, _, ln in peers])
+        return self.decode_reduce_v(ptrs, lens, len(peers), d[:n], d[n:2 * n], elems=d[2 * n:].view(torch.uint8),
+                                    set=set, stream=stream)
 
     def analyze_batch(self, data, offsets, stream=None):
         """Full-sample histograms (n, ws, 256), entropies (n, ws), mapping (n, ws), status."""

@@ -56,6 +56,9 @@ def main(argv):
             sys.path.insert(0, str(ROOT))
             from psyne_amd.build import DEC_ACC_FLAGS
             jobs.append((csrc / "tdt_dec_acc.hip", flags + DEC_ACC_FLAGS, tmp + "/dec_acc.o"))
+        if (csrc / "tdt_dec_reduce.hip").exists():  # (the decode-reduce kernels, same flags)
+            from psyne_amd.build import DEC_ACC_FLAGS
+            jobs.append((csrc / "tdt_dec_reduce.hip", flags + DEC_ACC_FLAGS, tmp + "/dec_reduce.o"))
         jobs += [(csrc / "tdt_enc_ws.hip", flags + ["-DPSY_INST_WS=%d" % ws], tmp + "/ws%d.o" % ws) for ws in ws_list]
         jobs += [(csrc / "tdt_enc_sizes_ws.hip", flags + ["-DPSY_INST_WS=%d" % ws], tmp + "/sws%d.o" % ws) for ws in ws_list]
         if (csrc / "tdt_enc_mapped_ws.hip").exists():  # (absent in a parent tree this file is copied into for an A/B)
@@ -66,7 +69,7 @@ def main(argv):
     names = subprocess.run(["c++filt"], input="\n".join(r["name"] for r in rows), capture_output=True,
                            text=True).stdout.splitlines()
     for r, name in zip(rows, names):
-        name = name.replace("void ", "").replace("psy::", "").replace("(EncodeArgs)", "").replace("(DecodeArgs)", "")
+        name = name.replace("void ", "").replace("psy::", "").replace("(EncodeArgs)", "").replace("(DecodeArgs)", "").replace("(ReduceArgs)", "")
         if grep and grep not in name:
             continue
         print("%-64s vgpr %3s vspill %3s sspill %3s scratch %4s occ %s lds %s" % (
