@@ -90,6 +90,7 @@ extern "C" {
 /* tdt_decode_reduce_v */
 #define TDT_REDUCE_MAX_PEERS 8
 #define TDT_REDUCE_SET 1u      /* flags: dst = sum of the peers (default: dst = dst + sum) */
+#define TDT_REDUCE_TILE_BYTES 33792u /* output bytes per tile of a long destination: 11 decoder windows of 3,072 */
 
 /* Element codes of tdt_decode_accumulate_v */
 #define TDT_ELEM_STORE 0      /* plain decode of this message (as tdt_decode_batch_v) */
@@ -263,14 +264,22 @@ int tdt_decode_accumulate_v(tdt_ctx *ctx, const uint8_t *const *d_blobs, const u
  *     peer; TDT_E_MISMATCH when every blob is valid but the decoded sizes differ; TDT_E_UNSUPPORTED
  *     when a peer's blob has a generic word size (not 1, 2, 4, 8, 16).  A destination whose status is
  *     not TDT_OK has length 0 and is untouched, byte for byte.  d_peer_status holds each blob's own
- *     check.  Between the call's two kernels d_status may hold a value outside this list; it is final
+ *     check.  Between the call's kernels d_status may hold a value outside this list; it is final
  *     when the stream has run the call.
  *   The peers of one destination may differ in everything but the decoded size: mapping and stream
  *     split, word size among 1, 2, 4, 8, 16, UNCP or TDT blob (a sender using the raw fallback writes
  *     UNCP blobs).  Blobs and destinations at any alignment tdt_decode_accumulate_v accepts.
- *   Asynchronous on the caller's stream, nothing read back, no workspace: capturable from the first
- *     call.  One workgroup walks a destination, however long: send tensors of many MiB through
- *     tdt_decode_accumulate_v, whose tiled pipeline spreads them over the chip. */
+ *   Long destinations: one whose decoded size is above the tiled-path threshold (max(TDT_OPT_LARGE_MIN,
+ *     1/4096 of the call's decoded bytes), taken on the device) is summed as tiles of
+ *     TDT_REDUCE_TILE_BYTES of output over the whole device, one workgroup per tile and one wave per
+ *     peer; every other one by one workgroup.  Bits, statuses and the all-or-nothing rule are the same on
+ *     both routes (TDT_OPT_REDUCE_TILED, below).  A long destination with a valid peer off the fast path
+ *     (three or more referenced streams, odd segments, more than 16 stored streams) and every refused
+ *     one stay on the one-workgroup route.
+ *   Asynchronous on the caller's stream, nothing read back: capturable from the first call.  The tiled
+ *     route keeps a workspace in the context that grows on eager calls only; under stream capture a
+ *     destination that finds it cold or its budget spent is walked by its one workgroup, correct and
+ *     slow, and the call never fails for it. */
 int tdt_decode_reduce_v(tdt_ctx *ctx, const uint8_t *const *d_blobs, const uint64_t *d_blob_len, uint32_t n_msgs,
                         uint32_t n_peers, uint8_t *const *d_outs, const uint64_t *d_out_cap, const uint8_t *d_elem,
                         int elem, uint32_t flags, uint64_t *d_out_len, int32_t *d_status, int32_t *d_peer_status,
@@ -566,6 +575,11 @@ int tdt_ctx_error_flags(tdt_ctx *ctx, void *hip_stream, uint32_t *flags);
  *     one-message call stores the raw bytes on the host, with no second launch.
  *   TDT_STAT_HOST_RAW_FALLBACKS counts the messages of the most recent host encode call. */
 #define TDT_OPT_HOST_RAW_FALLBACK 11
+/* TILED DECODE-REDUCE.  Default 1 (PSYNE_TDT_REDUCE_TILED): tdt_decode_reduce_v sums destinations above the
+ * tiled-path threshold as tiles over the whole device.  0: the call launches exactly its two one-workgroup
+ * kernels, whatever the sizes — the A/B switch; the bits are the same.  TDT_OPT_TILE_CAP lowers the tile
+ * budget of a call: a destination that finds no tiles left stays on its one workgroup. */
+#define TDT_OPT_REDUCE_TILED 12
 int tdt_ctx_set_option(tdt_ctx *ctx, int option, uint64_t value);
 
 /* Read-only counters of the context (tests and tools: which path a call took).  The claims are those
@@ -589,6 +603,10 @@ int tdt_ctx_set_option(tdt_ctx *ctx, int option, uint64_t value);
 #define TDT_STAT_HOST_RAW_FALLBACKS 8     /* messages the most recent host encode call of the context (tdt_encode_host
                                              / _v) stored raw by TDT_OPT_HOST_RAW_FALLBACK's rule.  Host calls block, so
                                              the value is final when the call returns; 0 after a call with the option off */
+#define TDT_STAT_REDUCE_LARGE 9           /* destinations the most recent tdt_decode_reduce_v call whose snapshot has
+                                             landed summed as tiles (0 after a call with TDT_OPT_REDUCE_TILED 0 or
+                                             one that found the workspace cold under capture) */
+#define TDT_STAT_REDUCE_TILES 10          /* the tiles of those destinations */
 int tdt_ctx_get_stat(tdt_ctx *ctx, int stat, uint64_t *value);
 
 /* Host-memory analyze (analyze_data :206-222): h_entropy n*ws doubles, h_mapping n*ws int32

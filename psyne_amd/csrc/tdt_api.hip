@@ -30,7 +30,7 @@
 #if defined(PSY_FAST_BUILD) || (defined(PSY_PROF) && PSY_PROF) || defined(PSY_SINGLE_TU)
 #define PSY_DEC_REDUCE_TU 1  // (diagnostic single-file builds: the decode-reduce kernels are defined here)
 #endif
-#include "tdt_dec_reduce.h"
+#include "tdt_dec_reduce_tiled.h"
 #include "tdt_pack.h"
 #include "tdt_plan.h"
 #include "tdt_rawfb.h"
@@ -68,6 +68,8 @@ PSY_DEC_ACC_INSTANCES(PSY_DEC_ACC_EXT)
 // (the decode-reduce kernels: tdt_dec_reduce.hip)
 #define PSY_DEC_REDUCE_EXT(...) extern template __global__ void __VA_ARGS__(psy::ReduceArgs);
 PSY_DEC_REDUCE_INSTANCES(PSY_DEC_REDUCE_EXT)
+#define PSY_DEC_REDUCE_TILED_EXT(...) extern template __global__ void __VA_ARGS__(psy::RedTiledArgs);
+PSY_DEC_REDUCE_TILED_INSTANCES(PSY_DEC_REDUCE_TILED_EXT)
 #endif
 
 // The generic-word-size kernels live in tdt_anyws.hip; the diagnostic single-file builds leave
@@ -257,6 +259,26 @@ struct AnyDecWS {
     }
 };
 
+// Workspace of the tiled decode-reduce (tdt_dec_reduce_tiled.h), one per context, as AnyDecWS: the
+// calls that use it hold the context's lock.
+struct RedWS {
+    uint8_t *buf = nullptr;  // counters (kPlanCounterBytes) | one mark word per destination | the sum pass's partial sums
+    size_t bytes = 0;
+    uint8_t *rec = nullptr;  // RedRec records | tile entries | block entries | block sums | per-tile carry blocks
+    size_t rec_bytes = 0;
+    uint32_t lcap = 0, tcap = 0, bcap = 0;
+    CountHist<psy::RedCount> h;
+    bool last_tiled = false;  // the most recent call ran the plan (TDT_STAT_REDUCE_*: 0 otherwise)
+    void release() {
+        if (buf) (void)hipFree(buf);
+        if (rec) (void)hipFree(rec);
+        buf = rec = nullptr;
+        bytes = rec_bytes = 0;
+        lcap = tcap = bcap = 0;
+        h.release();
+    }
+};
+
 // host pipeline slots (chunks in flight per tdt_encode_host / tdt_decode_host call)
 constexpr int kHostSlots = 4;
 
@@ -354,6 +376,10 @@ struct tdt_ctx {
     // threshold take the decode tile pipeline; off: every one of them on the one-workgroup kernel
     bool any_dec_tiled = true;
     AnyDecWS anydw;
+    // TDT_OPT_REDUCE_TILED (PSYNE_TDT_REDUCE_TILED): destinations of tdt_decode_reduce_v above the threshold are
+    // summed as tiles over the whole device; off: every destination on its one workgroup
+    bool reduce_tiled = true;
+    RedWS redw;
     // diagnostic knobs (read once at tdt_ctx_create from the environment, or tdt_ctx_set_option)
     bool no_side = false;       // PSYNE_TDT_NO_SIDE: no side stream for the tile pipeline
     bool small_main = false;    // PSYNE_TDT_SMALL_MAIN: small lists on the caller's stream
@@ -2616,6 +2642,7 @@ int tdt_ctx_create(int device, const tdt_config *cfg, tdt_ctx **out) {
     if (const char *e = std::getenv("PSYNE_TDT_TILE_CAP")) x->tile_cap = (uint32_t)std::strtoul(e, nullptr, 10);
     if (const char *e = std::getenv("PSYNE_TDT_ANY_TILED")) x->any_tiled = *e != '0';
     if (const char *e = std::getenv("PSYNE_TDT_ANY_DEC_TILED")) x->any_dec_tiled = *e != '0';
+    if (const char *e = std::getenv("PSYNE_TDT_REDUCE_TILED")) x->reduce_tiled = *e != '0';
     auto flag = [](const char *name) {
         const char *e = std::getenv(name);
         return e && *e == '1';
@@ -2662,6 +2689,7 @@ void tdt_ctx_destroy(tdt_ctx *ctx) {
     ctx->pw.release();
     ctx->anyw.release();
     ctx->anydw.release();
+    ctx->redw.release();
     ctx->rf_h.release();
     for (auto &w : ctx->mx_pw)
         if (w) w->release();
@@ -2730,6 +2758,7 @@ int tdt_ctx_set_option(tdt_ctx *ctx, int option, uint64_t value) {
         case TDT_OPT_ANY_TILED: ctx->any_tiled = value != 0; return TDT_OK;
         case TDT_OPT_ANY_DEC_TILED: ctx->any_dec_tiled = value != 0; return TDT_OK;
         case TDT_OPT_RAW_FALLBACK: ctx->raw_fallback = value != 0; return TDT_OK;
+        case TDT_OPT_REDUCE_TILED: ctx->reduce_tiled = value != 0; return TDT_OK;
     }
     return set_err(TDT_E_ARG, "unknown option");
 }
@@ -2748,6 +2777,13 @@ int tdt_ctx_get_stat(tdt_ctx *ctx, int stat, uint64_t *value) {
     if (stat == TDT_STAT_RAW_FALLBACKS) {
         ctx->rf_h.refresh();  // (as below: the newest snapshot that has landed)
         *value = ctx->rf_last_on.load() && ctx->rf_h.valid ? ctx->rf_h[psy::RC_FLAGGED] : 0;
+        return TDT_OK;
+    }
+    if (stat == TDT_STAT_REDUCE_LARGE || stat == TDT_STAT_REDUCE_TILES) {
+        RedWS &r = ctx->redw;
+        r.h.refresh();  // (as below)
+        const bool on = r.last_tiled && r.h.valid;
+        *value = !on ? 0 : r.h[stat == TDT_STAT_REDUCE_LARGE ? psy::RC_TILED : psy::RC_TILED_TILES];
         return TDT_OK;
     }
     AnyDecWS &w = ctx->anydw;
@@ -3281,6 +3317,94 @@ int tdt_encoded_sizes_v(tdt_ctx *ctx, const uint8_t *const *d_msgs, const uint64
     return st ? st : raw_min_sizes(ctx, d_sizes, nullptr, d_enc_sizes, n_msgs, (hipStream_t)stream);
 }
 
+// ---------------------------------------------------------------------------------------
+// The tiled decode-reduce's workspace (RedWS; the kernels: tdt_dec_reduce_tiled.h), handled as the
+// generic-width decode's (decode_deferred): budgets that start small, the claims in a counter block,
+// the pinned snapshot behind the call, growth in powers of two on a later eager call with the old
+// buffer retired.  The host reads nothing back.  Under stream capture nothing grows and nothing is
+// snapshotted, and the call never fails because of this workspace: a destination that finds a cold
+// workspace or a spent budget stays on the one-workgroup kernel.
+namespace {
+static_assert(TDT_REDUCE_TILE_BYTES == psy::kRedTileBytes, "the header's tile size is the kernel's");
+constexpr uint32_t kRedL0 = 64, kRedLmax = 1u << 14;       // long destinations per call
+constexpr uint32_t kRedT0 = 16384, kRedTmax = 1u << 22;    // 33 KiB tiles: 528 MiB of output, 132 GiB
+constexpr uint32_t kRedB0 = 1u << 20, kRedBmax = 1u << 26; // block sums (1 KiB of pairs each): 1 GiB of blobs, 64 GiB
+struct RedLayoutWS { size_t tent, bent, bsum, tblk, bytes; };  // (records at 0)
+RedLayoutWS red_ws_layout(uint32_t lcap, uint32_t tcap, uint32_t bcap) {
+    const size_t tent = ((size_t)lcap * sizeof(psy::RedRec) + 15) & ~(size_t)15, bent = tent + 4ull * tcap,
+                 bsum = bent + 4ull * bcap, tblk = bsum + 4ull * bcap;
+    return {tent, bent, bsum, tblk, tblk + 4ull * psy::kRedTblk * tcap};
+}
+size_t red_buf_bytes(uint32_t n) { return psy::kPlanCounterBytes + ((4ull * n + 7) & ~7ull) + 8ull * ((n + 1023u) / 1024u); }
+
+// Ahead of the one-workgroup kernel of a tdt_decode_reduce_v call (the caller holds the context's lock):
+// the sum and plan launches and, unless the last landed snapshot saw no long destination, the prep
+// launch; a.mark is set for the kernel.  tiles: launch the block, scan and tile passes behind it
+// (t.a is the caller's to refresh); snap: then snapshot the counters.
+int reduce_tiled_begin(tdt_ctx *c, psy::ReduceArgs &a, psy::RedTiledArgs &t, bool &tiles, bool &snap, hipStream_t s) {
+    RedWS &w = c->redw;
+    const uint32_t n = a.n_msgs;
+    const bool cap = capturing(s);
+    auto &H = w.h;
+    if (!cap) H.refresh();  // (event queries are not capturable)
+    w.last_tiled = false;
+    if (red_buf_bytes(n) > w.bytes) {
+        if (cap) return TDT_OK;  // (a cold context: nothing to allocate under capture)
+        const size_t need = red_buf_bytes(n);
+        if (int st = grow_retiring(w.buf, w.bytes, need, psy::cap_double(need, w.bytes), c->retired, s)) return st;
+    }
+    // the tile pipeline is off when an earlier plan found no long destination (its launches would find none)
+    const bool tiles_on = !H.valid || H[psy::RC_LARGE] > 0;
+    if (tiles_on && !cap) {
+        uint32_t lc = w.lcap ? w.lcap : kRedL0, tc = w.tcap ? w.tcap : kRedT0, bc = w.bcap ? w.bcap : kRedB0;
+        if (H.valid) {  // what an earlier plan claimed, beyond its budget too
+            lc = std::max(lc, pow2_at_least(H[psy::RC_LARGE], kRedL0, kRedLmax));
+            tc = std::max(tc, pow2_at_least(H[psy::RC_TILES], kRedT0, kRedTmax));
+            bc = std::max(bc, pow2_at_least(H[psy::RC_BLOCKS], kRedB0, kRedBmax));
+        }
+        if (lc != w.lcap || tc != w.tcap || bc != w.bcap) {
+            const size_t b = red_ws_layout(lc, tc, bc).bytes;
+            w.lcap = w.tcap = w.bcap = 0;
+            // (retired, not freed: calls still queued, or a captured graph, may use the old records)
+            if (int st = psy::grow(w.rec, w.rec_bytes, b, b, retire_to(c->retired), DevAlloc{})) return st;
+            w.lcap = lc;
+            w.tcap = tc;
+            w.bcap = bc;
+        }
+    }
+    const bool on = tiles_on && w.rec;
+    const RedLayoutWS L = red_ws_layout(w.lcap, w.tcap, w.bcap);
+    t.cnt = reinterpret_cast<unsigned long long *>(w.buf);
+    t.part = reinterpret_cast<uint64_t *>(w.buf + psy::kPlanCounterBytes + ((4ull * n + 7) & ~7ull));
+    t.rec = reinterpret_cast<psy::RedRec *>(w.rec);
+    t.tent = reinterpret_cast<uint32_t *>(w.rec + L.tent);
+    t.bent = reinterpret_cast<uint32_t *>(w.rec + L.bent);
+    t.bsum = reinterpret_cast<uint32_t *>(w.rec + L.bsum);
+    t.tblk = reinterpret_cast<uint32_t *>(w.rec + L.tblk);
+    t.lcap = on ? w.lcap : 0u;
+    t.tcap = on ? std::min(w.tcap, std::max(c->tile_cap, 1u)) : 0u;
+    t.bcap = on ? w.bcap : 0u;
+    t.large_min = c->large_min;
+    t.a = a;
+    t.a.mark = on ? reinterpret_cast<const uint32_t *>(w.buf + psy::kPlanCounterBytes) : nullptr;
+    const uint32_t pg = (n + 1023u) / 1024u;
+    hipLaunchKernelGGL(psy::tdt_decode_reduce_sum_kernel, dim3(pg), dim3(1024), 0, s, t);
+    hipLaunchKernelGGL(psy::tdt_decode_reduce_plan_kernel, dim3(pg), dim3(1024), 0, s, t);
+    if (on) {
+        const dim3 g(std::min(t.lcap, (uint32_t)c->cus * 4u));
+        if (a.n_peers <= 2) hipLaunchKernelGGL(psy::tdt_decode_reduce_prep_kernel<2>, g, dim3(128), 0, s, t);
+        else if (a.n_peers <= 4) hipLaunchKernelGGL(psy::tdt_decode_reduce_prep_kernel<4>, g, dim3(256), 0, s, t);
+        else hipLaunchKernelGGL(psy::tdt_decode_reduce_prep_kernel<8>, g, dim3(512), 0, s, t);
+    }
+    HIPCHK(hipGetLastError());
+    a.mark = t.a.mark;
+    tiles = on;
+    snap = !cap;
+    w.last_tiled = true;
+    return TDT_OK;
+}
+}  // namespace
+
 int tdt_decode_batch_v(tdt_ctx *ctx, const uint8_t *const *d_blobs, const uint64_t *d_blob_len, uint32_t n_msgs,
                        uint8_t *const *d_outs, const uint64_t *d_out_cap, uint64_t *d_out_len, int32_t *d_status,
                        void *stream) {
@@ -3338,11 +3462,36 @@ int tdt_decode_reduce_v(tdt_ctx *ctx, const uint8_t *const *d_blobs, const uint6
     a.out_len = d_out_len;
     a.status = d_status;
     a.peer_status = d_peer_status;
+    // the long destinations: planned and prepared ahead of the one-workgroup kernel, summed as tiles behind it
+    std::unique_lock<std::mutex> lk(ctx->mu, std::defer_lock);
+    psy::RedTiledArgs t{};
+    bool tiles = false, snap = false;
+    if (ctx->reduce_tiled) {
+        lk.lock();
+        if (int st = reduce_tiled_begin(ctx, a, t, tiles, snap, s)) return st;
+    } else {
+        std::lock_guard<std::mutex> g(ctx->mu);
+        ctx->redw.last_tiled = false;
+    }
     // one workgroup per destination, one wave per peer: the smallest team that holds the peers
     if (n_peers <= 2) hipLaunchKernelGGL(psy::tdt_decode_reduce_kernel<2>, dim3(n_msgs), dim3(128), 0, s, a);
     else if (n_peers <= 4) hipLaunchKernelGGL(psy::tdt_decode_reduce_kernel<4>, dim3(n_msgs), dim3(256), 0, s, a);
     else hipLaunchKernelGGL(psy::tdt_decode_reduce_kernel<8>, dim3(n_msgs), dim3(512), 0, s, a);
     HIPCHK(hipGetLastError());
+    if (tiles) {
+        t.a = a;
+        // block sums, their scan, then the tiles: 16 waves per CU is what the staged windows' LDS admits
+        const uint32_t cus = (uint32_t)ctx->cus, nw = n_peers <= 2 ? 2u : n_peers <= 4 ? 4u : 8u;
+        hipLaunchKernelGGL(psy::tdt_decode_reduce_block_kernel, dim3(cus * 8u), dim3(256), 0, s, t);
+        hipLaunchKernelGGL(psy::tdt_decode_reduce_scan_kernel, dim3(std::min(t.lcap, cus * 4u), 2u * n_peers), dim3(64), 0, s, t);
+        const dim3 tg(std::max(1u, std::min(t.tcap, cus * (16u / nw))));
+        if (nw == 2) hipLaunchKernelGGL(psy::tdt_decode_reduce_tile_kernel<2>, tg, dim3(128), 0, s, t);
+        else if (nw == 4) hipLaunchKernelGGL(psy::tdt_decode_reduce_tile_kernel<4>, tg, dim3(256), 0, s, t);
+        else hipLaunchKernelGGL(psy::tdt_decode_reduce_tile_kernel<8>, tg, dim3(512), 0, s, t);
+        HIPCHK(hipGetLastError());
+    }
+    if (snap)
+        if (int st = record_counts(ctx->redw.h, ctx->redw.buf, n_msgs, s)) return st;
     // the destinations it left to the serial path (none, with psyne's encoder): 64 statuses per wave and step
     const uint32_t sg = (n_msgs + 63u) / 64u;
     hipLaunchKernelGGL(psy::tdt_decode_reduce_serial_kernel, dim3(sg < 1024u ? sg : 1024u), dim3(64), 0, s, a);

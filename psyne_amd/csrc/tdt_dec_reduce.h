@@ -41,9 +41,12 @@
 //      are selected by wave-uniform scalars (the wave index and the record's kind, through
 //      readfirstlane), and none of them leaves its loop early.
 //
-// A long destination is walked by its one workgroup: there is no tiled form, and a tensor of many
-// MiB runs on one CU.  Send such tensors through tdt_decode_accumulate_v, whose
-// tiled pipeline spreads them over the chip.
+// A long destination (above the batch's large-message threshold) is not walked by this kernel: the
+// tiled form (tdt_dec_reduce_tiled.h) marks it, sums it as tiles over the whole device with the same
+// sink, and the workgroup here returns at the mark (ReduceArgs::mark).  Without marks (a null array:
+// TDT_OPT_REDUCE_TILED 0, a cold workspace under capture) and for every destination the tiled form
+// leaves alone — short, refused, serial, over a budget — one workgroup walks the destination as
+// described above, however long it is.
 #pragma once
 #include "tdt_decode.h"
 
@@ -69,6 +72,9 @@ struct ReduceArgs {
     uint64_t *out_len;
     int32_t *status;
     int32_t *peer_status;  // [n_peers][n_msgs] or null
+    // [n_msgs] or null: a destination with a set word is summed by the tile pass
+    // (tdt_dec_reduce_tiled.h), and the one-workgroup kernel returns at it
+    const uint32_t *mark;
 };
 
 // LDS of a workgroup of NW waves: each wave's decode state (the decoder's own layout), the staged
@@ -121,7 +127,8 @@ struct RedSink {
     uint8_t *mine;   // this wave's slice
     uint8_t *dst;
     uint64_t osize;
-    uint32_t gc;  // the destination's 16-byte groups (the last may be partial)
+    uint32_t gc;     // the end of the walk: the destination's 16-byte groups (the last may be partial), or a tile's end
+    uint32_t gbase;  // the first group of the walk (0, or a tile's first group): window `win` starts kRedWinGroups * win past it
     uint32_t n_peers, elem, tid;
     bool set, dal16;
     uint4 dpre[NPF];  // the destination groups of the coming window (whole aligned groups, not under SET)
@@ -136,7 +143,7 @@ struct RedSink {
         if (set) return;
 #pragma unroll
         for (int q = 0; q < NPF; ++q) {
-            const uint32_t j = tid + (uint32_t)q * T, g = win * kRedWinGroups + j;
+            const uint32_t j = tid + (uint32_t)q * T, g = gbase + win * kRedWinGroups + j;
             if (j < kRedWinGroups && g < gc && whole(g)) dpre[q] = acc_ld16(dst + 16ull * g);
         }
     }
@@ -146,7 +153,7 @@ struct RedSink {
         __syncthreads();  // A: every peer's slice of this window is staged
 #pragma unroll
         for (int q = 0; q < NPF; ++q) {
-            const uint32_t j = tid + (uint32_t)q * T, g = win * kRedWinGroups + j;
+            const uint32_t j = tid + (uint32_t)q * T, g = gbase + win * kRedWinGroups + j;
             if (j < kRedWinGroups && g < gc) {
                 uint8_t *p = dst + 16ull * g;
                 const bool wh = whole(g);
@@ -190,12 +197,75 @@ __device__ __forceinline__ RedVerdict red_verdict(const uint32_t *rec, uint32_t 
     return v;
 }
 
+// The header phase of wave w < n_peers: peer w's blob of destination msg is parsed (parse_fast;
+// blob_check for every other shape) and checked against the destination (capacity, the 2^35 limit,
+// element alignment and size: acc_status); (kind, status, decoded size) go to the LDS record rec[4 w ..]
+// and the status to peer_status.  hdrc: kHdrCache bytes of the wave's own LDS.  Shared by the
+// one-workgroup kernel and the tiled form's prep pass, so both refuse and accept the same blobs.
+struct RedHead {
+    FastHdr H;
+    const uint8_t *blob;
+    uint64_t len;
+};
+__device__ __forceinline__ RedHead red_header(const ReduceArgs &a, uint32_t msg, uint32_t w, uint32_t elem, uint8_t *dst,
+                                              uint64_t cap, uint8_t *hdrc, uint32_t *rec) {
+    const uint32_t lane = (uint32_t)lane_id();
+    const uint64_t bi = (uint64_t)w * a.n_msgs + msg;
+    const uint8_t *blob = reinterpret_cast<const uint8_t *>(a.blobs[bi]);
+    const uint64_t len = a.blob_len[bi];
+    const uint32_t hcl = len < (uint64_t)kHdrCache ? (uint32_t)len : (uint32_t)kHdrCache;
+    {
+        static_assert(kHdrCache == 256, "one dword per lane");
+        const uint32_t o = lane * 4u;
+        uint32_t v = 0;
+        if (((uintptr_t)blob & 3) == 0 && o + 4u <= hcl) {
+            v = *reinterpret_cast<const uint32_t *>(blob + o);
+        } else {
+#pragma unroll
+            for (uint32_t i = 0; i < 4; ++i)
+                if (o + i < hcl) v |= (uint32_t)blob[o + i] << (8u * i);
+        }
+        reinterpret_cast<uint32_t *>(hdrc)[lane] = v;
+    }
+    team_sync<1>();
+    const FastHdr H = parse_fast(blob, len, hdrc, hcl);
+    uint32_t st = ST_OK;
+    uint64_t osize = H.osize;
+    if (H.kind == 0u) {
+        // every other shape, errors included: the reference's checks (every lane the same words)
+        auto rd32 = [&](uint64_t off) -> uint32_t {
+            if (off + 4 <= hcl) return ld_u32_bytes(hdrc + off);
+            return ld_u32_bytes(blob + off);
+        };
+        uint32_t uncp;
+        st = blob_check(rd32, len, uncp, osize);
+    }
+    st = (uint32_t)__builtin_amdgcn_readfirstlane((int)st);
+    if (st == ST_DEFER) {  // a generic word size: no accumulate form
+        st = elem > kElemMax || elem == kElemStore ? (uint32_t)ST_ARG : (uint32_t)ST_UNSUPPORTED;
+    } else {
+        if (st == ST_OK && osize > cap) st = ST_CAPACITY;
+        if (st == ST_OK && (osize >> 35) != 0) st = ST_UNSUPPORTED;  // (group indices are 32 bits wide)
+        if (st == ST_OK && elem == kElemStore) st = ST_ARG;
+        st = acc_status(st, elem, dst, osize);
+    }
+    if (st != ST_OK) osize = 0;
+    if (lane == 0) {
+        rec[4 * w] = H.kind;
+        rec[4 * w + 1] = st;
+        *reinterpret_cast<uint64_t *>(rec + 4 * w + 2) = osize;
+        if (a.peer_status) a.peer_status[bi] = (int32_t)st;
+    }
+    return RedHead{H, blob, len};
+}
+
 template <int NW>
 __global__ __launch_bounds__(64 * NW) void tdt_decode_reduce_kernel(ReduceArgs a) {
     using Lay = RedLayout<NW>;
     using Dec = DecLayoutT<kRedWR>;
     __shared__ __attribute__((aligned(16))) uint8_t smem[Lay::BYTES];
     const uint32_t msg = blockIdx.x;
+    if (a.mark && a.mark[msg]) return;  // (uniform) the tile pass sums it
     const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const uint32_t lane = (uint32_t)lane_id();
     const uint32_t n_peers = a.n_peers;
@@ -208,59 +278,10 @@ __global__ __launch_bounds__(64 * NW) void tdt_decode_reduce_kernel(ReduceArgs a
     const uint64_t cap = a.out_cap[msg];
 
     // ------------------------------------------------ header: wave k checks peer k's blob
-    const uint8_t *blob = nullptr, *blim = nullptr;
-    uint64_t len = 0;
-    FastHdr H{};
-    if (w < n_peers) {
-        const uint64_t bi = (uint64_t)w * a.n_msgs + msg;
-        blob = reinterpret_cast<const uint8_t *>(a.blobs[bi]);
-        len = a.blob_len[bi];
-        blim = blob + len;
-        uint8_t *hdrc = dec + Dec::OFF_HDR;
-        const uint32_t hcl = len < (uint64_t)kHdrCache ? (uint32_t)len : (uint32_t)kHdrCache;
-        {
-            static_assert(kHdrCache == 256, "one dword per lane");
-            const uint32_t o = lane * 4u;
-            uint32_t v = 0;
-            if (((uintptr_t)blob & 3) == 0 && o + 4u <= hcl) {
-                v = *reinterpret_cast<const uint32_t *>(blob + o);
-            } else {
-#pragma unroll
-                for (uint32_t i = 0; i < 4; ++i)
-                    if (o + i < hcl) v |= (uint32_t)blob[o + i] << (8u * i);
-            }
-            reinterpret_cast<uint32_t *>(hdrc)[lane] = v;
-        }
-        team_sync<1>();
-        H = parse_fast(blob, len, hdrc, hcl);
-        uint32_t st = ST_OK;
-        uint64_t osize = H.osize;
-        if (H.kind == 0u) {
-            // every other shape, errors included: the reference's checks (every lane the same words)
-            auto rd32 = [&](uint64_t off) -> uint32_t {
-                if (off + 4 <= hcl) return ld_u32_bytes(hdrc + off);
-                return ld_u32_bytes(blob + off);
-            };
-            uint32_t uncp;
-            st = blob_check(rd32, len, uncp, osize);
-        }
-        st = (uint32_t)__builtin_amdgcn_readfirstlane((int)st);
-        if (st == ST_DEFER) {  // a generic word size: no accumulate form
-            st = elem > kElemMax || elem == kElemStore ? (uint32_t)ST_ARG : (uint32_t)ST_UNSUPPORTED;
-        } else {
-            if (st == ST_OK && osize > cap) st = ST_CAPACITY;
-            if (st == ST_OK && (osize >> 35) != 0) st = ST_UNSUPPORTED;  // (group indices are 32 bits wide)
-            if (st == ST_OK && elem == kElemStore) st = ST_ARG;
-            st = acc_status(st, elem, dst, osize);
-        }
-        if (st != ST_OK) osize = 0;
-        if (lane == 0) {
-            rec[4 * w] = H.kind;
-            rec[4 * w + 1] = st;
-            *reinterpret_cast<uint64_t *>(rec + 4 * w + 2) = osize;
-            if (a.peer_status) a.peer_status[bi] = (int32_t)st;
-        }
-    }
+    RedHead P{};
+    if (w < n_peers) P = red_header(a, msg, w, elem, dst, cap, dec + Dec::OFF_HDR, rec);
+    const FastHdr &H = P.H;
+    const uint8_t *const blob = P.blob, *const blim = P.blob + P.len;
     __syncthreads();  // header barrier: every wave, once
     const RedVerdict V = red_verdict(rec, n_peers);
     if (w == 0 && lane == 0) {
@@ -280,6 +301,7 @@ __global__ __launch_bounds__(64 * NW) void tdt_decode_reduce_kernel(ReduceArgs a
     S.dst = dst;
     S.osize = osize;
     S.gc = gc;
+    S.gbase = 0u;
     S.n_peers = n_peers;
     S.elem = elem;
     S.tid = threadIdx.x;

@@ -53,7 +53,17 @@ enum AnyDecCount : int {
     ADC_TILES = 2        // tiles claimed (likewise)
 };
 
+// The tiled decode-reduce (tdt_dec_reduce_tiled.h) likewise; its sum pass zeroes the block.
+enum RedCount : int {
+    RC_LARGE = 0,        // long-destination records claimed (beyond the budget too: the next call grows it)
+    RC_TILES = 1,        // tile entries claimed (likewise)
+    RC_BLOCKS = 2,       // block sums claimed (likewise)
+    RC_TILED = 3,        // destinations the prep pass handed to the tile pass
+    RC_TILED_TILES = 4   // their tiles
+};
+
 // u32 view of the block: index of a counter's low word (the only place the two units meet)
+constexpr int lo32(RedCount k) { return 2 * (int)k; }
 constexpr int lo32(EncCount k) { return 2 * (int)k; }
 constexpr int lo32(DecCount k) { return 2 * (int)k; }
 constexpr int lo32(AnyCount k) { return 2 * (int)k; }

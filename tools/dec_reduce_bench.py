@@ -10,6 +10,13 @@ after --warmup rounds; median of --steps rounds with the lowest and highest.  On
            4    the same shape as bfloat16 at K = 4
            5    SMALL x 1 KiB float32 at K = 4
            6    row 2 with every blob UNCP
+           7-9  one long float32 destination, the tiled form's rows: 64 MiB at K = 4, 256 MiB at K = 2 and K = 8
+           a    one 256 MiB destination beside 4,096 x 64 KiB at K = 4
+           b    row 2 again with the extra column
+                these five add column d_reduce_one_wg: decode_reduce_v with TDT_OPT_REDUCE_TILED 0, the
+                one-workgroup kernels alone (what the call launched before the tiled form); b_reduce runs
+                with the default, 1.  --parent: the loaded library (PSYNE_TDT_LIB) predates the option;
+                column d is left out and b_reduce is that library's call.
 
 Before timing, each row checks once that (a) and (b) leave identical bytes on equal destinations.
 
@@ -34,6 +41,7 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--rows", default="123456")
+    ap.add_argument("--parent", action="store_true")
     ap.add_argument("--out", default="profiles/dec_reduce/dec_reduce_bench.jsonl")
     a = ap.parse_args()
     import torch
@@ -67,11 +75,15 @@ def main():
                 ms[k].append(e0.elapsed_time(e1))
         return {k: dict(min=min(v), median=float(np.median(v)), max=max(v)) for k, v in ms.items()}
 
-    def run(row, n, nbytes, K, dtype=torch.float32, uncp=False):
+    def run(row, n, nbytes, K, dtype=torch.float32, uncp=False, sizes=None, one_wg=False):
         ws, code = dtype.itemsize, {torch.float32: 1, torch.bfloat16: 3}[dtype]
+        if sizes is None:
+            sizes = [nbytes] * n
+        n, total = len(sizes), sum(sizes)
+        starts = torch.tensor(np.cumsum([0] + sizes[:-1]), dtype=torch.int64, device="cuda")
         ptrs, lens, keep, wire = [], [], [], 0
         for _ in range(K):  # each peer's blobs: one buffer, message i at its slot
-            data = grads(n * nbytes, dtype)
+            data = grads(total, dtype)
             if uncp:
                 rows = torch.empty((n, nbytes + 4), dtype=torch.uint8, device="cuda")
                 rows[:, :4] = torch.tensor(list(b"PCNU"), dtype=torch.uint8, device="cuda")
@@ -80,7 +92,7 @@ def main():
                 ln = torch.full((n,), nbytes + 4, dtype=torch.int64, device="cuda")
             else:
                 enc = codec_of(ws)
-                blobs, slots, ln, st = enc.encode_tensors(list(torch.split(data, nbytes // ws)))
+                blobs, slots, ln, st = enc.encode_tensors(list(torch.split(data, [b // ws for b in sizes])))
                 torch.cuda.synchronize()
                 assert int(st.abs().sum()) == 0
                 off, ln = slots[:n].clone(), ln[:n].clone()
@@ -91,18 +103,23 @@ def main():
             lens.append(ln)
             wire += int(ln.sum().item())
         all_ptrs, all_lens = torch.cat(ptrs), torch.cat(lens)
-        cap = torch.full((n,), nbytes, dtype=torch.int64, device="cuda")
+        cap = torch.tensor(sizes, dtype=torch.int64, device="cuda")
 
         def dests(fill):
-            buf = torch.empty(n * nbytes // ws, dtype=dtype, device="cuda")
+            buf = torch.empty(total // ws, dtype=dtype, device="cuda")
             if fill is not None:
                 buf.fill_(fill)
-            return buf, torch.arange(n, device="cuda", dtype=torch.int64) * nbytes + buf.data_ptr()
+            return buf, starts + buf.data_ptr()
 
+        one_wg = one_wg and not a.parent
         (da, ta), (db, tb), (dc, tc) = dests(0.25), dests(0.25), dests(None)
         ctx = dict(a=codec_of(ws), b=codec_of(ws), c=codec_of(ws))
+        if one_wg:
+            from psyne_amd._lib import TDT_OPT_REDUCE_TILED
+            (dd, td), ctx["d"] = dests(0.25), codec_of(ws)
+            ctx["d"].set_option(TDT_OPT_REDUCE_TILED, 0)
         res = {k: (torch.zeros(n, dtype=torch.int64, device="cuda"), torch.zeros(n, dtype=torch.int32, device="cuda"))
-               for k in "abc"}
+               for k in ctx}
 
         def k_calls():
             for k in range(K):
@@ -113,11 +130,17 @@ def main():
                                                                status=res["b"][1]),
                      c_decode_one_peer=lambda: ctx["c"].decode_v(ptrs[0], lens[0], tc, cap, lengths=res["c"][0],
                                                                  status=res["c"][1]))
+        if one_wg:
+            calls["d_reduce_one_wg"] = lambda: ctx["d"].decode_reduce_v(all_ptrs, all_lens, K, td, cap, elem=code,
+                                                                        lengths=res["d"][0], status=res["d"][1])
+            calls["d_reduce_one_wg"]()
         calls["a_k_accumulates"]()
         calls["b_reduce"]()
         torch.cuda.synchronize()
-        assert all(int(st.abs().sum()) == 0 for _, st in (res["a"], res["b"]))
+        assert all(int(st.abs().sum()) == 0 for _, st in res.values())
         assert torch.equal(da.view(torch.uint8), db.view(torch.uint8)), "the reduce call and K accumulate calls differ"
+        assert not one_wg or torch.equal(dd.view(torch.uint8), db.view(torch.uint8)), "the tiled and one-workgroup forms differ"
+        tiled = None if a.parent else ctx["b"].stat("REDUCE_LARGE")
         t = timed(calls)
         torch.cuda.synchronize()
         assert all(int(st.abs().sum()) == 0 for _, st in res.values())
@@ -125,7 +148,8 @@ def main():
             assert c.error_flags() == 0
             c.close()
         line = json.dumps(dict(tool="dec_reduce_bench", row=row, steps=a.steps, warmup=a.warmup, msgs=n, peers=K,
-                               decoded_bytes_per_peer=n * nbytes, wire_bytes=wire, ms=t,
+                               decoded_bytes_per_peer=total, wire_bytes=wire, ms=t, tiled_destinations=tiled,
+                               parent_library=a.parent,
                                reduce_over_k_accumulates=t["b_reduce"]["median"] / t["a_k_accumulates"]["median"],
                                reduce_median_below_accumulates_min=t["b_reduce"]["median"] < t["a_k_accumulates"]["min"]))
         print(line, flush=True)
@@ -144,6 +168,13 @@ def main():
         run("5_f32_%dx1024_k4" % a.small, a.small, 1024, 4)
     if "6" in a.rows:
         run("6_f32_%dx%d_k4_uncp" % (a.msgs, a.bytes), a.msgs, a.bytes, 4, uncp=True)
+    for r, mib, K in (("7", 64, 4), ("8", 256, 2), ("9", 256, 8)):
+        if r in a.rows:
+            run("%s_f32_1x%dMiB_k%d" % (r, mib, K), 0, 0, K, sizes=[mib << 20], one_wg=True)
+    if "a" in a.rows:
+        run("a_f32_1x256MiB_4096x65536_k4", 0, 0, 4, sizes=[256 << 20] + [65536] * 4096, one_wg=True)
+    if "b" in a.rows:
+        run("b_f32_%dx%d_k4" % (a.msgs, a.bytes), a.msgs, a.bytes, 4, one_wg=True)
 
 
 if __name__ == "__main__":
