@@ -98,6 +98,10 @@ extern "C" {
 #define TDT_ELEM_F16 2
 #define TDT_ELEM_BF16 3
 #define TDT_ELEM_F64 4
+/* Widening codes, tdt_decode_reduce_v only (the destination's code | the wire's << 4): the blobs hold
+ * 2-byte elements, the destination fp32.  tdt_decode_accumulate_v answers them TDT_E_ARG. */
+#define TDT_ELEM_F32_FROM_BF16 0x31
+#define TDT_ELEM_F32_FROM_F16 0x21
 
 /* TDTConfig (:31-43).  Fields the reference declares but never reads
  * (auto_detect_clusters, max_clusters, enable_simd) are omitted. */
@@ -258,6 +262,22 @@ int tdt_decode_accumulate_v(tdt_ctx *ctx, const uint8_t *const *d_blobs, const u
  *   Element codes: TDT_ELEM_F32, F16, BF16, F64.  TDT_ELEM_STORE or an unknown code is TDT_E_ARG (per
  *     destination from d_elem, the call's return value from `elem`); n_peers outside
  *     1..TDT_REDUCE_MAX_PEERS returns TDT_E_ARG.
+ *   Wide destinations: TDT_ELEM_F32_FROM_BF16 and TDT_ELEM_F32_FROM_F16 sum half-precision blobs into an
+ *     fp32 destination (mixed-precision training: gradients travel at 2 bytes and are kept in fp32).  A
+ *     destination whose blobs each decode to w bytes takes them as w/2 bf16 / fp16 elements, UNCP or
+ *     fast-path TDT at any tuned word size: dst[j] = ((dst[j] + f32(b0[j])) + f32(b1[j])) + ... over w/2
+ *     fp32 elements, the widening exact (fp16 subnormals become the fp32 values they denote), each + one
+ *     IEEE fp32 add; with TDT_REDUCE_SET the chain starts from f32(b0[j]).  Decoded zeros take part as
+ *     +0.0f.  d_out_cap[i] is in destination bytes and must be at least 2w (TDT_E_CAPACITY: a capacity
+ *     of w holds the wire, not the destination); d_out_len[i] reports 2w.  TDT_E_ELEMENT when the
+ *     destination is not 4-byte aligned or w is odd; TDT_E_MISMATCH on the decoded sizes as for every
+ *     code; TDT_E_UNSUPPORTED when w >= 2^34 (the destination's group indices are 32 bits wide), for a
+ *     generic-width peer, and for a valid peer off the fast path (three or more referenced streams, odd
+ *     segments, more than 16 stored streams): such peers are summed by the serial kernel through the
+ *     accumulate decode's stores, which have no widening form, and psyne's encoder writes fast-path
+ *     blobs only.  Every refusal precedes the first store.  One list may mix narrow and wide codes
+ *     through d_elem; all peers of one destination share its wire type.  A one-peer widening add is this
+ *     call with n_peers = 1.
  *   All or nothing per destination: every one of its blobs is checked (header, truncation, capacity
  *     against the decoded size, element alignment and size as in tdt_decode_accumulate_v) before a
  *     byte of it is written.  d_status[i] is TDT_OK, or the status of the lowest-numbered failing

@@ -17,6 +17,8 @@ TDT_E_HIP, TDT_E_ARG, TDT_E_CAPTURE = 10, 11, 12
 TDT_E_ELEMENT = 13  # decode-accumulate: destination not aligned to its element, or not a whole number of elements
 # element codes of tdt_decode_accumulate_v (TDT_ELEM_STORE: a plain decode of that message)
 TDT_ELEM_STORE, TDT_ELEM_F32, TDT_ELEM_F16, TDT_ELEM_BF16, TDT_ELEM_F64 = 0, 1, 2, 3, 4
+# tdt_decode_reduce_v only: bf16 / fp16 blobs summed into a float32 destination (destination | wire << 4)
+TDT_ELEM_F32_FROM_BF16, TDT_ELEM_F32_FROM_F16 = 0x31, 0x21
 TDT_E_MISMATCH = 14  # decode-reduce: the peers' blobs of one destination decode to different sizes
 TDT_REDUCE_MAX_PEERS = 8
 TDT_REDUCE_SET = 1  # tdt_decode_reduce_v flag: dst = sum of the peers (default: dst = dst + sum)

@@ -3443,7 +3443,14 @@ int tdt_decode_reduce_v(tdt_ctx *ctx, const uint8_t *const *d_blobs, const uint6
                         uint32_t flags, uint64_t *d_out_len, int32_t *d_status, int32_t *d_peer_status, void *stream) {
     if (!ctx) return set_err(TDT_E_ARG, "null context");
     if (n_peers < 1 || n_peers > TDT_REDUCE_MAX_PEERS) return set_err(TDT_E_ARG, "n_peers outside 1..TDT_REDUCE_MAX_PEERS");
-    if (!d_elem && (elem < TDT_ELEM_F32 || elem > TDT_ELEM_F64)) return set_err(TDT_E_ARG, "no element type to sum in");
+    const bool wide_elem = elem == TDT_ELEM_F32_FROM_BF16 || elem == TDT_ELEM_F32_FROM_F16;
+    if (!d_elem && !wide_elem && (elem < TDT_ELEM_F32 || elem > TDT_ELEM_F64))
+        return set_err(TDT_E_ARG, "no element type to sum in");
+    // The instances that also take the widening codes: chosen when `elem` widens, and for codes per
+    // destination (d_elem lies on the device: any of them may widen, and narrow and wide destinations
+    // share the launch, branching on the destination's uniform code).  A narrow `elem` keeps the narrow
+    // instances, whose registers and code are what they were.
+    const bool wide = d_elem || wide_elem;
     if (flags & ~(uint32_t)TDT_REDUCE_SET) return set_err(TDT_E_ARG, "unknown flag");
     if (n_msgs == 0) return TDT_OK;
     if (!(d_blobs && d_blob_len && d_outs && d_out_cap && d_status)) return set_err(TDT_E_ARG, "null pointer, size or status array");
@@ -3474,7 +3481,11 @@ int tdt_decode_reduce_v(tdt_ctx *ctx, const uint8_t *const *d_blobs, const uint6
         ctx->redw.last_tiled = false;
     }
     // one workgroup per destination, one wave per peer: the smallest team that holds the peers
-    if (n_peers <= 2) hipLaunchKernelGGL(psy::tdt_decode_reduce_kernel<2>, dim3(n_msgs), dim3(128), 0, s, a);
+    if (wide) {
+        if (n_peers <= 2) hipLaunchKernelGGL(psy::tdt_decode_reduce_wide_kernel<2>, dim3(n_msgs), dim3(128), 0, s, a);
+        else if (n_peers <= 4) hipLaunchKernelGGL(psy::tdt_decode_reduce_wide_kernel<4>, dim3(n_msgs), dim3(256), 0, s, a);
+        else hipLaunchKernelGGL(psy::tdt_decode_reduce_wide_kernel<8>, dim3(n_msgs), dim3(512), 0, s, a);
+    } else if (n_peers <= 2) hipLaunchKernelGGL(psy::tdt_decode_reduce_kernel<2>, dim3(n_msgs), dim3(128), 0, s, a);
     else if (n_peers <= 4) hipLaunchKernelGGL(psy::tdt_decode_reduce_kernel<4>, dim3(n_msgs), dim3(256), 0, s, a);
     else hipLaunchKernelGGL(psy::tdt_decode_reduce_kernel<8>, dim3(n_msgs), dim3(512), 0, s, a);
     HIPCHK(hipGetLastError());
@@ -3485,7 +3496,11 @@ int tdt_decode_reduce_v(tdt_ctx *ctx, const uint8_t *const *d_blobs, const uint6
         hipLaunchKernelGGL(psy::tdt_decode_reduce_block_kernel, dim3(cus * 8u), dim3(256), 0, s, t);
         hipLaunchKernelGGL(psy::tdt_decode_reduce_scan_kernel, dim3(std::min(t.lcap, cus * 4u), 2u * n_peers), dim3(64), 0, s, t);
         const dim3 tg(std::max(1u, std::min(t.tcap, cus * (16u / nw))));
-        if (nw == 2) hipLaunchKernelGGL(psy::tdt_decode_reduce_tile_kernel<2>, tg, dim3(128), 0, s, t);
+        if (wide) {
+            if (nw == 2) hipLaunchKernelGGL(psy::tdt_decode_reduce_tile_wide_kernel<2>, tg, dim3(128), 0, s, t);
+            else if (nw == 4) hipLaunchKernelGGL(psy::tdt_decode_reduce_tile_wide_kernel<4>, tg, dim3(256), 0, s, t);
+            else hipLaunchKernelGGL(psy::tdt_decode_reduce_tile_wide_kernel<8>, tg, dim3(512), 0, s, t);
+        } else if (nw == 2) hipLaunchKernelGGL(psy::tdt_decode_reduce_tile_kernel<2>, tg, dim3(128), 0, s, t);
         else if (nw == 4) hipLaunchKernelGGL(psy::tdt_decode_reduce_tile_kernel<4>, tg, dim3(256), 0, s, t);
         else hipLaunchKernelGGL(psy::tdt_decode_reduce_tile_kernel<8>, tg, dim3(512), 0, s, t);
         HIPCHK(hipGetLastError());

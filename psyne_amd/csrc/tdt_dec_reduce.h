@@ -1,7 +1,12 @@
 // tdt_dec_reduce.h — decode-reduce (tdt_decode_reduce_v): the blobs of up to 8 peers for one
 // destination are decoded and summed into it in one pass, dst = ((dst + b0) + b1) + ... in the
 // destination's element type (or, with TDT_REDUCE_SET, dst = (b0 + b1) + ...), the bits of that
-// many tdt_decode_accumulate_v calls in peer order.
+// many tdt_decode_accumulate_v calls in peer order.  With a widening code (TDT_ELEM_F32_FROM_BF16 /
+// _F16) the blobs hold 2-byte elements and the destination fp32 of twice the bytes: the same decode and
+// staging, a sum stage that widens (RedSinkT, WIDE), in instances of their own; the fused path only —
+// the serial kernel below sums through decode_one's ACC stores, which have no widening form, and
+// psyne's encoder writes fast-path blobs only, so a wide destination with a peer off the fast path is
+// TDT_E_UNSUPPORTED.
 //
 // Work split: one workgroup per destination, one 64-lane wave per peer; NW, the
 // workgroup's wave count, is the smallest of 2, 4, 8 that holds the peers.  A wave without a peer
@@ -116,18 +121,95 @@ __device__ __forceinline__ void red_st16(uint8_t *p, uint4 v, uint32_t valid) {
         if (2u * i < valid) q[i] = (uint16_t)(w[i >> 1] >> (16u * (i & 1u)));
 }
 
+// The widening codes (TDT_ELEM_F32_FROM_BF16, TDT_ELEM_F32_FROM_F16): the destination's code in the
+// low nibble, the wire's in the high one.  Decode-reduce's own: the accumulate kernels (acc_status,
+// kElemMax) know neither.
+constexpr uint32_t kElemF32FromBF16 = kElemF32 | kElemBF16 << 4, kElemF32FromF16 = kElemF32 | kElemF16 << 4;
+__device__ __forceinline__ bool red_wide(uint32_t e) { return e == kElemF32FromBF16 || e == kElemF32FromF16; }
+
+// Four wire elements (8 bytes of a staged slice) as fp32, exactly: bf16 is the upper half of an fp32
+// (a shift and a mask per dword), fp16 goes through v_cvt_f32_f16, which keeps subnormals (the fp16
+// denormal mode of these kernels is IEEE)
+typedef float psy_f4 __attribute__((ext_vector_type(4)));
+template <bool BF>
+__device__ __forceinline__ psy_f4 red_widen(uint2 x) {
+    psy_f4 r;
+    if constexpr (BF) {
+        r.x = __uint_as_float(x.x << 16);
+        r.y = __uint_as_float(x.x & 0xffff0000u);
+        r.z = __uint_as_float(x.y << 16);
+        r.w = __uint_as_float(x.y & 0xffff0000u);
+    } else {
+        r.x = (float)__builtin_bit_cast(_Float16, (uint16_t)x.x);
+        r.y = (float)__builtin_bit_cast(_Float16, (uint16_t)(x.x >> 16));
+        r.z = (float)__builtin_bit_cast(_Float16, (uint16_t)x.y);
+        r.w = (float)__builtin_bit_cast(_Float16, (uint16_t)(x.y >> 16));
+    }
+    return r;
+}
+__device__ __forceinline__ psy_f4 red_f4(uint4 v) {
+    psy_f4 r;
+    r.x = __uint_as_float(v.x), r.y = __uint_as_float(v.y), r.z = __uint_as_float(v.z), r.w = __uint_as_float(v.w);
+    return r;
+}
+
+// red_ld16 / red_st16 of a wide destination: 4-byte aligned, `valid` a multiple of 4 (fp32 elements)
+__device__ __forceinline__ uint4 red_ld16w(const uint8_t *p, uint32_t valid) {
+    const uint32_t *q = reinterpret_cast<const uint32_t *>(p);
+    uint32_t w[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (uint32_t i = 0; i < 4; ++i)
+        if (4u * i < valid) w[i] = q[i];
+    return make_uint4(w[0], w[1], w[2], w[3]);
+}
+__device__ __forceinline__ void red_st16w(uint8_t *p, uint4 v, uint32_t valid) {
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+    uint32_t *q = reinterpret_cast<uint32_t *>(p);
+#pragma unroll
+    for (uint32_t i = 0; i < 4; ++i)
+        if (4u * i < valid) q[i] = w[i];
+}
+
 // decode_fast's sink of the fused path (and the UNCP and idle waves' window step).  All fields but
 // `tid` and `dpre` are uniform over the workgroup.
-template <int NW>
-struct RedSink {
+//
+// WIDE instances also sum a destination with a widening code (red_wide(elem), a scalar branch taken
+// once per prefetch and once per window, outside the peer loop): the wire elements are 2 bytes, the
+// destination's fp32.  Nothing changes on the decode side: wave k stages the same window of
+// kRedWinGroups wire groups in its slice, and gbase, gc and osize stay in WIRE groups and bytes.  What
+// doubles is the destination: the window's 192 wire groups are 384 destination groups (6 KiB), the
+// destination ends at 2 osize bytes, and window `win` starts at destination group 2 (gbase + 192 win).
+//   - Destination group h of the window is wire bytes [8h, 8h + 8) of every peer's slice.  A lane
+//     takes the groups h = tid + q T (NPF = 3 / 2 / 1 of them at NW = 2 / 4 / 8), and per peer issues
+//     one ds_read_b64 at stage + k kRedSlice + 8h.
+//   - Banks: the lanes of a wave read consecutive 8-byte words, 512 contiguous bytes per instruction.
+//     The LDS serves a b64 read in passes of lanes that together cover a contiguous, 8-byte-aligned
+//     span no longer than the banks' 4-byte stride times their count, so no two lanes of a pass meet
+//     in a bank: the read runs at the width's own rate, whatever k (kRedSlice only moves the base).
+//   - Adds: four v_add_f32 per peer and group.  This object is built without the packed fp32 forms
+//     (build.py: DEC_ACC_FLAGS), so the 4-vector add below never becomes v_pk_add_f32; the
+//     disassembly of the wide instances shows v_add_f32 only.
+//   - Stores: one st16_nt of 16 consecutive destination bytes per lane where the group is whole and
+//     16-byte aligned; otherwise (a destination 4 or 12 bytes off, the last group of 4, 8 or 12
+//     bytes) dword loads and stores (red_ld16w / red_st16w) with `valid` from 2 osize, so no byte at or past 2 osize is touched.
+//     A wire window that ends on half a wire group (osize % 16 in 1..8) ends one destination group
+//     earlier: the bound is min(2 gc, ceil(2 osize / 16)).
+//   - BARRIERS: as for the narrow sink.  prefetch and window keep their place, two barriers per
+//     window, and every wave calls window once per window; the callers' trip counts come from the
+//     destination's WIRE group count alone (gc, or a tile's range), which the widening does not
+//     change, and the wide / narrow branch is on a scalar that every wave of the workgroup holds.
+template <int NW, bool WIDE>
+struct RedSinkT {
     static constexpr bool on = true;
-    static constexpr uint32_t T = 64u * NW;                       // lanes of the workgroup
-    static constexpr int NPF = (int)((kRedWinGroups + T - 1) / T);  // groups per lane and window
+    static constexpr uint32_t T = 64u * NW;                          // lanes of the workgroup
+    static constexpr int NPFN = (int)((kRedWinGroups + T - 1) / T);  // groups per lane and window
+    static constexpr int NPFW = (int)((2u * kRedWinGroups + T - 1) / T);  // ... of a wide destination
+    static constexpr int NPF = WIDE ? NPFW : NPFN;
     uint8_t *stage;  // the workgroup's staged windows; peer k's slice at k * kRedSlice
     uint8_t *mine;   // this wave's slice
     uint8_t *dst;
-    uint64_t osize;
-    uint32_t gc;     // the end of the walk: the destination's 16-byte groups (the last may be partial), or a tile's end
+    uint64_t osize;  // decoded (wire) bytes
+    uint32_t gc;     // the end of the walk: the decoded size's 16-byte groups (the last may be partial), or a tile's end
     uint32_t gbase;  // the first group of the walk (0, or a tile's first group): window `win` starts kRedWinGroups * win past it
     uint32_t n_peers, elem, tid;
     bool set, dal16;
@@ -138,39 +220,108 @@ struct RedSink {
 
     __device__ __forceinline__ bool whole(uint32_t g) const { return dal16 && 16ull * g + 16ull <= osize; }
 
+    // a wide destination: its bytes, the end of the walk in its groups, and whether group g is whole
+    __device__ __forceinline__ uint64_t wsize() const { return 2ull * osize; }
+    __device__ __forceinline__ uint32_t wend() const {
+        const uint32_t a = 2u * gc, b = (uint32_t)((wsize() + 15ull) / 16ull);  // (osize < 2^34: red_header)
+        return a < b ? a : b;
+    }
+    __device__ __forceinline__ bool wwhole(uint32_t g) const { return dal16 && 16ull * g + 16ull <= wsize(); }
+
     // the destination loads of window `win`, issued before its decode
     __device__ __forceinline__ void prefetch(uint32_t win) {
         if (set) return;
-#pragma unroll
-        for (int q = 0; q < NPF; ++q) {
-            const uint32_t j = tid + (uint32_t)q * T, g = gbase + win * kRedWinGroups + j;
-            if (j < kRedWinGroups && g < gc && whole(g)) dpre[q] = acc_ld16(dst + 16ull * g);
+        if constexpr (WIDE) {
+            if (red_wide(elem)) {
+                if constexpr (NPFW > 2) dpre[2] = prefetch_wide(win, 2u, dpre[2]);
+                if constexpr (NPFW > 1) dpre[1] = prefetch_wide(win, 1u, dpre[1]);
+                dpre[0] = prefetch_wide(win, 0u, dpre[0]);
+                return;
+            }
+        }
+        if constexpr (NPFN > 1) dpre[1] = prefetch_group(win, 1u, dpre[1]);
+        dpre[0] = prefetch_group(win, 0u, dpre[0]);
+    }
+
+    // The lane's groups are written out, last to first, on both walks, and a prefetch returns the
+    // group it keeps.  With loops, or with stores under the tests, hipcc 7.2 merged the tails of the
+    // two walks into stores through a pointer chosen between dpre's entries, which kept dpre in scratch
+    // in the instances where the walks differ in length; ending both on dpre[0] leaves nothing to choose.
+    static_assert(NPFN <= 2 && NPFW <= 3, "prefetch and window write the lane's groups out");
+    __device__ __forceinline__ uint4 prefetch_group(uint32_t win, uint32_t q, uint4 pre) const {
+        const uint32_t j = tid + q * T, g = gbase + win * kRedWinGroups + j;
+        return j < kRedWinGroups && g < gc && whole(g) ? acc_ld16(dst + 16ull * g) : pre;
+    }
+    __device__ __forceinline__ uint4 prefetch_wide(uint32_t win, uint32_t q, uint4 pre) const {
+        const uint32_t j = tid + q * T, g = 2u * (gbase + win * kRedWinGroups) + j;
+        return j < 2u * kRedWinGroups && g < wend() && wwhole(g) ? acc_ld16(dst + 16ull * g) : pre;
+    }
+
+    // the sums of window `win` into a wide destination (BF: the wire is bf16, else fp16): the lane's
+    // q-th group, `pre` its prefetched bytes
+    template <bool BF>
+    __device__ __forceinline__ void sum_wide_group(uint32_t win, uint32_t q, uint4 pre) {
+        const uint32_t j = tid + q * T, g = 2u * (gbase + win * kRedWinGroups) + j;
+        if (j < 2u * kRedWinGroups && g < wend()) {
+            uint8_t *p = dst + 16ull * g;
+            const bool wh = wwhole(g);
+            const uint64_t left = wsize() - 16ull * g;
+            const uint32_t valid = left >= 16ull ? 16u : (uint32_t)left;  // (4, 8 or 12 in the last group)
+            const uint2 *sv = reinterpret_cast<const uint2 *>(stage + 8u * j);
+            psy_f4 d = red_widen<BF>(sv[0]);
+            if (!set) {
+                uint4 b = pre;
+                if (!wh) b = red_ld16w(p, valid);
+                d = red_f4(b) + d;
+            }
+            for (uint32_t k = 1u; k < n_peers; ++k) d = d + red_widen<BF>(sv[k * (kRedSlice / 8u)]);
+            const uint4 o = make_uint4(__float_as_uint(d.x), __float_as_uint(d.y), __float_as_uint(d.z), __float_as_uint(d.w));
+            if (wh) st16_nt(p, o);
+            else red_st16w(p, o, valid);
+        }
+    }
+    template <bool BF>
+    __device__ __forceinline__ void sum_wide(uint32_t win) {
+        if constexpr (NPFW > 2) sum_wide_group<BF>(win, 2u, dpre[2]);
+        if constexpr (NPFW > 1) sum_wide_group<BF>(win, 1u, dpre[1]);
+        sum_wide_group<BF>(win, 0u, dpre[0]);
+    }
+
+    // the sums of window `win` in the destination's own type: the lane's q-th group
+    __device__ __forceinline__ void sum_group(uint32_t win, uint32_t q, uint4 pre) {
+        const uint32_t j = tid + q * T, g = gbase + win * kRedWinGroups + j;
+        if (j < kRedWinGroups && g < gc) {
+            uint8_t *p = dst + 16ull * g;
+            const bool wh = whole(g);
+            const uint64_t left = osize - 16ull * g;
+            const uint32_t valid = left >= 16ull ? 16u : (uint32_t)left;
+            const uint4 *sv = reinterpret_cast<const uint4 *>(stage + 16u * j);
+            uint4 d = sv[0];
+            if (!set) d = acc4(wh ? pre : red_ld16(p, valid), d, elem);
+            for (uint32_t k = 1u; k < n_peers; ++k) d = acc4(d, sv[k * (kRedSlice / 16u)], elem);
+            if (wh) st16_nt(p, d);
+            else red_st16(p, d, valid);
         }
     }
 
     // the end of window `win`: every wave of the workgroup calls this once per window
     __device__ __forceinline__ void window(uint32_t win) {
         __syncthreads();  // A: every peer's slice of this window is staged
-#pragma unroll
-        for (int q = 0; q < NPF; ++q) {
-            const uint32_t j = tid + (uint32_t)q * T, g = gbase + win * kRedWinGroups + j;
-            if (j < kRedWinGroups && g < gc) {
-                uint8_t *p = dst + 16ull * g;
-                const bool wh = whole(g);
-                const uint64_t left = osize - 16ull * g;
-                const uint32_t valid = left >= 16ull ? 16u : (uint32_t)left;
-                const uint4 *sv = reinterpret_cast<const uint4 *>(stage + 16u * j);
-                uint4 d = sv[0];
-                if (!set) d = acc4(wh ? dpre[q] : red_ld16(p, valid), d, elem);
-                for (uint32_t k = 1u; k < n_peers; ++k) d = acc4(d, sv[k * (kRedSlice / 16u)], elem);
-                if (wh) st16_nt(p, d);
-                else red_st16(p, d, valid);
-            }
+        bool done = false;
+        if constexpr (WIDE) {
+            if (elem == kElemF32FromBF16) sum_wide<true>(win), done = true;
+            else if (elem == kElemF32FromF16) sum_wide<false>(win), done = true;
+        }
+        if (!done) {
+            if constexpr (NPFN > 1) sum_group(win, 1u, dpre[1]);
+            sum_group(win, 0u, dpre[0]);
         }
         __syncthreads();  // B: the slices may be written again
         prefetch(win + 1u);
     }
 };
+template <int NW>
+using RedSink = RedSinkT<NW, false>;
 
 // What every wave concludes from the peers' records (the same code over the same LDS words)
 struct RedVerdict {
@@ -202,11 +353,18 @@ __device__ __forceinline__ RedVerdict red_verdict(const uint32_t *rec, uint32_t 
 // element alignment and size: acc_status); (kind, status, decoded size) go to the LDS record rec[4 w ..]
 // and the status to peer_status.  hdrc: kHdrCache bytes of the wave's own LDS.  Shared by the
 // one-workgroup kernel and the tiled form's prep pass, so both refuse and accept the same blobs.
+//
+// WIDE (the instances that take the widening codes; every other instance answers them TDT_E_ARG as any
+// unknown code): under a widening code the decoded size w is the wire's and the destination holds 2 w
+// bytes of fp32, so the capacity is held against 2 w, the destination must be 4-byte aligned and w
+// even, and w < 2^34 keeps the destination's group indices in 32 bits.  The record's size stays w:
+// TDT_E_MISMATCH is decided on decoded sizes.
 struct RedHead {
     FastHdr H;
     const uint8_t *blob;
     uint64_t len;
 };
+template <bool WIDE>
 __device__ __forceinline__ RedHead red_header(const ReduceArgs &a, uint32_t msg, uint32_t w, uint32_t elem, uint8_t *dst,
                                               uint64_t cap, uint8_t *hdrc, uint32_t *rec) {
     const uint32_t lane = (uint32_t)lane_id();
@@ -241,8 +399,13 @@ __device__ __forceinline__ RedHead red_header(const ReduceArgs &a, uint32_t msg,
         st = blob_check(rd32, len, uncp, osize);
     }
     st = (uint32_t)__builtin_amdgcn_readfirstlane((int)st);
+    const bool wide = WIDE && red_wide(elem);  // (uniform)
     if (st == ST_DEFER) {  // a generic word size: no accumulate form
-        st = elem > kElemMax || elem == kElemStore ? (uint32_t)ST_ARG : (uint32_t)ST_UNSUPPORTED;
+        st = !wide && (elem > kElemMax || elem == kElemStore) ? (uint32_t)ST_ARG : (uint32_t)ST_UNSUPPORTED;
+    } else if (wide) {
+        if (st == ST_OK && osize > (cap >> 1)) st = ST_CAPACITY;  // (2 osize > cap)
+        if (st == ST_OK && (osize >> 34) != 0) st = ST_UNSUPPORTED;
+        if (st == ST_OK && ((((uintptr_t)dst & 3) | (osize & 1)) != 0)) st = ST_ELEMENT;
     } else {
         if (st == ST_OK && osize > cap) st = ST_CAPACITY;
         if (st == ST_OK && (osize >> 35) != 0) st = ST_UNSUPPORTED;  // (group indices are 32 bits wide)
@@ -259,8 +422,12 @@ __device__ __forceinline__ RedHead red_header(const ReduceArgs &a, uint32_t msg,
     return RedHead{H, blob, len};
 }
 
-template <int NW>
-__global__ __launch_bounds__(64 * NW) void tdt_decode_reduce_kernel(ReduceArgs a) {
+// The one-workgroup kernel's body.  WIDE: an instance that also sums destinations with a widening
+// code; its sink carries both sums, and a valid wide destination with a peer off the fast path is
+// refused (TDT_E_UNSUPPORTED: the serial kernel sums through decode_one's ACC stores, which have no
+// widening form) where a narrow one is left to the serial kernel.
+template <int NW, bool WIDE>
+__device__ __forceinline__ void red_one_workgroup(const ReduceArgs &a) {
     using Lay = RedLayout<NW>;
     using Dec = DecLayoutT<kRedWR>;
     __shared__ __attribute__((aligned(16))) uint8_t smem[Lay::BYTES];
@@ -279,15 +446,17 @@ __global__ __launch_bounds__(64 * NW) void tdt_decode_reduce_kernel(ReduceArgs a
 
     // ------------------------------------------------ header: wave k checks peer k's blob
     RedHead P{};
-    if (w < n_peers) P = red_header(a, msg, w, elem, dst, cap, dec + Dec::OFF_HDR, rec);
+    if (w < n_peers) P = red_header<WIDE>(a, msg, w, elem, dst, cap, dec + Dec::OFF_HDR, rec);
     const FastHdr &H = P.H;
     const uint8_t *const blob = P.blob, *const blim = P.blob + P.len;
     __syncthreads();  // header barrier: every wave, once
-    const RedVerdict V = red_verdict(rec, n_peers);
+    const bool wide = WIDE && red_wide(elem);
+    RedVerdict V = red_verdict(rec, n_peers);
+    if (wide && V.st == ST_OK && !V.fused) V.st = ST_UNSUPPORTED;
     if (w == 0 && lane == 0) {
         // (a valid destination with a peer off the fast path: left to the serial kernel that follows)
         a.status[msg] = (int32_t)(V.st == ST_OK && !V.fused ? ST_RED_SERIAL : V.st);
-        if (a.out_len) a.out_len[msg] = V.st == ST_OK ? V.osize : 0;
+        if (a.out_len) a.out_len[msg] = V.st == ST_OK ? (wide ? 2ull * V.osize : V.osize) : 0;
     }
     if (V.st != ST_OK || !V.fused) return;  // refused: nothing of the destination is read or written
 
@@ -295,7 +464,8 @@ __global__ __launch_bounds__(64 * NW) void tdt_decode_reduce_kernel(ReduceArgs a
     const uint64_t osize = V.osize;
     const uint32_t gc = (uint32_t)((osize + 15) / 16);
     const uint32_t nwin = (gc + kRedWinGroups - 1) / kRedWinGroups;
-    RedSink<NW> S;
+    using Sink = RedSinkT<NW, WIDE>;
+    Sink S;
     S.stage = smem + Lay::OFF_STAGE;
     S.mine = S.stage + w * kRedSlice;
     S.dst = dst;
@@ -308,14 +478,14 @@ __global__ __launch_bounds__(64 * NW) void tdt_decode_reduce_kernel(ReduceArgs a
     S.set = set;
     S.dal16 = ((uintptr_t)dst & 15) == 0;
 #pragma unroll
-    for (int q = 0; q < RedSink<NW>::NPF; ++q) S.dpre[q] = make_uint4(0, 0, 0, 0);
+    for (int q = 0; q < Sink::NPF; ++q) S.dpre[q] = make_uint4(0, 0, 0, 0);
     S.prefetch(0);
     const uint32_t kind = (uint32_t)__builtin_amdgcn_readfirstlane((int)(w < n_peers ? H.kind : 0u));
     if (kind == 2u) {
         // window loop inside: gwin = 0, 64 WR, ... < gc, S.window(win) at the end of each
         const uint64_t wbytes = (uint64_t)(H.orig / H.ws) * H.ws;
-        decode_fast<kRedWR, false, RedSink<NW>>(H, dec, blob, blim, nullptr, gc, wbytes, 0, gc, nullptr, nullptr, nullptr,
-                                                0u, 0u, &S);
+        decode_fast<kRedWR, false, Sink>(H, dec, blob, blim, nullptr, gc, wbytes, 0, gc, nullptr, nullptr, nullptr, 0u, 0u,
+                                         &S);
     } else if (kind == 1u) {
         for (uint32_t win = 0; win < nwin; ++win) {
 #pragma unroll
@@ -333,6 +503,15 @@ __global__ __launch_bounds__(64 * NW) void tdt_decode_reduce_kernel(ReduceArgs a
     } else {
         for (uint32_t win = 0; win < nwin; ++win) S.window(win);  // a wave without a peer
     }
+}
+template <int NW>
+__global__ __launch_bounds__(64 * NW) void tdt_decode_reduce_kernel(ReduceArgs a) {
+    red_one_workgroup<NW, false>(a);
+}
+// (launched when the call's codes may widen: a widening `elem`, or codes per destination)
+template <int NW>
+__global__ __launch_bounds__(64 * NW) void tdt_decode_reduce_wide_kernel(ReduceArgs a) {
+    red_one_workgroup<NW, true>(a);
 }
 
 // The serial path: the destinations the kernel above marked ST_RED_SERIAL (every blob valid, the
@@ -387,6 +566,9 @@ __global__ __launch_bounds__(64) void tdt_decode_reduce_serial_kernel(ReduceArgs
 #define PSY_DEC_REDUCE_INSTANCES(X)           \
     X(psy::tdt_decode_reduce_kernel<2>)       \
     X(psy::tdt_decode_reduce_kernel<4>)       \
-    X(psy::tdt_decode_reduce_kernel<8>)
+    X(psy::tdt_decode_reduce_kernel<8>)       \
+    X(psy::tdt_decode_reduce_wide_kernel<2>)  \
+    X(psy::tdt_decode_reduce_wide_kernel<4>)  \
+    X(psy::tdt_decode_reduce_wide_kernel<8>)
 
 }  // namespace psy

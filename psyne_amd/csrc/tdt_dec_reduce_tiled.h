@@ -43,6 +43,17 @@
 // A tile is kRedTileWin whole windows, so no window straddles two tiles and only a tensor's last
 // window is partial; it starts a multiple of 16 bytes into an element-aligned destination, so it
 // holds whole elements, and two tiles never share a group.
+//
+// WIDE destinations (a widening code: 2-byte wire elements summed into fp32, tdt_dec_reduce.h).  The
+// sum, plan, block and scan passes work in decoded wire bytes and are the same: the threshold is held
+// against decoded bytes and a destination claims ceil(w / kRedTileBytes) tiles.  A tile is still
+// kRedTileWin wire windows; the wide sink writes 2 kRedTileBytes = 67,584 destination bytes for it,
+// from destination group 2 g_lo to min(2 g_hi, the destination's end).  The record keeps the decoded
+// size; prep reports 2 w as the length.  Prep always takes the widening header checks (red_header<true>:
+// a narrow call cannot hold a widening code, so it decides as before), and a wide destination with a peer
+// off the fast path is not tiled: its mark is cleared and the one-workgroup kernel refuses it.  The
+// tile kernel has a second set of instances (tdt_decode_reduce_tile_wide_kernel) launched when the
+// call's codes may widen, so the narrow instances keep their registers.
 #pragma once
 #include "tdt_dec_reduce.h"
 #include "tdt_red_tiles.h"
@@ -262,7 +273,7 @@ __global__ __launch_bounds__(64 * NW) void tdt_decode_reduce_prep_kernel(RedTile
             (uint32_t)__builtin_amdgcn_readfirstlane((int)(a.elem_codes ? (uint32_t)a.elem_codes[msg] : a.elem));
         uint8_t *dst = reinterpret_cast<uint8_t *>(a.outs[msg]);
         RedHead P{};
-        if (w < n_peers) P = red_header(a, msg, w, elem, dst, a.out_cap[msg], hdrs[w], rec);
+        if (w < n_peers) P = red_header<true>(a, msg, w, elem, dst, a.out_cap[msg], hdrs[w], rec);
         if (lane == 0 && w < kRedMaxPeers) {
             const bool fast = w < n_peers && P.H.kind == 2u;
             s_nb[2 * w] = fast ? red_nblocks(P.H.np[0]) : 0u;
@@ -297,7 +308,7 @@ __global__ __launch_bounds__(64 * NW) void tdt_decode_reduce_prep_kernel(RedTile
                 m->dst = (uint64_t)(uintptr_t)dst;
                 m->osize = V.osize;
                 a.status[msg] = (int32_t)ST_OK;
-                if (a.out_len) a.out_len[msg] = V.osize;
+                if (a.out_len) a.out_len[msg] = red_wide(elem) ? 2ull * V.osize : V.osize;
                 atomicAdd(p.cnt + RC_TILED, 1ull);
                 atomicAdd(p.cnt + RC_TILED_TILES, (unsigned long long)ntiles);
             } else {
@@ -311,8 +322,8 @@ __global__ __launch_bounds__(64 * NW) void tdt_decode_reduce_prep_kernel(RedTile
 }
 
 // Tile pass: a workgroup of NW waves per tile entry (a grid striding over the device-side count).
-template <int NW>
-__global__ __launch_bounds__(64 * NW) void tdt_decode_reduce_tile_kernel(RedTiledArgs p) {
+template <int NW, bool WIDE>
+__device__ __forceinline__ void red_tiles(const RedTiledArgs &p) {
     using Lay = RedLayout<NW>;
     __shared__ __attribute__((aligned(16))) uint8_t smem[Lay::BYTES];
     const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -334,7 +345,8 @@ __global__ __launch_bounds__(64 * NW) void tdt_decode_reduce_tile_kernel(RedTile
         const uint32_t nwin = (g_hi - g_lo + kRedWinGroups - 1) / kRedWinGroups;
         const uint32_t n_peers = (uint32_t)__builtin_amdgcn_readfirstlane((int)m->n_peers);
         uint8_t *dst = reinterpret_cast<uint8_t *>(m->dst);
-        RedSink<NW> S;
+        using Sink = RedSinkT<NW, WIDE>;
+        Sink S;
         S.stage = smem + Lay::OFF_STAGE;
         S.mine = S.stage + w * kRedSlice;
         S.dst = dst;
@@ -347,7 +359,7 @@ __global__ __launch_bounds__(64 * NW) void tdt_decode_reduce_tile_kernel(RedTile
         S.set = set;
         S.dal16 = ((uintptr_t)dst & 15) == 0;
 #pragma unroll
-        for (int q = 0; q < RedSink<NW>::NPF; ++q) S.dpre[q] = make_uint4(0, 0, 0, 0);
+        for (int q = 0; q < Sink::NPF; ++q) S.dpre[q] = make_uint4(0, 0, 0, 0);
         S.prefetch(0);
         const RedPeer &P = m->p[w < n_peers ? w : 0u];
         const uint32_t kind = (uint32_t)__builtin_amdgcn_readfirstlane((int)(w < n_peers ? P.H.kind : 0u));
@@ -368,8 +380,7 @@ __global__ __launch_bounds__(64 * NW) void tdt_decode_reduce_tile_kernel(RedTile
                 }
             }
             // window loop inside: gwin = g_lo, g_lo + 64 WR, ... < g_hi, S.window(win) at the end of each
-            decode_fast<kRedWR, false, RedSink<NW>>(H, dec, blob, blim, nullptr, gc, wbytes, g_lo, g_hi, b0, s0, nullptr, 0u,
-                                                    0u, &S);
+            decode_fast<kRedWR, false, Sink>(H, dec, blob, blim, nullptr, gc, wbytes, g_lo, g_hi, b0, s0, nullptr, 0u, 0u, &S);
         } else if (kind == 1u) {
             for (uint32_t win = 0; win < nwin; ++win) {
 #pragma unroll
@@ -389,6 +400,14 @@ __global__ __launch_bounds__(64 * NW) void tdt_decode_reduce_tile_kernel(RedTile
         }
     }
 }
+template <int NW>
+__global__ __launch_bounds__(64 * NW) void tdt_decode_reduce_tile_kernel(RedTiledArgs p) {
+    red_tiles<NW, false>(p);
+}
+template <int NW>
+__global__ __launch_bounds__(64 * NW) void tdt_decode_reduce_tile_wide_kernel(RedTiledArgs p) {
+    red_tiles<NW, true>(p);
+}
 
 #define PSY_DEC_REDUCE_TILED_INSTANCES(X)          \
     X(psy::tdt_decode_reduce_prep_kernel<2>)       \
@@ -396,6 +415,9 @@ __global__ __launch_bounds__(64 * NW) void tdt_decode_reduce_tile_kernel(RedTile
     X(psy::tdt_decode_reduce_prep_kernel<8>)       \
     X(psy::tdt_decode_reduce_tile_kernel<2>)       \
     X(psy::tdt_decode_reduce_tile_kernel<4>)       \
-    X(psy::tdt_decode_reduce_tile_kernel<8>)
+    X(psy::tdt_decode_reduce_tile_kernel<8>)       \
+    X(psy::tdt_decode_reduce_tile_wide_kernel<2>)  \
+    X(psy::tdt_decode_reduce_tile_wide_kernel<4>)  \
+    X(psy::tdt_decode_reduce_tile_wide_kernel<8>)
 
 }  // namespace psy

@@ -411,7 +411,9 @@ class TdtCodec:
         from peer k is in_lengths[k * n + i] bytes at address ptrs[k * n + i] (n = out_ptrs.numel();
         peer k's slice is what decode_accumulate_v takes), added in ascending peer order as elements
         of code elems[i] (None: `elem`, TDT_ELEM_F32 by default) — the bits of n_peers
-        decode_accumulate_v calls.  set=True writes the peers' sum alone and never reads the
+        decode_accumulate_v calls.  TDT_ELEM_F32_FROM_BF16 / TDT_ELEM_F32_FROM_F16 take the blobs as
+        bfloat16 / float16 elements and add them, widened exactly, into a float32 destination of twice
+        the decoded bytes (out_caps and lengths are in destination bytes).  set=True writes the peers' sum alone and never reads the
         destination.  Every blob of a destination is checked before a byte of it is written: one
         whose status is not 0 is untouched.  peer_status (an int32 tensor of n_peers * n entries)
         receives each blob's own check.  Returns (lengths, status)."""
@@ -731,17 +733,30 @@ class TdtCodec:
         return self.decode_accumulate_v(ptrs, in_lengths, d[:n], d[n:2 * n], elems=d[2 * n:].view(torch.uint8),
                                         stream=stream)
 
-    def decode_reduce_tensors(self, peers, outs, set=False, stream=None):
+    def decode_reduce_tensors(self, peers, outs, set=False, stream=None, wire_dtype=None):
         """outs[i] += the sum over peers of their tensor i (set=True: outs[i] = that sum), in one pass
         over each destination (decode_reduce_v).  peers: one (blobs, offsets, in_lengths) triple per
         peer, each as decode_tensors takes it; outs: float32, float16, bfloat16 or float64 tensors,
-        each summed in its own type, in ascending peer order.  Returns (lengths, status)."""
+        each summed in its own type, in ascending peer order.  Returns (lengths, status).
+
+        wire_dtype=torch.bfloat16 or torch.float16: the blobs hold tensors of that type and every
+        outs[i] is a float32 tensor of as many elements, which the widened elements are added to in
+        fp32 (mixed-precision gradients: half the wire, fp32 main gradients)."""
         import torch
-        from ._lib import TDT_ELEM_BF16, TDT_ELEM_F16, TDT_ELEM_F32, TDT_ELEM_F64
-        codes = {torch.float32: TDT_ELEM_F32, torch.float16: TDT_ELEM_F16, torch.bfloat16: TDT_ELEM_BF16,
-                 torch.float64: TDT_ELEM_F64}
+        from ._lib import (TDT_ELEM_BF16, TDT_ELEM_F16, TDT_ELEM_F32, TDT_ELEM_F32_FROM_BF16, TDT_ELEM_F32_FROM_F16,
+                           TDT_ELEM_F64)
+        if wire_dtype is None:
+            codes = {torch.float32: TDT_ELEM_F32, torch.float16: TDT_ELEM_F16, torch.bfloat16: TDT_ELEM_BF16,
+                     torch.float64: TDT_ELEM_F64}
+        elif wire_dtype in (torch.bfloat16, torch.float16):
+            codes = {torch.float32: TDT_ELEM_F32_FROM_BF16 if wire_dtype == torch.bfloat16 else TDT_ELEM_F32_FROM_F16}
+        else:
+            raise ValueError("wire_dtype is torch.bfloat16, torch.float16 or None, not %s" % wire_dtype)
         for t in outs:
             if t.dtype not in codes:
+                if wire_dtype is not None:
+                    raise ValueError("decode_reduce_tensors widens %s blobs into float32 tensors, not %s"
+                                     % (wire_dtype, t.dtype))
                 raise ValueError("decode_reduce_tensors sums float32, float16, bfloat16 and float64 tensors, not %s"
                                  % t.dtype)
         optrs, osizes = self._tensor_table(outs)
