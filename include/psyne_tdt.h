@@ -102,6 +102,9 @@ extern "C" {
  * 2-byte elements, the destination fp32.  tdt_decode_accumulate_v answers them TDT_E_ARG. */
 #define TDT_ELEM_F32_FROM_BF16 0x31
 #define TDT_ELEM_F32_FROM_F16 0x21
+/* Narrowing codes, tdt_encode_narrow_v only (the same composition): the source is fp32, the wire 2-byte elements. */
+#define TDT_ELEM_BF16_FROM_F32 0x13
+#define TDT_ELEM_F16_FROM_F32 0x12
 
 /* TDTConfig (:31-43).  Fields the reference declares but never reads
  * (auto_detect_clusters, max_clusters, enable_simd) are omitted. */
@@ -304,6 +307,37 @@ int tdt_decode_reduce_v(tdt_ctx *ctx, const uint8_t *const *d_blobs, const uint6
                         uint32_t n_peers, uint8_t *const *d_outs, const uint64_t *d_out_cap, const uint8_t *d_elem,
                         int elem, uint32_t flags, uint64_t *d_out_len, int32_t *d_status, int32_t *d_peer_status,
                         void *hip_stream);
+/* ENCODE-NARROW — the sender's side of the wide destinations above: fp32 tensors encoded as the
+ * width-2 blobs of their bf16 / fp16 narrowing, in one pass.  Each tensor is read, narrowed in
+ * registers and encoded; no half-precision copy of it exists in device memory.
+ *   Conventions of tdt_encode_batch_v: every array in device memory with n_msgs entries, d_elem (NULL:
+ *     `elem` for every message) one TDT_ELEM_BF16_FROM_F32 / TDT_ELEM_F16_FROM_F32 code per message;
+ *     asynchronous on the caller's stream, nothing read back, n_msgs == 0 returns TDT_OK and touches
+ *     nothing.  No workspace, no plan, no lists: one launch of n_msgs workgroups, capturable from the
+ *     first call.  A null array with n_msgs > 0 and a bad `elem` with d_elem == NULL return TDT_E_ARG.
+ *   d_sizes[i] is the SOURCE size in bytes; the wire message has w = d_sizes[i] / 2 bytes.
+ *   The contract: blob i, d_out_len[i] and d_status[i] are byte for byte what tdt_encode_batch_v gives
+ *     on a context of word size 2 with the same metrics, config and TDT_OPT_RAW_FALLBACK setting for the
+ *     w narrowed bytes and the same capacity, whatever this context's own word size: the routing
+ *     decision (should_transform and the size guard) taken on w, the UNCP form (marker + narrowed
+ *     bytes), TDT_E_CAPACITY with length 0, and under TDT_OPT_RAW_FALLBACK the UNCP form whenever the
+ *     TDT blob would exceed w + 4 (the blob's length is counted in the same launch, before the first
+ *     store).  TDT_STAT_RAW_FALLBACKS is not updated by this call, as the size calls do not update it.
+ *   Further statuses, each decided before the first store, the blob untouched and its length 0:
+ *     TDT_E_ELEMENT when the source is not 4-byte aligned or d_sizes[i] % 4 != 0; TDT_E_ARG for a code
+ *     other than the two (per message from d_elem).  No byte outside [d_blobs[i], d_blobs[i] +
+ *     d_blob_cap[i]) is written; blob pointers may have any alignment; inputs may alias each other.
+ *   The narrowing rule, u the fp32 bit pattern (integers: the casts of other libraries disagree on NaNs):
+ *     bf16, not NaN   (u + 0x7FFF + ((u >> 16) & 1)) >> 16 — round to nearest even, overflow reaches
+ *                     infinity by the carry
+ *     bf16, NaN       ((u & 0x7FFFFFFF) > 0x7F800000)  (u >> 16) | 0x0040
+ *     fp16, not NaN   IEEE round to nearest even; subnormal results are kept, not flushed; values past
+ *                     the largest finite fp16 become infinity
+ *     fp16, NaN       sign | 0x7E00 | ((u >> 13) & 0x3FF)
+ *   A tensor of up to 16,384 elements is read once; a longer one three times, on its one workgroup. */
+int tdt_encode_narrow_v(tdt_ctx *ctx, const uint8_t *const *d_msgs, const uint64_t *d_sizes, uint32_t n_msgs,
+                        const uint8_t *d_elem, int elem, uint8_t *const *d_blobs, const uint64_t *d_blob_cap,
+                        uint64_t *d_out_len, int32_t *d_status, void *hip_stream);
 /* MIXED WORD SIZES — tdt_encode_batch_v with one record width per message (a mixed-precision
  * gradient list: bf16 / fp16 tensors at width 2 beside fp32 ones at 4 and fp64 / int64 ones at 8).
  * d_word_size[i] (device memory, n_msgs entries) is message i's width; the context's own word_size

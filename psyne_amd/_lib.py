@@ -19,6 +19,8 @@ TDT_E_ELEMENT = 13  # decode-accumulate: destination not aligned to its element,
 TDT_ELEM_STORE, TDT_ELEM_F32, TDT_ELEM_F16, TDT_ELEM_BF16, TDT_ELEM_F64 = 0, 1, 2, 3, 4
 # tdt_decode_reduce_v only: bf16 / fp16 blobs summed into a float32 destination (destination | wire << 4)
 TDT_ELEM_F32_FROM_BF16, TDT_ELEM_F32_FROM_F16 = 0x31, 0x21
+# tdt_encode_narrow_v only: float32 tensors encoded as their bf16 / fp16 narrowing
+TDT_ELEM_BF16_FROM_F32, TDT_ELEM_F16_FROM_F32 = 0x13, 0x12
 TDT_E_MISMATCH = 14  # decode-reduce: the peers' blobs of one destination decode to different sizes
 TDT_REDUCE_MAX_PEERS = 8
 TDT_REDUCE_SET = 1  # tdt_decode_reduce_v flag: dst = sum of the peers (default: dst = dst + sum)
@@ -89,6 +91,7 @@ SIGNATURES = {
     "tdt_decode_accumulate_v": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp]),
     "tdt_decode_reduce_v": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, C.c_int, C.c_uint32, _vp, _vp,
                                       _vp, _vp]),
+    "tdt_encode_narrow_v": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "tdt_decoded_sizes_v": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp]),
     "tdt_encode_slots": (C.c_int, [_vp, _vp, C.c_uint32, _vp, _vp]),
     "tdt_decode_slots": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp]),

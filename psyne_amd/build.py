@@ -32,8 +32,9 @@ DEC_ACC_SRC = CSRC / "tdt_dec_acc.hip"  # the decode-accumulate instances (tdt_d
 # (its fp32 adds stay scalar v_add_f32: no packed fp32 forms in this object)
 DEC_ACC_FLAGS = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 DEC_REDUCE_SRC = CSRC / "tdt_dec_reduce.hip"  # the decode-reduce kernels (tdt_decode_reduce_v); scalar fp32 adds as well
+ENC_NARROW_SRC = CSRC / "tdt_enc_narrow.hip"  # the encode-narrow kernel (tdt_encode_narrow_v); no packed fp32 forms either
 # every source and header under csrc/ (tdt_api.hip includes the headers, directly or not)
-DEPS = SOURCES + [DEC_ACC_SRC, DEC_REDUCE_SRC, ENC_WS_SRC, ENC_SIZES_WS_SRC, ENC_MAPPED_WS_SRC] + sorted(CSRC.glob("*.h")) + [ROOT / "include" / "psyne_tdt.h"]
+DEPS = SOURCES + [DEC_ACC_SRC, DEC_REDUCE_SRC, ENC_NARROW_SRC, ENC_WS_SRC, ENC_SIZES_WS_SRC, ENC_MAPPED_WS_SRC] + sorted(CSRC.glob("*.h")) + [ROOT / "include" / "psyne_tdt.h"]
 OBJ_DIR = PKG / "build"
 
 
@@ -45,7 +46,7 @@ def needs_build() -> bool:
 
 
 def build(force: bool = False, verbose: bool = False) -> pathlib.Path:
-    """Compile tdt_api.hip, tdt_anyws.hip, tdt_pack.hip, tdt_rawfb.hip, tdt_dec_acc.hip, tdt_dec_reduce.hip and one tdt_enc_ws.hip, tdt_enc_sizes_ws.hip and
+    """Compile tdt_api.hip, tdt_anyws.hip, tdt_pack.hip, tdt_rawfb.hip, tdt_dec_acc.hip, tdt_dec_reduce.hip, tdt_enc_narrow.hip and one tdt_enc_ws.hip, tdt_enc_sizes_ws.hip and
     tdt_enc_mapped_ws.hip object per word size in parallel (the encode kernels dominate the compile time), then
     link libpsyne_tdt.so."""
     if force or needs_build():
@@ -57,6 +58,8 @@ def build(force: bool = False, verbose: bool = False) -> pathlib.Path:
         jobs.append((base + DEC_ACC_FLAGS + ["-c", str(DEC_ACC_SRC), "-o", str(o)], o))
         o = OBJ_DIR / (DEC_REDUCE_SRC.stem + ".o")
         jobs.append((base + DEC_ACC_FLAGS + ["-c", str(DEC_REDUCE_SRC), "-o", str(o)], o))
+        o = OBJ_DIR / (ENC_NARROW_SRC.stem + ".o")
+        jobs.append((base + DEC_ACC_FLAGS + ["-c", str(ENC_NARROW_SRC), "-o", str(o)], o))
         for ws in WORD_SIZES:
             o = OBJ_DIR / f"tdt_enc_ws{ws}.o"
             jobs.append((base + [f"-DPSY_INST_WS={ws}", "-c", str(ENC_WS_SRC), "-o", str(o)], o))

@@ -18,6 +18,7 @@
 #include "tdt_copy.h"
 #include "tdt_decode.h"
 #include "tdt_encode.h"
+#include "tdt_entropy.h"
 
 // The mapping decision is bit-exact only if nothing below is contracted (tdt_log2.h).
 #pragma clang fp contract(off)
@@ -199,28 +200,7 @@ __device__ __forceinline__ void any_chunk(const uint8_t *base, const uint8_t *li
     if (tid == 0 && Lc) s_buf[15] = (uint8_t)c.lastb;  // (only lane 0 reads it)
 }
 
-// The entropy of one byte position (calculate_entropy :470-480): the exact chain only.  Lane l of
-// a wave holds the counts of bins l, l + 64, l + 128, l + 192 and computes their (-prob, log2 prob)
-// (0, 0 for an empty bin: fma(0, 0, e) == e for the non-negative running sum), then every lane
-// runs the chain over the bins in order 0..255.
-__device__ __forceinline__ double any_entropy(const uint32_t (&c)[4], double total) {
-    double np[4], L[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        np[k] = 0.0;
-        L[k] = 0.0;
-        if (c[k]) {
-            const double prob = (double)c[k] / total;
-            L[k] = psy_log2_glibc(prob, c_log2_tab, c_log2_tab2);
-            np[k] = -prob;
-        }
-    }
-    double e = 0.0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-        for (int l = 0; l < 64; ++l) e = __builtin_fma(readlane_f64(np[k], l), readlane_f64(L[k], l), e);
-    return e;
-}
+// (the entropy of one byte position, any_entropy: tdt_entropy.h)
 
 // ---------------------------------------------------------------------------------------
 // Encode.  HP: histogram positions held in LDS (>= ws; 1 for MODE_MAPPED, which has none).

@@ -26,6 +26,7 @@
 #include "tdt_decode.h"
 #include "tdt_encode.h"
 #include "tdt_enc_lmap.h"
+#include "tdt_enc_narrow.h"
 #include "tdt_grow.h"
 #if defined(PSY_FAST_BUILD) || (defined(PSY_PROF) && PSY_PROF) || defined(PSY_SINGLE_TU)
 #define PSY_DEC_REDUCE_TU 1  // (diagnostic single-file builds: the decode-reduce kernels are defined here)
@@ -3512,6 +3513,42 @@ int tdt_decode_reduce_v(tdt_ctx *ctx, const uint8_t *const *d_blobs, const uint6
     hipLaunchKernelGGL(psy::tdt_decode_reduce_serial_kernel, dim3(sg < 1024u ? sg : 1024u), dim3(64), 0, s, a);
     HIPCHK(hipGetLastError());
     return TDT_OK;
+}
+
+int tdt_encode_narrow_v(tdt_ctx *ctx, const uint8_t *const *d_msgs, const uint64_t *d_sizes, uint32_t n_msgs,
+                        const uint8_t *d_elem, int elem, uint8_t *const *d_blobs, const uint64_t *d_blob_cap,
+                        uint64_t *d_out_len, int32_t *d_status, void *stream) {
+    if (!ctx) return set_err(TDT_E_ARG, "null context");
+    if (!d_elem && elem != TDT_ELEM_BF16_FROM_F32 && elem != TDT_ELEM_F16_FROM_F32)
+        return set_err(TDT_E_ARG, "no narrowing element code");
+    if (n_msgs == 0) return TDT_OK;
+    if (!(d_msgs && d_sizes && d_blobs && d_blob_cap && d_out_len && d_status))
+        return set_err(TDT_E_ARG, "null pointer, size, length or status array");
+#if PSY_HAVE_ANYWS
+    HIPCHK(hipSetDevice(ctx->device));
+    psy::NarrowArgs a{};
+    a.msgs = reinterpret_cast<const uint64_t *>(d_msgs);
+    a.sizes = d_sizes;
+    a.n_msgs = n_msgs;
+    a.elem_codes = d_elem;
+    a.elem = (uint32_t)elem;
+    a.blobs = reinterpret_cast<const uint64_t *>(d_blobs);
+    a.blob_cap = d_blob_cap;
+    a.out_len = d_out_len;
+    a.status = d_status;
+    std::lock_guard<std::mutex> g(ctx->mu);  // (the metrics, the config and the option as one call sees them)
+    a.min_tensor = ctx->cfg.min_tensor_size;
+    a.policy_on = policy_on(ctx) ? 1 : 0;
+    a.raw_fallback = ctx->raw_fallback ? 1 : 0;
+    // one launch on the caller's stream: no workspace, no plan, no lists (the blob's length is counted
+    // in the kernel, so the raw fallback needs no second pass and TDT_STAT_RAW_FALLBACKS is not updated)
+    if (const int e = psy::launch_encode_narrow(a, (hipStream_t)stream))
+        return set_err(TDT_E_HIP, std::string("encode-narrow launch: ") + hipGetErrorString((hipError_t)e));
+    return TDT_OK;
+#else
+    (void)stream;
+    return set_err(TDT_E_UNSUPPORTED, "this build holds no encode-narrow kernel");
+#endif
 }
 
 int tdt_decoded_sizes_v(tdt_ctx *ctx, const uint8_t *const *d_blobs, const uint64_t *d_blob_len, uint32_t n_msgs,

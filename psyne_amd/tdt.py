@@ -338,6 +338,27 @@ class TdtCodec:
                                            _ptr(lengths), _ptr(status), self._stream(stream)))
         return lengths, status
 
+    def encode_narrow_v(self, ptrs, sizes, out_ptrs, out_caps, elems=None, elem=_lib.TDT_ELEM_BF16_FROM_F32, lengths=None,
+                        status=None, stream=None):
+        """encode_v of float32 messages narrowed on the way: message i = sizes[i] bytes of float32 at
+        address ptrs[i] is encoded as the width-2 blob of its bfloat16 / float16 narrowing (code
+        elems[i], a uint8 tensor on the GPU of TDT_ELEM_BF16_FROM_F32 / TDT_ELEM_F16_FROM_F32 values;
+        None: `elem` for every message) into out_caps[i] bytes at out_ptrs[i] — what a codec of
+        word_size 2 gives for the sizes[i] / 2 narrowed bytes, raw fallback included, in one launch and
+        without a half-precision copy.  Returns (lengths, status)."""
+        import torch
+        n = sizes.numel()
+        if elems is not None and (elems.dtype != torch.uint8 or elems.numel() < n):
+            raise ValueError("elems must be a uint8 tensor of one code per message")
+        if lengths is None:
+            lengths = torch.empty(max(n, 1), dtype=torch.int64, device=sizes.device)
+        if status is None:
+            status = torch.empty(max(n, 1), dtype=torch.int32, device=sizes.device)
+        check(self._lib.tdt_encode_narrow_v(self._h, _ptr(ptrs), _ptr(sizes), n, _ptr(elems) if elems is not None else None,
+                                            int(elem), _ptr(out_ptrs), _ptr(out_caps), _ptr(lengths), _ptr(status),
+                                            self._stream(stream)))
+        return lengths, status
+
     @staticmethod
     def width_mask(word_sizes) -> int:
         """The mask encode_vw takes: bit w - 1 set for every width w in `word_sizes` (host ints)."""
@@ -556,7 +577,7 @@ class TdtCodec:
         return ptrs, sizes
 
     def encode_tensors(self, tensors, out=None, stream=None, word_sizes=None, packed=False, exact=False, mapbits=None,
-                       return_mappings=False):
+                       return_mappings=False, wire_dtype=None):
         """Encode a list of contiguous GPU tensors (message i = the bytes of tensors[i]) without
         packing them: blob i goes to out[slots[i]:slots[i+1]], the slots being the prefix sum of the
         encode bounds.  Returns (out, slots, lengths, status).
@@ -596,8 +617,18 @@ class TdtCodec:
             out, slots, lengths, status = codec.encode_tensors(grads, mapbits=bits)   # steps 2 .. K
         (exact=True sizes the blobs under the mappings the codec decides, so with it mapbits must be
         those of the same bytes, as return_mappings=True makes them: a stale mapping's longer blob
-        gets status 5 there.)"""
+        gets status 5 there.)
+
+        wire_dtype=torch.bfloat16 or torch.float16 (the sender of decode_reduce_tensors(wire_dtype=...)):
+        every tensor is a contiguous float32 one and blob i is the width-2 blob of its narrowing to that
+        type (encode_narrow_v: the tensor is read once and no half-precision copy is made); the slots
+        are the width-2 bounds of the wire sizes, n + 4 under raw_fallback.  Returns (out, slots,
+        lengths, status).  It combines with none of word_sizes, packed, exact, mapbits and
+        return_mappings."""
         import torch
+        if wire_dtype is not None:
+            return self._encode_tensors_narrow(tensors, out, stream, wire_dtype, word_sizes=word_sizes, packed=packed,
+                                               exact=exact, mapbits=mapbits, return_mappings=return_mappings)
         ptrs, sizes = self._tensor_table(tensors)
         n = len(tensors)
         if return_mappings and mapbits is not None:
@@ -677,6 +708,32 @@ class TdtCodec:
             dw = d[5 * n + 1:].view(torch.int32)[:n]
             lengths, status = self.encode_vw(d[:n], d[n:2 * n], dw, mask, d[2 * n:3 * n], d[3 * n:4 * n],
                                              stream=stream, mapbits=mapbits)
+        return out, d[4 * n:5 * n + 1], lengths, status
+
+    def _encode_tensors_narrow(self, tensors, out, stream, wire_dtype, **others):
+        """encode_tensors(wire_dtype=...): the slotted form through encode_narrow_v."""
+        import torch
+        for name, value in others.items():
+            if value is not None and value is not False:
+                raise ValueError("wire_dtype does not combine with %s" % name)
+        if wire_dtype not in (torch.bfloat16, torch.float16):
+            raise ValueError("wire_dtype is torch.bfloat16, torch.float16 or None, not %s" % wire_dtype)
+        for t in tensors:
+            if t.dtype != torch.float32:
+                raise ValueError("encode_tensors(wire_dtype=...) narrows float32 tensors, not %s" % t.dtype)
+        ptrs, sizes = self._tensor_table(tensors)
+        n = len(tensors)
+        dev = tensors[0].device if n else torch.device("cuda", self.device)
+        slots = np.zeros(n + 1, np.int64)
+        np.cumsum(self._bounds(sizes // 2, 2), out=slots[1:])
+        if out is None:
+            out = torch.empty(max(int(slots[-1]), 1), dtype=torch.uint8, device=dev)
+        elif out.numel() < int(slots[-1]):
+            raise ValueError("out holds %d bytes, the slots need %d" % (out.numel(), int(slots[-1])))
+        # one upload: addresses | sizes | blob addresses | capacities | slots
+        d = torch.from_numpy(np.concatenate([ptrs, sizes, out.data_ptr() + slots[:-1], np.diff(slots), slots])).to(dev)
+        code = _lib.TDT_ELEM_BF16_FROM_F32 if wire_dtype == torch.bfloat16 else _lib.TDT_ELEM_F16_FROM_F32
+        lengths, status = self.encode_narrow_v(d[:n], d[n:2 * n], d[2 * n:3 * n], d[3 * n:4 * n], elem=code, stream=stream)
         return out, d[4 * n:5 * n + 1], lengths, status
 
     def _encode_tensors_mapped(self, tensors, ptrs, sizes, out, stream, word_sizes, packed, exact):
