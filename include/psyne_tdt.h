@@ -313,8 +313,9 @@ int tdt_decode_reduce_v(tdt_ctx *ctx, const uint8_t *const *d_blobs, const uint6
  *   Conventions of tdt_encode_batch_v: every array in device memory with n_msgs entries, d_elem (NULL:
  *     `elem` for every message) one TDT_ELEM_BF16_FROM_F32 / TDT_ELEM_F16_FROM_F32 code per message;
  *     asynchronous on the caller's stream, nothing read back, n_msgs == 0 returns TDT_OK and touches
- *     nothing.  No workspace, no plan, no lists: one launch of n_msgs workgroups, capturable from the
- *     first call.  A null array with n_msgs > 0 and a bad `elem` with d_elem == NULL return TDT_E_ARG.
+ *     nothing.  With TDT_OPT_NARROW_TILED 0: no workspace, no plan, no lists, one launch of n_msgs
+ *     workgroups.  Capturable from the first call under either setting (below).  A null array with
+ *     n_msgs > 0 and a bad `elem` with d_elem == NULL return TDT_E_ARG.
  *   d_sizes[i] is the SOURCE size in bytes; the wire message has w = d_sizes[i] / 2 bytes.
  *   The contract: blob i, d_out_len[i] and d_status[i] are byte for byte what tdt_encode_batch_v gives
  *     on a context of word size 2 with the same metrics, config and TDT_OPT_RAW_FALLBACK setting for the
@@ -334,7 +335,18 @@ int tdt_decode_reduce_v(tdt_ctx *ctx, const uint8_t *const *d_blobs, const uint6
  *     fp16, not NaN   IEEE round to nearest even; subnormal results are kept, not flushed; values past
  *                     the largest finite fp16 become infinity
  *     fp16, NaN       sign | 0x7E00 | ((u >> 13) & 0x3FF)
- *   A tensor of up to 16,384 elements is read once; a longer one three times, on its one workgroup. */
+ *   A tensor of up to 16,384 elements is read once on its one workgroup.  A longer one is read three
+ *     times there — unless it takes the TILE PATH (TDT_OPT_NARROW_TILED, default 1): a tensor with a valid
+ *     code, an aligned source and size, w < 2^32 and a source size above TDT_OPT_LARGE_MIN is encoded as
+ *     tiles of TDT_NARROW_TILE_ELEMS elements, one workgroup per tile over the whole device, and read
+ *     twice.  Blob, length and status are byte for byte the one workgroup's; every refusal still precedes
+ *     the first store.  The tile path keeps a workspace in the context (a plan launch ahead of the
+ *     one-workgroup kernel, three tile launches and a snapshot launch behind it, all on the caller's
+ *     stream) that grows on eager calls only, from the claims of an earlier call: under stream capture a
+ *     tensor that finds it cold or its budget spent stays on its one workgroup, correct and slow, and the
+ *     call never fails for it.  The tile launches are dropped once a landed snapshot shows no long tensor,
+ *     and return with the first snapshot that shows one.  TDT_OPT_TILE_CAP lowers the tile budget of a call. */
+#define TDT_NARROW_TILE_ELEMS 16384u
 int tdt_encode_narrow_v(tdt_ctx *ctx, const uint8_t *const *d_msgs, const uint64_t *d_sizes, uint32_t n_msgs,
                         const uint8_t *d_elem, int elem, uint8_t *const *d_blobs, const uint64_t *d_blob_cap,
                         uint64_t *d_out_len, int32_t *d_status, void *hip_stream);
@@ -634,6 +646,10 @@ int tdt_ctx_error_flags(tdt_ctx *ctx, void *hip_stream, uint32_t *flags);
  * kernels, whatever the sizes — the A/B switch; the bits are the same.  TDT_OPT_TILE_CAP lowers the tile
  * budget of a call: a destination that finds no tiles left stays on its one workgroup. */
 #define TDT_OPT_REDUCE_TILED 12
+/* TILED ENCODE-NARROW.  Default 1 (PSYNE_TDT_NARROW_TILED): tdt_encode_narrow_v encodes tensors above
+ * TDT_OPT_LARGE_MIN as tiles over the whole device (see the call).  0: the call launches exactly its one
+ * kernel, one workgroup per tensor whatever the sizes — the A/B switch; the bytes are the same. */
+#define TDT_OPT_NARROW_TILED 13
 int tdt_ctx_set_option(tdt_ctx *ctx, int option, uint64_t value);
 
 /* Read-only counters of the context (tests and tools: which path a call took).  The claims are those
@@ -661,6 +677,10 @@ int tdt_ctx_set_option(tdt_ctx *ctx, int option, uint64_t value);
                                              landed summed as tiles (0 after a call with TDT_OPT_REDUCE_TILED 0 or
                                              one that found the workspace cold under capture) */
 #define TDT_STAT_REDUCE_TILES 10          /* the tiles of those destinations */
+#define TDT_STAT_NARROW_LARGE 11          /* tensors the most recent tdt_encode_narrow_v call whose snapshot has landed
+                                             encoded as tiles (0 after a call with TDT_OPT_NARROW_TILED 0 or one that
+                                             found the workspace cold under capture) */
+#define TDT_STAT_NARROW_TILES 12          /* the tiles of those tensors */
 int tdt_ctx_get_stat(tdt_ctx *ctx, int stat, uint64_t *value);
 
 /* Host-memory analyze (analyze_data :206-222): h_entropy n*ws doubles, h_mapping n*ws int32

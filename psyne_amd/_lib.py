@@ -32,8 +32,11 @@ TDT_OPT_ANY_DEC_TILED = 9  # generic word sizes: long blobs decoded as 32 KiB ti
 TDT_OPT_RAW_FALLBACK = 10  # 1: a message whose TDT blob would exceed n + 4 bytes is stored as its UNCP blob (default 0)
 TDT_OPT_HOST_RAW_FALLBACK = 11  # 1: the same rule for the host calls (tdt_encode_host / _v); independent of option 10
 TDT_OPT_REDUCE_TILED = 12  # decode-reduce: destinations above the threshold summed as tiles over the device (default 1)
+TDT_OPT_NARROW_TILED = 13  # encode-narrow: tensors above TDT_OPT_LARGE_MIN encoded as tiles over the device (default 1)
+TDT_NARROW_TILE_ELEMS = 16384  # elements per tile of the tiled encode-narrow
 TDT_REDUCE_TILE_BYTES = 33792  # output bytes per tile of a long destination (11 decoder windows)
 TDT_STAT_REDUCE_LARGE, TDT_STAT_REDUCE_TILES = 9, 10  # destinations the last landed decode-reduce call tiled; their tiles
+TDT_STAT_NARROW_LARGE, TDT_STAT_NARROW_TILES = 11, 12  # tensors the last landed encode-narrow call tiled; their tiles
 # tdt_ctx_get_stat: the generic-width decode plan's claims of the last call whose snapshot landed, and the budgets
 TDT_STAT_ANY_DEC_LARGE, TDT_STAT_ANY_DEC_BLOCKS, TDT_STAT_ANY_DEC_TILES = 1, 2, 3
 TDT_STAT_ANY_DEC_BUDGET_LARGE, TDT_STAT_ANY_DEC_BUDGET_TILES = 4, 5
@@ -44,7 +47,8 @@ STATS = {"ANY_DEC_LARGE": TDT_STAT_ANY_DEC_LARGE, "ANY_DEC_BLOCKS": TDT_STAT_ANY
          "ANY_DEC_TILES": TDT_STAT_ANY_DEC_TILES, "ANY_DEC_BUDGET_LARGE": TDT_STAT_ANY_DEC_BUDGET_LARGE,
          "ANY_DEC_BUDGET_TILES": TDT_STAT_ANY_DEC_BUDGET_TILES, "RAW_FALLBACKS": TDT_STAT_RAW_FALLBACKS,
          "PACK_SCRATCH_BYTES": TDT_STAT_PACK_SCRATCH_BYTES, "HOST_RAW_FALLBACKS": TDT_STAT_HOST_RAW_FALLBACKS,
-         "REDUCE_LARGE": TDT_STAT_REDUCE_LARGE, "REDUCE_TILES": TDT_STAT_REDUCE_TILES}
+         "REDUCE_LARGE": TDT_STAT_REDUCE_LARGE, "REDUCE_TILES": TDT_STAT_REDUCE_TILES,
+         "NARROW_LARGE": TDT_STAT_NARROW_LARGE, "NARROW_TILES": TDT_STAT_NARROW_TILES}
 
 
 class TdtConfigC(C.Structure):

@@ -26,7 +26,7 @@
 #include "tdt_decode.h"
 #include "tdt_encode.h"
 #include "tdt_enc_lmap.h"
-#include "tdt_enc_narrow.h"
+#include "tdt_enc_narrow_tiled.h"
 #include "tdt_grow.h"
 #if defined(PSY_FAST_BUILD) || (defined(PSY_PROF) && PSY_PROF) || defined(PSY_SINGLE_TU)
 #define PSY_DEC_REDUCE_TU 1  // (diagnostic single-file builds: the decode-reduce kernels are defined here)
@@ -280,6 +280,26 @@ struct RedWS {
     }
 };
 
+// Workspace of the tiled encode-narrow (tdt_enc_narrow_tiled.h), one per context, as AnyTiledWS: the
+// calls that use it hold the context's lock.
+struct NarWS {
+    uint8_t *buf = nullptr;  // counters (kPlanCounterBytes, zero between calls) | one mark word per tensor
+    size_t bytes = 0;
+    uint8_t *rec = nullptr;  // NarLarge records | NarTileRec records | kNarBins bins per large record (zero between calls)
+    size_t rec_bytes = 0;
+    uint32_t lcap = 0, tcap = 0;
+    CountHist<psy::NarCount> h;
+    bool last_tiled = false;  // the most recent call ran the plan (TDT_STAT_NARROW_*: 0 otherwise)
+    void release() {
+        if (buf) (void)hipFree(buf);
+        if (rec) (void)hipFree(rec);
+        buf = rec = nullptr;
+        bytes = rec_bytes = 0;
+        lcap = tcap = 0;
+        h.release();
+    }
+};
+
 // host pipeline slots (chunks in flight per tdt_encode_host / tdt_decode_host call)
 constexpr int kHostSlots = 4;
 
@@ -381,6 +401,10 @@ struct tdt_ctx {
     // summed as tiles over the whole device; off: every destination on its one workgroup
     bool reduce_tiled = true;
     RedWS redw;
+    // TDT_OPT_NARROW_TILED (PSYNE_TDT_NARROW_TILED): tensors of tdt_encode_narrow_v above large_min are encoded as
+    // tiles over the whole device; off: every tensor on its one workgroup
+    bool narrow_tiled = true;
+    NarWS narw;
     // diagnostic knobs (read once at tdt_ctx_create from the environment, or tdt_ctx_set_option)
     bool no_side = false;       // PSYNE_TDT_NO_SIDE: no side stream for the tile pipeline
     bool small_main = false;    // PSYNE_TDT_SMALL_MAIN: small lists on the caller's stream
@@ -2644,6 +2668,7 @@ int tdt_ctx_create(int device, const tdt_config *cfg, tdt_ctx **out) {
     if (const char *e = std::getenv("PSYNE_TDT_ANY_TILED")) x->any_tiled = *e != '0';
     if (const char *e = std::getenv("PSYNE_TDT_ANY_DEC_TILED")) x->any_dec_tiled = *e != '0';
     if (const char *e = std::getenv("PSYNE_TDT_REDUCE_TILED")) x->reduce_tiled = *e != '0';
+    if (const char *e = std::getenv("PSYNE_TDT_NARROW_TILED")) x->narrow_tiled = *e != '0';
     auto flag = [](const char *name) {
         const char *e = std::getenv(name);
         return e && *e == '1';
@@ -2691,6 +2716,7 @@ void tdt_ctx_destroy(tdt_ctx *ctx) {
     ctx->anyw.release();
     ctx->anydw.release();
     ctx->redw.release();
+    ctx->narw.release();
     ctx->rf_h.release();
     for (auto &w : ctx->mx_pw)
         if (w) w->release();
@@ -2760,6 +2786,7 @@ int tdt_ctx_set_option(tdt_ctx *ctx, int option, uint64_t value) {
         case TDT_OPT_ANY_DEC_TILED: ctx->any_dec_tiled = value != 0; return TDT_OK;
         case TDT_OPT_RAW_FALLBACK: ctx->raw_fallback = value != 0; return TDT_OK;
         case TDT_OPT_REDUCE_TILED: ctx->reduce_tiled = value != 0; return TDT_OK;
+        case TDT_OPT_NARROW_TILED: ctx->narrow_tiled = value != 0; return TDT_OK;
     }
     return set_err(TDT_E_ARG, "unknown option");
 }
@@ -2785,6 +2812,13 @@ int tdt_ctx_get_stat(tdt_ctx *ctx, int stat, uint64_t *value) {
         r.h.refresh();  // (as below)
         const bool on = r.last_tiled && r.h.valid;
         *value = !on ? 0 : r.h[stat == TDT_STAT_REDUCE_LARGE ? psy::RC_TILED : psy::RC_TILED_TILES];
+        return TDT_OK;
+    }
+    if (stat == TDT_STAT_NARROW_LARGE || stat == TDT_STAT_NARROW_TILES) {
+        NarWS &r = ctx->narw;
+        r.h.refresh();  // (as below)
+        const bool on = r.last_tiled && r.h.valid;
+        *value = !on ? 0 : r.h[stat == TDT_STAT_NARROW_LARGE ? psy::NC_TILED : psy::NC_TILED_TILES];
         return TDT_OK;
     }
     AnyDecWS &w = ctx->anydw;
@@ -3515,6 +3549,106 @@ int tdt_decode_reduce_v(tdt_ctx *ctx, const uint8_t *const *d_blobs, const uint6
     return TDT_OK;
 }
 
+// ---------------------------------------------------------------------------------------
+// The tiled encode-narrow's workspace (NarWS; the kernels: tdt_enc_narrow_tiled.h), handled as the
+// generic-width encode's (any_tiled_begin / any_tiled_end): budgets that start small, the claims in a
+// counter block, the pinned snapshot behind the call, growth in powers of two on a later call with the
+// old buffer retired.  The host reads nothing back.  Under stream capture nothing grows and nothing is
+// snapshotted, and the call never fails because of this workspace: a tensor that finds it cold or a
+// budget spent stays on the one-workgroup kernel.
+#if PSY_HAVE_ANYWS
+namespace {
+static_assert(TDT_NARROW_TILE_ELEMS == psy::kNarTile, "the header's tile size is the kernel's");
+constexpr uint32_t kNarL0 = 64, kNarLmax = 1u << 16;     // long tensors per call (2 KiB of bins each)
+constexpr uint32_t kNarT0 = 8192, kNarTmax = 1u << 22;   // 64 KiB tiles: 512 MiB of long tensors, 256 GiB
+struct NarRecLayout { size_t tiles, bins, bytes; };      // (the NarLarge records at 0)
+NarRecLayout nar_rec_layout(uint32_t lcap, uint32_t tcap) {
+    const size_t tiles = ((size_t)lcap * sizeof(psy::NarLarge) + 15) & ~(size_t)15,
+                 bins = tiles + (size_t)tcap * sizeof(psy::NarTileRec);
+    return {tiles, bins, bins + (size_t)lcap * psy::kNarBins * sizeof(uint32_t)};
+}
+struct NarTiled {
+    psy::NarTiledArgs t{};
+    bool plan = false, tiles = false, snap = false;
+};
+// Ahead of the one-workgroup kernel (the caller holds the context's lock): the plan launch; a.mark is
+// set for the kernel.  x.tiles: launch the tile passes behind it; then nar_tiled_end.
+int nar_tiled_begin(tdt_ctx *c, psy::NarrowArgs &a, hipStream_t s, NarTiled &x) {
+    NarWS &w = c->narw;
+    w.last_tiled = false;
+    if (!c->narrow_tiled) return TDT_OK;
+    const uint32_t n = a.n_msgs;
+    const bool cap = capturing(s);
+    auto &H = w.h;
+    if (!cap) H.refresh();  // (event queries are not capturable)
+    const size_t need = psy::kPlanCounterBytes + 4ull * n;
+    if (need > w.bytes) {
+        if (cap) return TDT_OK;  // (a cold context: nothing to allocate under capture)
+        if (int st = grow_retiring(w.buf, w.bytes, need, psy::cap_double(need, w.bytes), c->retired, s)) return st;
+        HIPCHK(hipMemsetAsync(w.buf, 0, psy::kPlanCounterBytes, s));  // (from here on the snapshot pass zeroes it)
+    }
+    // the tile passes are off when an earlier plan found no long tensor (their launches would find none)
+    const bool tiles_on = !H.valid || H[psy::NC_LARGE] > 0;
+    if (tiles_on && !cap) {
+        uint32_t lc = w.lcap ? w.lcap : kNarL0, tc = w.tcap ? w.tcap : kNarT0;
+        if (H.valid) {  // what an earlier plan claimed, beyond its budget too
+            lc = std::max(lc, pow2_at_least(H[psy::NC_LARGE], kNarL0, kNarLmax));
+            tc = std::max(tc, pow2_at_least(H[psy::NC_TILES], kNarT0, kNarTmax));
+        }
+        if (lc != w.lcap || tc != w.tcap) {
+            const NarRecLayout RL = nar_rec_layout(lc, tc);
+            w.lcap = w.tcap = 0;
+            // (retired, not freed: calls still queued, or a captured graph, may use the old records)
+            if (int st = psy::grow(w.rec, w.rec_bytes, RL.bytes, RL.bytes, retire_to(c->retired), DevAlloc{})) return st;
+            HIPCHK(hipMemsetAsync(w.rec + RL.bins, 0, RL.bytes - RL.bins, s));  // (the bins are zero between calls)
+            w.lcap = lc;
+            w.tcap = tc;
+        }
+    }
+    const bool on = tiles_on && w.rec;
+    const NarRecLayout RL = nar_rec_layout(w.lcap, w.tcap);
+    x.t.cnt = reinterpret_cast<unsigned long long *>(w.buf);
+    x.t.mark = reinterpret_cast<uint32_t *>(w.buf + psy::kPlanCounterBytes);
+    x.t.large = reinterpret_cast<psy::NarLarge *>(w.rec);
+    x.t.tiles = reinterpret_cast<psy::NarTileRec *>(w.rec + RL.tiles);
+    x.t.bins = reinterpret_cast<uint32_t *>(w.rec + RL.bins);
+    x.t.lcap = on ? w.lcap : 0u;
+    x.t.tcap = on ? std::min(w.tcap, std::max(c->tile_cap, 1u)) : 0u;
+    x.t.grid = (uint32_t)c->cus * 8u;
+    x.t.large_min = c->large_min;
+    a.mark = x.t.mark;
+    x.t.a = a;
+    x.plan = true;
+    x.tiles = on;
+    x.snap = !cap;
+    w.last_tiled = true;
+    if (const int e = psy::launch_narrow_plan(x.t, s))
+        return set_err(TDT_E_HIP, std::string("encode-narrow plan launch: ") + hipGetErrorString((hipError_t)e));
+    return TDT_OK;
+}
+// Behind the one-workgroup kernel: the tile passes, then the counters to the pinned snapshot and to zero.
+int nar_tiled_end(tdt_ctx *c, const NarTiled &x, hipStream_t s) {
+    if (!x.plan) return TDT_OK;
+    auto &H = c->narw.h;
+    if (x.tiles)
+        if (const int e = psy::launch_narrow_tiles(x.t, s))
+            return set_err(TDT_E_HIP, std::string("encode-narrow tile launch: ") + hipGetErrorString((hipError_t)e));
+    if (x.snap && !H.pin) {
+        HIPCHK(hipHostMalloc(&H.pin, psy::kPlanSnapBytes, hipHostMallocDefault));
+        HIPCHK(hipEventCreateWithFlags(&H.ev, hipEventDisableTiming));
+    }
+    if (const int e = psy::launch_narrow_snap(x.t, x.snap ? H.pin : nullptr, s))
+        return set_err(TDT_E_HIP, std::string("encode-narrow snapshot launch: ") + hipGetErrorString((hipError_t)e));
+    if (x.snap) {
+        HIPCHK(hipEventRecord(H.ev, s));
+        H.n_pending = x.t.a.n_msgs;
+        H.pending = true;
+    }
+    return TDT_OK;
+}
+}  // namespace
+#endif
+
 int tdt_encode_narrow_v(tdt_ctx *ctx, const uint8_t *const *d_msgs, const uint64_t *d_sizes, uint32_t n_msgs,
                         const uint8_t *d_elem, int elem, uint8_t *const *d_blobs, const uint64_t *d_blob_cap,
                         uint64_t *d_out_len, int32_t *d_status, void *stream) {
@@ -3540,11 +3674,15 @@ int tdt_encode_narrow_v(tdt_ctx *ctx, const uint8_t *const *d_msgs, const uint64
     a.min_tensor = ctx->cfg.min_tensor_size;
     a.policy_on = policy_on(ctx) ? 1 : 0;
     a.raw_fallback = ctx->raw_fallback ? 1 : 0;
-    // one launch on the caller's stream: no workspace, no plan, no lists (the blob's length is counted
-    // in the kernel, so the raw fallback needs no second pass and TDT_STAT_RAW_FALLBACKS is not updated)
-    if (const int e = psy::launch_encode_narrow(a, (hipStream_t)stream))
+    // the long tensors: planned ahead of the one-workgroup kernel, encoded as tiles behind it
+    hipStream_t s = (hipStream_t)stream;
+    NarTiled x;
+    if (int st = nar_tiled_begin(ctx, a, s, x)) return st;
+    // one workgroup per tensor on the caller's stream (the blob's length is counted in the kernel, so
+    // the raw fallback needs no second pass and TDT_STAT_RAW_FALLBACKS is not updated)
+    if (const int e = psy::launch_encode_narrow(a, s))
         return set_err(TDT_E_HIP, std::string("encode-narrow launch: ") + hipGetErrorString((hipError_t)e));
-    return TDT_OK;
+    return nar_tiled_end(ctx, x, s);
 #else
     (void)stream;
     return set_err(TDT_E_UNSUPPORTED, "this build holds no encode-narrow kernel");

@@ -26,6 +26,8 @@
 // A longer tensor takes the same phases over chunks of kNarResident elements, restaged from the
 // source for C and for E (three reads of 4 bytes per element, on one workgroup); the run carries
 // cross the chunks.  Blobs, lengths and statuses are the width-2 encode's of the narrowed bytes.
+// Above the large-message threshold a tensor leaves this kernel for the tile passes of
+// tdt_enc_narrow_tiled.h (two reads, one workgroup per chunk); its bytes are the same.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -53,6 +55,7 @@ struct NarrowArgs {
     uint64_t min_tensor;
     int32_t policy_on;           // as EncodeArgs::policy_on
     int32_t raw_fallback;        // TDT_OPT_RAW_FALLBACK
+    const uint32_t *mark;        // null, or one word per message: non-zero = the tile passes have it (tdt_enc_narrow_tiled.h)
 };
 
 // One launch per 2^24 - 1 messages on stream s.  Returns a hipError_t as int (0: launched).

@@ -8,10 +8,11 @@
 //   :557-582, serialize :81-117.
 // (the headers' non-template kernels are defined once, in tdt_api.hip)
 #define PSY_ENC_INST_TU 1
-#include "tdt_enc_narrow.h"
+#include "tdt_enc_narrow_tiled.h"
 
 #include <algorithm>
 
+#include "tdt_anyws_tiles.h"
 #include "tdt_encode.h"
 #include "tdt_entropy.h"
 
@@ -250,13 +251,12 @@ __device__ __forceinline__ void nar_step(const uint8_t *s_pl, bool inter, uint32
     c.cpairs += tadd[0] + extra;
 }
 
-// The UNCP form: the marker and the w = 2 ne narrowed bytes, 16 per lane and store.  staged: the
-// planes hold the whole message (ne <= kNarResident); else it is narrowed from the source again.
-__device__ __forceinline__ void nar_uncp(uint8_t *dst, const uint8_t *src, uint64_t ne, bool bf, bool staged, const uint8_t *s_pl) {
-    const uint32_t tid = threadIdx.x;
+// The 16-byte groups [g0, g1) of the w = 2 ne narrowed bytes behind the marker, one per lane and store.
+// staged: the planes hold the whole message (ne <= kNarResident); else it is narrowed from the source again.
+__device__ __forceinline__ void nar_uncp_groups(uint8_t *dst, const uint8_t *src, uint64_t ne, bool bf, bool staged, const uint8_t *s_pl,
+                                                uint64_t g0, uint64_t g1) {
     const uint64_t w = 2ull * ne;
-    if (tid < 4) dst[tid] = (uint8_t)(kMagicUNCP >> (8 * tid));
-    for (uint64_t g = tid; 16ull * g < w; g += kNarTeam) {
+    for (uint64_t g = g0 + threadIdx.x; g < g1; g += kNarTeam) {
         const int valid = w - 16ull * g >= 16 ? 16 : (int)(w - 16ull * g);
         uint4 v;
         if (staged) {
@@ -274,6 +274,11 @@ __device__ __forceinline__ void nar_uncp(uint8_t *dst, const uint8_t *src, uint6
         st16_any(dst + 4 + 16ull * g, v, valid);
     }
 }
+// The UNCP form: the marker and every group.
+__device__ __forceinline__ void nar_uncp(uint8_t *dst, const uint8_t *src, uint64_t ne, bool bf, bool staged, const uint8_t *s_pl) {
+    if (threadIdx.x < 4) dst[threadIdx.x] = (uint8_t)(kMagicUNCP >> (8 * threadIdx.x));
+    nar_uncp_groups(dst, src, ne, bf, staged, s_pl, 0, (2ull * ne + 15) / 16);
+}
 
 __global__ __launch_bounds__(kNarTeam) void tdt_encode_narrow_kernel(NarrowArgs a, uint32_t base) {
     __shared__ __attribute__((aligned(16))) uint8_t s_pl[2 * kNarResident];
@@ -285,6 +290,7 @@ __global__ __launch_bounds__(kNarTeam) void tdt_encode_narrow_kernel(NarrowArgs 
     const uint32_t tid = threadIdx.x, lane = (uint32_t)lane_id(), wv = tid >> 6;
     const uint32_t msg = base + blockIdx.x;
     if (msg >= a.n_msgs) return;
+    if (a.mark && a.mark[msg]) return;  // (uniform) the tile passes have it
     const uint32_t code = a.elem_codes ? (uint32_t)a.elem_codes[msg] : a.elem;
     const uint64_t srca = a.msgs[msg], size = a.sizes[msg], cap = a.blob_cap[msg];
     const uint8_t *src = reinterpret_cast<const uint8_t *>(srca);
@@ -404,7 +410,392 @@ __global__ __launch_bounds__(kNarTeam) void tdt_encode_narrow_kernel(NarrowArgs 
     pass(std::true_type{}, pairs, Pe);
 }
 
+// ---------------------------------------------------------------------------------------
+// The tiled form (tdt_enc_narrow_tiled.h).  Every kernel below but the plan and the snapshot runs a
+// fixed grid striding over the records the plan claimed; their counts stay in device memory.
+
+// the records in use: what the plan claimed, within the budgets it ran with
+__device__ __forceinline__ uint32_t nar_claimed(const NarTiledArgs &t, NarCount k, uint32_t cap) {
+    const unsigned long long c = t.cnt[k];
+    return (uint32_t)__builtin_amdgcn_readfirstlane((int)(c < cap ? (uint32_t)c : cap));
+}
+__device__ __forceinline__ uint32_t nar_uniform(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }
+// the wire halfword of element e
+__device__ __forceinline__ uint32_t nar_halfword(const uint8_t *src, uint64_t e, bool bf) {
+    const uint32_t u = gload<uint32_t>(src + 4ull * e);
+    return bf ? nar_bf16(u) : nar_f16(u);
+}
+// the bytes of d that are not 0, as a 4-bit mask (the tail of neq_prev_mask4)
+__device__ __forceinline__ uint32_t nar_nz_mask4(uint32_t d) {
+    const uint32_t nz = (((d & 0x7f7f7f7fu) + 0x7f7f7f7fu) | d) & 0x80808080u;
+    return (((nz >> 7) * 0x00204081u) >> 21) & 0xfu;
+}
+// bit i of a 16-bit mask to bit 2 i
+__device__ __forceinline__ uint32_t nar_spread16(uint32_t x) {
+    x = (x | (x << 8)) & 0x00ff00ffu;
+    x = (x | (x << 4)) & 0x0f0f0f0fu;
+    x = (x | (x << 2)) & 0x33333333u;
+    return (x | (x << 1)) & 0x55555555u;
+}
+
+// ---- plan: one lane per tensor
+__global__ __launch_bounds__(1024) void tdt_narrow_plan_kernel(NarTiledArgs t) {
+    __shared__ uint64_t lds[2 * (16 + 1)];
+    const NarrowArgs &a = t.a;
+    const uint32_t msg = blockIdx.x * 1024u + threadIdx.x, lane = (uint32_t)lane_id();
+    bool want = false;
+    uint32_t code = 0u;
+    uint64_t srca = 0, size = 0;
+    if (msg < a.n_msgs) {
+        code = a.elem_codes ? (uint32_t)a.elem_codes[msg] : a.elem;
+        srca = a.msgs[msg];
+        size = a.sizes[msg];
+        // (everything else is the one-workgroup kernel's: the refusals, a wire size of 2^32 and more)
+        want = (code == kNarBF16 || code == kNarF16) && !((srca | size) & 3u) && size / 2 < (1ull << 32) && size > t.large_min;
+    }
+    const uint64_t ne = size / 4, w = size / 2;
+    const uint32_t nt = want ? (uint32_t)((ne + kNarTile - 1) / kNarTile) : 0u;
+    uint64_t A[2][1] = {{want ? 1u : 0u}, {nt}}, SA[2][1];
+    {
+        constexpr int ia[2] = {NC_LARGE, NC_TILES};
+        wg_claim_n<2, 1>(A, SA, t.cnt, ia, lds);
+    }
+    const uint64_t L = SA[0][0], T = SA[1][0];
+    const bool ok = want && L < t.lcap && T + nt <= t.tcap;
+    uint64_t B[2][1] = {{ok ? 1u : 0u}, {ok ? nt : 0u}}, SB[2][1];
+    {
+        constexpr int ib[2] = {NC_TILED, NC_TILED_TILES};
+        wg_claim_n<2, 1>(B, SB, t.cnt, ib, lds);
+    }
+    if (want && L < t.lcap) {
+        NarLarge g{};  // (over the tile budget: ntiles 0, no pass's record)
+        if (ok) {
+            g.src = reinterpret_cast<const uint8_t *>(srca);
+            g.dst = reinterpret_cast<uint8_t *>(a.blobs[msg]);
+            g.cap = a.blob_cap[msg];
+            g.msg = msg;
+            g.ne = (uint32_t)ne;
+            g.tile0 = (uint32_t)T;
+            g.ntiles = nt;
+            // should_transform :186-201 and compress_tdt's size guard :364-367, as the one-workgroup kernel
+            const bool compress = a.policy_on && w >= a.min_tensor && (w % 4 == 0) && w >= 64 && w < (1ull << 32);
+            g.flags = (compress ? 0u : kNarUncpRouted) | (code == kNarBF16 ? kNarIsBf16 : 0u);
+        }
+        t.large[L] = g;
+    }
+    // the owner of every tile record a claim reached, 64 records a step (one lane writing a long
+    // tensor's thousands of entries would be the plan's whole time); over a budget: no owner
+    const uint32_t tb = (uint32_t)(T < t.tcap ? T : t.tcap), te = (uint32_t)(T + nt < t.tcap ? T + nt : t.tcap);
+    const uint32_t own = ok ? (uint32_t)L : kNarNoOwner;
+    uint64_t m = __ballot(want && tb < te);
+    while (m) {  // (uniform)
+        const int l = __builtin_ctzll(m);
+        m &= m - 1;
+        const uint32_t b = (uint32_t)__shfl((int)tb, l), e = (uint32_t)__shfl((int)te, l), o = (uint32_t)__shfl((int)own, l);
+        for (uint32_t k = b + lane; k < e; k += 64u) t.tiles[k].owner = o;
+    }
+    if (msg < a.n_msgs) t.mark[msg] = ok ? 1u : 0u;
+}
+
+// ---- A: one tile staged once — its bins, and the run records of all three candidate streams
+__global__ __launch_bounds__(kNarTeam) void tdt_narrow_analyse_kernel(NarTiledArgs t) {
+    __shared__ __attribute__((aligned(16))) uint8_t s_pl[2 * kNarResident];
+    __shared__ __attribute__((aligned(16))) uint32_t s_hist[kNarHistCopies * 512];
+    __shared__ uint32_t s_slots[2][kNarCand * kNW];
+    __shared__ uint32_t s_first[kNarCand];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t nt = nar_claimed(t, NC_TILES, t.tcap);
+    for (uint32_t i = tid; i < kNarHistCopies * 512u; i += kNarTeam) s_hist[i] = 0u;
+    for (uint32_t e = blockIdx.x; e < nt; e += gridDim.x) {  // (uniform)
+        NarTileRec &r = t.tiles[e];
+        const uint32_t L = nar_uniform(r.owner);
+        if (L == kNarNoOwner) continue;
+        const NarLarge &g = t.large[L];
+        const uint32_t flags = nar_uniform(g.flags);
+        if (flags & kNarUncpRouted) continue;  // (nothing to decide: its tiles copy)
+        const uint8_t *src = g.src;
+        const bool bf = (flags & kNarIsBf16) != 0u;
+        const uint32_t eb = (e - nar_uniform(g.tile0)) * kNarTile, ne = nar_uniform(g.ne);
+        const uint32_t cnt = ne - eb < kNarTile ? ne - eb : kNarTile;
+        __syncthreads();  // (the tile before is done with the planes and s_first; the copies are zero)
+        if (tid < (uint32_t)kNarCand) s_first[tid] = 0u;
+        nar_stage<true>(src, eb, cnt, bf, s_pl, s_hist);
+        // the bytes before the tile: element eb - 1
+        const uint32_t hb = eb ? nar_halfword(src, eb - 1u, bf) : 0u;
+        const uint32_t pl = hb & 0xffu, ph = hb >> 8;
+        __syncthreads();
+        // the copies → the tensor's bins (integer adds: any order gives the same counts)
+        uint32_t *bins = t.bins + (size_t)L * kNarBins;
+        for (uint32_t b = tid; b < kNarBins; b += kNarTeam) {
+            uint32_t c = 0u;
+#pragma unroll
+            for (uint32_t q = 0; q < kNarHistCopies; ++q) {
+                c += s_hist[q * 512u + b];
+                s_hist[q * 512u + b] = 0u;
+            }
+            if (c) atomicAdd(bins + b, c);
+        }
+        // the sweep: 16 elements of both planes per lane and step; positions in each stream's own
+        // coordinates, + 1; cst: the candidate's last run start so far in this tile (0: none yet)
+        uint32_t cst[kNarCand] = {0u, 0u, 0u}, inner[kNarCand] = {0u, 0u, 0u};
+        for (uint32_t sb = 0; sb < cnt; sb += kNarStep) {  // (uniform)
+            const uint32_t l0 = sb + 16u * tid;
+            const uint32_t mv = l0 >= cnt ? 0u : (cnt - l0 >= 16u ? 16u : cnt - l0);
+            const uint4 lo = *reinterpret_cast<const uint4 *>(s_pl + l0);
+            const uint4 hi = *reinterpret_cast<const uint4 *>(s_pl + kNarResident + l0);
+            const uint32_t p0 = l0 ? s_pl[l0 - 1u] : pl, p1 = l0 ? s_pl[kNarResident + l0 - 1u] : ph;
+            const uint32_t x0[4] = {lo.x, lo.y, lo.z, lo.w}, x1[4] = {hi.x, hi.y, hi.z, hi.w};
+            uint32_t sm[kNarCand] = {0u, 0u, 0u}, ma = 0u, mb = 0u;
+#pragma unroll
+            for (int d = 0; d < 4; ++d) {
+                const uint32_t b0 = d ? x0[d ? d - 1 : 0] : p0 << 24, b1 = d ? x1[d ? d - 1 : 0] : p1 << 24;
+                sm[0] |= neq_prev_mask4(x0[d], b0) << (4 * d);
+                sm[1] |= neq_prev_mask4(x1[d], b1) << (4 * d);
+                // the interleaved stream: its byte 2 i is lo[i] (after hi[i - 1]), byte 2 i + 1 is hi[i] (after lo[i])
+                ma |= nar_nz_mask4(x0[d] ^ __builtin_amdgcn_alignbyte(x1[d], b1, 3)) << (4 * d);
+                mb |= nar_nz_mask4(x0[d] ^ x1[d]) << (4 * d);
+            }
+            sm[2] = nar_spread16(ma) | (nar_spread16(mb) << 1);
+            const uint32_t vm = (1u << mv) - 1u;
+            const uint32_t q[kNarCand] = {eb + l0, eb + l0, 2u * (eb + l0)};  // the lane's first position in each stream
+            uint32_t vmax[kNarCand], tmax[kNarCand], vadd[kNarCand], tadd[kNarCand];
+#pragma unroll
+            for (int s = 0; s < kNarCand; ++s) {
+                if (eb + l0 == 0u) sm[s] |= 1u;  // the stream's first byte
+                sm[s] &= s == 2 ? (mv == 16u ? ~0u : (1u << (2u * mv)) - 1u) : vm;
+                vmax[s] = sm[s] ? q[s] + (31u - (uint32_t)__builtin_clz(sm[s])) + 1u : 0u;
+            }
+            team_excl_scan<kNW, kNarCand, OpMax>(vmax, tmax, s_slots[0]);
+#pragma unroll
+            for (int s = 0; s < kNarCand; ++s) {
+                const uint32_t cur = vmax[s] > cst[s] ? vmax[s] : cst[s];  // run start + 1 entering this lane
+                uint32_t np = 0u;
+                if (sm[s]) {
+                    const uint32_t qf = q[s] + (uint32_t)__builtin_ctz(sm[s]);
+                    np = (uint32_t)__builtin_popcount(sm[s]);
+                    if (cur == 0u) {  // the tile's first start: the run it closes is the scan's
+                        --np;
+                        s_first[s] = qf + 1u;
+                    } else {
+                        np += (qf - cur) / 255u;  // nar_step: (Lr - 1) / 255 full pairs, Lr = qf - (cur - 1)
+                    }
+                }
+                vadd[s] = np;
+            }
+            team_excl_scan<kNW, kNarCand, OpAdd>(vadd, tadd, s_slots[1]);
+#pragma unroll
+            for (int s = 0; s < kNarCand; ++s) {
+                cst[s] = tmax[s] > cst[s] ? tmax[s] : cst[s];
+                inner[s] += tadd[s];
+            }
+        }
+        __syncthreads();  // (s_first is written)
+        if (tid < (uint32_t)kNarCand) {
+            r.first[tid] = s_first[tid];
+            r.last[tid] = tid == 0u ? cst[0] : tid == 1u ? cst[1] : cst[2];
+            r.inner[tid] = tid == 0u ? inner[0] : tid == 1u ? inner[1] : inner[2];
+        }
+    }
+}
+
+// ---- M: the mapping of a large tensor, the scan over its tiles, its length, status and fixed words
+__global__ __launch_bounds__(kNarTeam) void tdt_narrow_map_kernel(NarTiledArgs t) {
+    __shared__ double s_ent[2];
+    __shared__ uint32_t s_slots[2][2 * kNW];
+    const NarrowArgs &a = t.a;
+    const uint32_t tid = threadIdx.x, lane = (uint32_t)lane_id(), wv = tid >> 6;
+    const uint32_t nl = nar_claimed(t, NC_LARGE, t.lcap);
+    for (uint32_t L = blockIdx.x; L < nl; L += gridDim.x) {  // (uniform)
+        NarLarge *g = t.large + L;
+        const uint32_t nt = nar_uniform(g->ntiles);
+        if (!nt) continue;
+        const uint32_t msg = g->msg, ne32 = nar_uniform(g->ne), flags = nar_uniform(g->flags);
+        const uint64_t w = 2ull * ne32, cap = g->cap;
+        const uint32_t w32 = (uint32_t)w;
+        uint8_t *dst = g->dst;
+        auto report = [&](int32_t st, uint64_t len) __attribute__((always_inline)) {
+            if (tid == 0) {
+                if (a.status) a.status[msg] = st;
+                if (a.out_len) a.out_len[msg] = len;
+            }
+        };
+        if (flags & kNarUncpRouted) {
+            const bool fits = w + 4 <= cap;
+            report(fits ? ST_OK : ST_CAPACITY, fits ? w + 4 : 0);
+            if (tid == 0) g->route = fits ? kNarRaw : kNarRefused;
+            continue;
+        }
+        // entropies, then perform_clustering :507-525: entropy > in-order sum / 2
+        uint32_t *bins = t.bins + (size_t)L * kNarBins;
+        __syncthreads();  // (the tensor before is done with s_ent)
+        if (wv < 2u) {
+            uint32_t cb[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                cb[k] = bins[wv * 256u + 64u * k + lane];
+                bins[wv * 256u + 64u * k + lane] = 0u;  // (all zero again for the next call)
+            }
+            const double e = any_entropy(cb, (double)ne32);
+            if (lane == 0) s_ent[wv] = e;
+        }
+        __syncthreads();
+        double sum = 0.0;
+        sum += s_ent[0];
+        sum += s_ent[1];
+        const double thr = sum / 2.0;
+        const uint32_t m0 = (uint32_t)__builtin_amdgcn_readfirstlane(s_ent[0] > thr ? 1 : 0);  // (uniform: every lane ran the same chain)
+        const uint32_t m1 = (uint32_t)__builtin_amdgcn_readfirstlane(s_ent[1] > thr ? 1 : 0);
+        const uint32_t ns = (m0 | m1) ? 2u : 1u;  // separate_byte_streams :527-549: max(mapping) + 1
+        const bool inter = ns == 1u;
+        const uint32_t S = inter ? w32 : ne32;  // bytes of a stream
+        // stream s is candidate cand[s]: stream 0 holds the positions mapped to 0
+        const uint32_t cand[2] = {inter ? 2u : m0, inter ? 2u : 1u - m0};
+        NarTileRec *tiles = t.tiles + g->tile0;
+        uint32_t carry[2] = {0u, 0u}, base[2] = {0u, 0u};  // (uniform) behind the tiles so far
+        for (uint32_t i0 = 0; i0 < nt; i0 += kNarTeam) {
+            const uint32_t i = i0 + tid;
+            AnyTileRuns runs[2] = {{0u, 0u, 0u}, {0u, 0u, 0u}};
+            if (i < nt) {
+#pragma unroll
+                for (int s = 0; s < 2; ++s)
+                    if ((uint32_t)s < ns) runs[s] = AnyTileRuns{tiles[i].first[cand[s]], tiles[i].last[cand[s]], tiles[i].inner[cand[s]]};
+            }
+            uint32_t vmax[2] = {runs[0].last, runs[1].last}, tmax[2];
+            team_excl_scan<kNW, 2, OpMax>(vmax, tmax, s_slots[0]);
+            uint32_t vadd[2], tadd[2], cin[2];
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                cin[s] = vmax[s] > carry[s] ? vmax[s] : carry[s];
+                vadd[s] = any_tile_pairs(runs[s], cin[s]);
+            }
+            team_excl_scan<kNW, 2, OpAdd>(vadd, tadd, s_slots[1]);
+            if (i < nt) {
+#pragma unroll
+                for (int s = 0; s < 2; ++s) {
+                    tiles[i].carry[s] = cin[s];
+                    tiles[i].base[s] = base[s] + vadd[s];
+                }
+            }
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                carry[s] = tmax[s] > carry[s] ? tmax[s] : carry[s];
+                base[s] += tadd[s];
+            }
+        }
+        // the run that closes at either stream's end; stream 0's total places stream 1
+        uint32_t P[2] = {0u, 0u};
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+            if ((uint32_t)s < ns) P[s] = base[s] + any_final_pairs(S, carry[s]);
+        const uint64_t o1 = 32 + 2ull * P[0];                        // stream 1's length word
+        const uint64_t Etdt = ns == 2u ? o1 + 4 + 2ull * P[1] : o1;  // header 28, length word(s), pairs
+        const bool raw = a.raw_fallback && Etdt > w + 4;             // TDT_OPT_RAW_FALLBACK
+        const uint64_t E = raw ? w + 4 : Etdt;
+        const bool fits = E <= cap;
+        report(fits ? ST_OK : ST_CAPACITY, fits ? E : 0);
+        if (tid == 0) {
+            g->route = !fits ? kNarRefused : raw ? kNarRaw : kNarTdt;
+            g->m0 = m0;
+            g->m1 = m1;
+            g->pairs[0] = P[0];
+            g->pairs[1] = P[1];
+        }
+        // header (serialize :81-117): magic, original size, streams, word size, mapping; length words
+        if (fits && !raw && tid < 36u) {
+            const uint32_t k = tid >> 2;
+            const uint32_t hv = k == 0 ? kMagicTDT : k == 1 ? w32 : k == 2 ? ns : k == 3 ? 2u : k == 4 ? 2u : k == 5 ? m0 : k == 6 ? m1
+                              : k == 7 ? 2u * P[0] : 2u * P[1];
+            const uint64_t at = k < 8u ? tid : o1 + (tid & 3u);
+            if (k < 8u || ns == 2u) dst[at] = (uint8_t)(hv >> (8u * (tid & 3u)));
+        }
+    }
+}
+
+// ---- E: one tile's pairs of the chosen stream(s), or its share of the UNCP form
+__global__ __launch_bounds__(kNarTeam) void tdt_narrow_emit_kernel(NarTiledArgs t) {
+    __shared__ __attribute__((aligned(16))) uint8_t s_pl[2 * kNarResident];
+    __shared__ __attribute__((aligned(16))) uint32_t s_stage[(2u * kNarStagePairs + 8u + 3u) / 4u];
+    __shared__ uint32_t s_slots[2][kNW];
+    __shared__ NarBig s_big;
+    const uint32_t tid = threadIdx.x;
+    const uint32_t nt = nar_claimed(t, NC_TILES, t.tcap);
+    for (uint32_t e = blockIdx.x; e < nt; e += gridDim.x) {  // (uniform)
+        const NarTileRec &r = t.tiles[e];
+        const uint32_t L = nar_uniform(r.owner);
+        if (L == kNarNoOwner) continue;
+        const NarLarge &g = t.large[L];
+        const uint32_t route = nar_uniform(g.route);
+        if (route == kNarRefused) continue;  // (nothing is written)
+        const uint8_t *src = g.src;
+        uint8_t *dst = g.dst;
+        const bool bf = (nar_uniform(g.flags) & kNarIsBf16) != 0u;
+        const uint32_t tt = e - nar_uniform(g.tile0), eb = tt * kNarTile, ne = nar_uniform(g.ne);
+        const uint32_t cnt = ne - eb < kNarTile ? ne - eb : kNarTile;
+        if (route == kNarRaw) {  // the tile's wire bytes behind the marker (a tile is whole 16-byte groups)
+            if (tt == 0u && tid < 4u) dst[tid] = (uint8_t)(kMagicUNCP >> (8 * tid));
+            nar_uncp_groups(dst, src, ne, bf, false, nullptr, eb / 8u, (2ull * (eb + cnt) + 15) / 16);
+            continue;
+        }
+        const uint32_t m0 = nar_uniform(g.m0), m1 = nar_uniform(g.m1);
+        const uint32_t ns = (m0 | m1) ? 2u : 1u;
+        const bool inter = ns == 1u;
+        const uint32_t S = inter ? 2u * ne : ne;
+        __syncthreads();  // (the tile before is done with the planes)
+        nar_stage<false>(src, eb, cnt, bf, s_pl, nullptr);
+        const uint32_t hb = eb ? nar_halfword(src, eb - 1u, bf) : 0u;  // the bytes before the tile
+        __syncthreads();
+        uint8_t *const pairs[2] = {dst + 32, dst + 32 + 2ull * g.pairs[0] + 4};
+#pragma unroll
+        for (uint32_t s = 0; s < 2; ++s) {
+            if (s >= ns) continue;
+            const uint32_t plane = m0 ? 1u - s : s;  // stream 0 holds the positions mapped to 0
+            NarCarry c{r.carry[s], r.base[s], inter || plane ? hb >> 8 : hb & 0xffu};
+            const uint32_t Qb = inter ? 2u * eb : eb, Ls = inter ? 2u * cnt : cnt;
+            for (uint32_t lq = 0; lq < Ls; lq += kNarStep)
+                nar_step<true>(s_pl, inter, plane, Qb + lq, lq, Ls - lq < kNarStep ? Ls - lq : kNarStep, c, pairs[s], s_stage, s_slots,
+                               &s_big);
+            if (tt + 1u == nar_uniform(g.ntiles)) {  // the stream's last tile: the run that closes at the stream's end
+                const uint32_t Lr = S - (c.cstart - 1u);
+                const uint32_t full = (Lr - 1u) / 255u;
+                uint8_t *A = pairs[s] + 2ull * c.cpairs;
+                nar_fill(A, full, c.lastb);
+                if (tid == 0) {
+                    A[2ull * full] = (uint8_t)(Lr - 255u * full);
+                    A[2ull * full + 1] = (uint8_t)c.lastb;
+                }
+            }
+        }
+    }
+}
+
+// ---- snap: the counters to the host's snapshot, and zero for the next call
+__global__ __launch_bounds__(64) void tdt_narrow_snap_kernel(unsigned long long *cnt, uint32_t *pin) {
+    uint32_t *c = reinterpret_cast<uint32_t *>(cnt);
+    if (threadIdx.x < kPlanSnapBytes / 4) {
+        if (pin) pin[threadIdx.x] = c[threadIdx.x];
+        c[threadIdx.x] = 0u;
+    }
+}
+
 }  // namespace
+
+int launch_narrow_plan(const NarTiledArgs &t, hipStream_t s) {
+    hipLaunchKernelGGL(tdt_narrow_plan_kernel, dim3((t.a.n_msgs + 1023u) / 1024u), dim3(1024), 0, s, t);
+    return (int)hipGetLastError();
+}
+
+int launch_narrow_tiles(const NarTiledArgs &t, hipStream_t s) {
+    const dim3 tg(std::max(1u, std::min(t.tcap, t.grid))), lg(std::max(1u, std::min(t.lcap, t.grid)));
+    hipLaunchKernelGGL(tdt_narrow_analyse_kernel, tg, dim3(kNarTeam), 0, s, t);
+    hipLaunchKernelGGL(tdt_narrow_map_kernel, lg, dim3(kNarTeam), 0, s, t);
+    hipLaunchKernelGGL(tdt_narrow_emit_kernel, tg, dim3(kNarTeam), 0, s, t);
+    return (int)hipGetLastError();
+}
+
+int launch_narrow_snap(const NarTiledArgs &t, uint32_t *pin, hipStream_t s) {
+    hipLaunchKernelGGL(tdt_narrow_snap_kernel, dim3(1), dim3(64), 0, s, t.cnt, pin);
+    return (int)hipGetLastError();
+}
 
 int launch_encode_narrow(const NarrowArgs &a, hipStream_t s) {
     // one workgroup per message; a launch holds < 2^32 threads

@@ -62,8 +62,17 @@ enum RedCount : int {
     RC_TILED_TILES = 4   // their tiles
 };
 
+// The tiled encode-narrow (tdt_enc_narrow_tiled.h) likewise; its snapshot pass zeroes the block again.
+enum NarCount : int {
+    NC_LARGE = 0,        // large-tensor records claimed (beyond the budget too: the next call grows it)
+    NC_TILES = 1,        // tile records claimed (likewise)
+    NC_TILED = 2,        // tensors the plan handed to the tile passes
+    NC_TILED_TILES = 3   // their tiles
+};
+
 // u32 view of the block: index of a counter's low word (the only place the two units meet)
 constexpr int lo32(RedCount k) { return 2 * (int)k; }
+constexpr int lo32(NarCount k) { return 2 * (int)k; }
 constexpr int lo32(EncCount k) { return 2 * (int)k; }
 constexpr int lo32(DecCount k) { return 2 * (int)k; }
 constexpr int lo32(AnyCount k) { return 2 * (int)k; }

@@ -852,7 +852,9 @@ class TdtCodec:
         values of psyne_amd._lib.  TDT_OPT_LARGE_MIN and TDT_OPT_TILE_CAP govern the tiled paths of every
         word size; TDT_OPT_ANY_TILED = 0 keeps every generic-width message on one workgroup, and
         TDT_OPT_ANY_DEC_TILED = 0 every generic-width blob; TDT_OPT_REDUCE_TILED = 0 keeps every destination of
-        decode_reduce_v on one workgroup (default 1: long destinations are summed as tiles over the device)."""
+        decode_reduce_v on one workgroup (default 1: long destinations are summed as tiles over the device), and
+        TDT_OPT_NARROW_TILED = 0 every tensor of encode_narrow_v (default 1: tensors above TDT_OPT_LARGE_MIN are
+        encoded as tiles of TDT_NARROW_TILE_ELEMS elements; stat("NARROW_LARGE") / stat("NARROW_TILES") count them)."""
         check(self._lib.tdt_ctx_set_option(self._h, option, int(value)))
 
     def stat(self, name) -> int:

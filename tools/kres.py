@@ -59,6 +59,9 @@ def main(argv):
         if (csrc / "tdt_dec_reduce.hip").exists():  # (the decode-reduce kernels, same flags)
             from psyne_amd.build import DEC_ACC_FLAGS
             jobs.append((csrc / "tdt_dec_reduce.hip", flags + DEC_ACC_FLAGS, tmp + "/dec_reduce.o"))
+        if (csrc / "tdt_enc_narrow.hip").exists():  # (the encode-narrow kernels, same flags)
+            from psyne_amd.build import DEC_ACC_FLAGS
+            jobs.append((csrc / "tdt_enc_narrow.hip", flags + DEC_ACC_FLAGS, tmp + "/enc_narrow.o"))
         jobs += [(csrc / "tdt_enc_ws.hip", flags + ["-DPSY_INST_WS=%d" % ws], tmp + "/ws%d.o" % ws) for ws in ws_list]
         jobs += [(csrc / "tdt_enc_sizes_ws.hip", flags + ["-DPSY_INST_WS=%d" % ws], tmp + "/sws%d.o" % ws) for ws in ws_list]
         if (csrc / "tdt_enc_mapped_ws.hip").exists():  # (absent in a parent tree this file is copied into for an A/B)
