@@ -350,6 +350,34 @@ int tdt_decode_reduce_v(tdt_ctx *ctx, const uint8_t *const *d_blobs, const uint6
 int tdt_encode_narrow_v(tdt_ctx *ctx, const uint8_t *const *d_msgs, const uint64_t *d_sizes, uint32_t n_msgs,
                         const uint8_t *d_elem, int elem, uint8_t *const *d_blobs, const uint64_t *d_blob_cap,
                         uint64_t *d_out_len, int32_t *d_status, void *hip_stream);
+/* ENCODE-NARROW WITH ERROR FEEDBACK — tdt_encode_narrow_v for a sender that keeps an fp32 residual r per
+ * tensor: the value narrowed and encoded is v = g + r, and r is updated in place to what the wire lost,
+ * in the same launches.  Conventions, statuses, routing, tile path, workspace, capture terms and
+ * TDT_STAT_NARROW_LARGE / NARROW_TILES are tdt_encode_narrow_v's.
+ *   d_resid: device array of n_msgs addresses, message i's fp32 residual of d_sizes[i] bytes.  NULL with
+ *     n_msgs > 0 is TDT_E_ARG.  An entry of 0 means no feedback for that tensor: the message is encoded
+ *     exactly as by tdt_encode_narrow_v.  A residual that is not 4-byte aligned is TDT_E_ELEMENT (per
+ *     message); otherwise it may have any alignment relative to its source.  A residual must not overlap
+ *     any source, blob or other residual of the call.
+ *   The rule per element, g the source, r the residual, beside the narrowing rule above:
+ *     v  = g + r          one fp32 addition: nearest even, subnormal operands and results kept, never contracted
+ *     h  = narrow(v)      the integer rule above; h goes to the wire
+ *     r' = v - widen(h)   one fp32 subtraction, exact whenever h is finite
+ *     r' = bit pattern 0  when h is an infinity or a NaN (wire exponent field all ones): one overflowing or
+ *                         NaN gradient does not stay in the residual
+ *   The contract: blob i, d_out_len[i] and d_status[i] are byte for byte what tdt_encode_narrow_v gives for an
+ *     fp32 tensor holding v, with the same capacity, options and raw-fallback setting, on every route (UNCP by
+ *     policy or size floor, TDT, raw fallback, one workgroup, tiles).  r' is written to every element of a
+ *     message whose status is TDT_OK, the UNCP and raw-fallback forms included (the wire is narrowed there
+ *     too).  For a refused message (TDT_E_ARG, TDT_E_ELEMENT, TDT_E_CAPACITY) the residual is untouched, bit
+ *     for bit: every refusal precedes the first store to blob and residual alike.  No byte outside
+ *     [d_resid[i], d_resid[i] + d_sizes[i]) is written.
+ *   Cost: a residual adds 4 bytes read per element and pass and 4 bytes written; a tensor of up to 16,384
+ *     elements is read twice (the second time to form r' once its status is known), a longer one three
+ *     times on one workgroup and twice as tiles, as without feedback. */
+int tdt_encode_narrow_ef_v(tdt_ctx *ctx, const uint8_t *const *d_msgs, const uint64_t *d_sizes, uint32_t n_msgs,
+                           uint8_t *const *d_resid, const uint8_t *d_elem, int elem, uint8_t *const *d_blobs,
+                           const uint64_t *d_blob_cap, uint64_t *d_out_len, int32_t *d_status, void *hip_stream);
 /* MIXED WORD SIZES — tdt_encode_batch_v with one record width per message (a mixed-precision
  * gradient list: bf16 / fp16 tensors at width 2 beside fp32 ones at 4 and fp64 / int64 ones at 8).
  * d_word_size[i] (device memory, n_msgs entries) is message i's width; the context's own word_size

@@ -96,6 +96,7 @@ SIGNATURES = {
     "tdt_decode_reduce_v": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, C.c_int, C.c_uint32, _vp, _vp,
                                       _vp, _vp]),
     "tdt_encode_narrow_v": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "tdt_encode_narrow_ef_v": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "tdt_decoded_sizes_v": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp]),
     "tdt_encode_slots": (C.c_int, [_vp, _vp, C.c_uint32, _vp, _vp]),
     "tdt_decode_slots": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp]),

@@ -3649,15 +3649,18 @@ int nar_tiled_end(tdt_ctx *c, const NarTiled &x, hipStream_t s) {
 }  // namespace
 #endif
 
-int tdt_encode_narrow_v(tdt_ctx *ctx, const uint8_t *const *d_msgs, const uint64_t *d_sizes, uint32_t n_msgs,
-                        const uint8_t *d_elem, int elem, uint8_t *const *d_blobs, const uint64_t *d_blob_cap,
-                        uint64_t *d_out_len, int32_t *d_status, void *stream) {
+// tdt_encode_narrow_v (ef false, d_resid null) and tdt_encode_narrow_ef_v: the same plan, launches and
+// snapshot; with d_resid the kernels' error-feedback instances run (tdt_enc_narrow.h).
+static int encode_narrow_common(tdt_ctx *ctx, const uint8_t *const *d_msgs, const uint64_t *d_sizes, uint32_t n_msgs,
+                                uint8_t *const *d_resid, bool ef, const uint8_t *d_elem, int elem, uint8_t *const *d_blobs,
+                                const uint64_t *d_blob_cap, uint64_t *d_out_len, int32_t *d_status, void *stream) {
     if (!ctx) return set_err(TDT_E_ARG, "null context");
     if (!d_elem && elem != TDT_ELEM_BF16_FROM_F32 && elem != TDT_ELEM_F16_FROM_F32)
         return set_err(TDT_E_ARG, "no narrowing element code");
     if (n_msgs == 0) return TDT_OK;
     if (!(d_msgs && d_sizes && d_blobs && d_blob_cap && d_out_len && d_status))
         return set_err(TDT_E_ARG, "null pointer, size, length or status array");
+    if (ef && !d_resid) return set_err(TDT_E_ARG, "null residual array");
 #if PSY_HAVE_ANYWS
     HIPCHK(hipSetDevice(ctx->device));
     psy::NarrowArgs a{};
@@ -3670,6 +3673,7 @@ int tdt_encode_narrow_v(tdt_ctx *ctx, const uint8_t *const *d_msgs, const uint64
     a.blob_cap = d_blob_cap;
     a.out_len = d_out_len;
     a.status = d_status;
+    a.resid = reinterpret_cast<const uint64_t *>(d_resid);
     std::lock_guard<std::mutex> g(ctx->mu);  // (the metrics, the config and the option as one call sees them)
     a.min_tensor = ctx->cfg.min_tensor_size;
     a.policy_on = policy_on(ctx) ? 1 : 0;
@@ -3687,6 +3691,20 @@ int tdt_encode_narrow_v(tdt_ctx *ctx, const uint8_t *const *d_msgs, const uint64
     (void)stream;
     return set_err(TDT_E_UNSUPPORTED, "this build holds no encode-narrow kernel");
 #endif
+}
+
+int tdt_encode_narrow_v(tdt_ctx *ctx, const uint8_t *const *d_msgs, const uint64_t *d_sizes, uint32_t n_msgs,
+                        const uint8_t *d_elem, int elem, uint8_t *const *d_blobs, const uint64_t *d_blob_cap,
+                        uint64_t *d_out_len, int32_t *d_status, void *stream) {
+    return encode_narrow_common(ctx, d_msgs, d_sizes, n_msgs, nullptr, false, d_elem, elem, d_blobs, d_blob_cap, d_out_len,
+                                d_status, stream);
+}
+
+int tdt_encode_narrow_ef_v(tdt_ctx *ctx, const uint8_t *const *d_msgs, const uint64_t *d_sizes, uint32_t n_msgs,
+                           uint8_t *const *d_resid, const uint8_t *d_elem, int elem, uint8_t *const *d_blobs,
+                           const uint64_t *d_blob_cap, uint64_t *d_out_len, int32_t *d_status, void *stream) {
+    return encode_narrow_common(ctx, d_msgs, d_sizes, n_msgs, d_resid, true, d_elem, elem, d_blobs, d_blob_cap, d_out_len,
+                                d_status, stream);
 }
 
 int tdt_decoded_sizes_v(tdt_ctx *ctx, const uint8_t *const *d_blobs, const uint64_t *d_blob_len, uint32_t n_msgs,

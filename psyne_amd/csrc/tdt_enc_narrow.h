@@ -28,6 +28,23 @@
 // cross the chunks.  Blobs, lengths and statuses are the width-2 encode's of the narrowed bytes.
 // Above the large-message threshold a tensor leaves this kernel for the tile passes of
 // tdt_enc_narrow_tiled.h (two reads, one workgroup per chunk); its bytes are the same.
+//
+// Error feedback (tdt_encode_narrow_ef_v) is a second instance of every kernel that reads the source
+// (template <bool EF>; the instances without it are the code they were).  Where a tensor has a residual
+// r, every read of the source g becomes a read of g and r and one v_add_f32, v = g + r, and the narrowed
+// halfword h is v's.  r' = v - widen(h) is stored by the LAST pass that reads the element, behind the
+// status decision, by a lane that has read it in that pass — r is updated in place, so no read of r[e]
+// may follow the write of r'[e]:
+//   longer than kNarResident   H and C form v again from g and r (the sum is deterministic); the emit
+//                              pass's restaging of a chunk stores the chunk's r' (the byte before a chunk
+//                              travels in NarCarry::lastb, not through memory); on the UNCP routes the
+//                              group copy stores it.  3 x (4 + 4) bytes read, 4 written per element
+//   resident                   the planes are staged in H, before length and capacity are known, and v
+//                              is not kept (64 VGPRs a lane): behind the decision one more pass reads g
+//                              and r, narrows again and stores r'.  2 x (4 + 4) read, 4 written
+//   tiles                      A reads g + r, E stores its own tile's r' on both routes and reads no
+//                              residual outside its tile: the halfword before the tile comes from the
+//                              tile record (NarTileRec::prev, written by A).  2 x (4 + 4) read, 4 written
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -56,6 +73,7 @@ struct NarrowArgs {
     int32_t policy_on;           // as EncodeArgs::policy_on
     int32_t raw_fallback;        // TDT_OPT_RAW_FALLBACK
     const uint32_t *mark;        // null, or one word per message: non-zero = the tile passes have it (tdt_enc_narrow_tiled.h)
+    const uint64_t *resid;       // null: tdt_encode_narrow_v; else the residual addresses of tdt_encode_narrow_ef_v (0: none)
 };
 
 // One launch per 2^24 - 1 messages on stream s.  Returns a hipError_t as int (0: launched).

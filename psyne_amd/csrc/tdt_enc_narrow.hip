@@ -78,17 +78,70 @@ __device__ __forceinline__ void nar_narrow4(const uint32_t (&u)[4], bool bf, uin
     h23 = h[2] | (h[3] << 16);
 }
 
+// ---- error feedback (psyne_tdt.h, tdt_encode_narrow_ef_v): the value narrowed is v = g + r
+// Elements e .. e + 3 of v; EF and a residual: the source plus the residual, one v_add_f32 each (subnormals
+// kept: the kernels' float mode); else the source as it is.
+template <bool EF>
+__device__ __forceinline__ void nar_value4(const uint8_t *src, const uint8_t *res, uint64_t e, uint64_t ne, uint32_t (&u)[4]) {
+    nar_load4(src, e, ne, u);
+    if constexpr (EF) {
+        if (res) {  // (uniform)
+            uint32_t r[4];
+            nar_load4(res, e, ne, r);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) u[i] = __float_as_uint(__uint_as_float(u[i]) + __uint_as_float(r[i]));
+        }
+    }
+}
+// r' = v - widen(h) of elements e .. e + 3 (u: v's bit patterns, h01 / h23: nar_narrow4's) to the residual,
+// bit pattern 0 where h is an infinity or a NaN; those at or past ne are not touched.
+__device__ __forceinline__ void nar_resid4(uint8_t *res, uint64_t e, uint64_t ne, const uint32_t (&u)[4], bool bf, uint32_t h01,
+                                           uint32_t h23) {
+    uint32_t o[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const uint32_t h = ((i < 2 ? h01 : h23) >> (16 * (i & 1))) & 0xffffu;
+        const uint32_t wide = bf ? h << 16 : __float_as_uint((float)__builtin_bit_cast(_Float16, (uint16_t)h));
+        const uint32_t ex = bf ? 0x7f80u : 0x7c00u;
+        o[i] = (h & ex) == ex ? 0u : __float_as_uint(__uint_as_float(u[i]) - __uint_as_float(wide));
+    }
+    uint8_t *p = res + 4ull * e;
+    if (e + 4 <= ne && ((uintptr_t)p & 15) == 0) {
+        psy_u32x4 t;
+        t.x = o[0], t.y = o[1], t.z = o[2], t.w = o[3];
+        *(__attribute__((address_space(1))) psy_u32x4 *)(p) = t;
+    } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            if (e + i < ne) *(__attribute__((address_space(1))) uint32_t *)(p + 4 * i) = o[i];
+    }
+}
+// The resident form's last pass: v again from one more read of the source and the residual, r' stored.
+__device__ __forceinline__ void nar_resid_pass(const uint8_t *src, uint8_t *res, uint32_t ne, bool bf) {
+    for (uint32_t k = threadIdx.x; 4u * k < ne; k += kNarTeam) {
+        uint32_t u[4], h01, h23;
+        nar_value4<true>(src, res, 4ull * k, ne, u);
+        nar_narrow4(u, bf, h01, h23);
+        nar_resid4(res, 4ull * k, ne, u, bf, h01, h23);
+    }
+}
+
 // Elements [eb, eb + cnt) of the source into the planes (cnt <= kNarResident; the planes' bytes past
-// cnt are left as they are); HIST: counted into this lane's copy of the bins.
-template <bool HIST>
-__device__ __forceinline__ void nar_stage(const uint8_t *src, uint64_t eb, uint32_t cnt, bool bf, uint8_t *s_pl, uint32_t *s_hist) {
+// cnt are left as they are); HIST: counted into this lane's copy of the bins.  EF: of source + residual
+// (nar_value4); WR: this is the last read of these elements, and r' is stored behind it.
+template <bool HIST, bool EF = false, bool WR = false>
+__device__ __forceinline__ void nar_stage(const uint8_t *src, uint8_t *res, uint64_t eb, uint32_t cnt, bool bf, uint8_t *s_pl,
+                                          uint32_t *s_hist) {
     uint32_t *p0 = reinterpret_cast<uint32_t *>(s_pl), *p1 = reinterpret_cast<uint32_t *>(s_pl + kNarResident);
     uint32_t *h = s_hist + (threadIdx.x & (kNarHistCopies - 1u)) * 512u;
 #pragma unroll 2
     for (uint32_t k = threadIdx.x; 4u * k < cnt; k += kNarTeam) {
         uint32_t u[4], h01, h23;
-        nar_load4(src, eb + 4ull * k, eb + cnt, u);
+        nar_value4<EF>(src, res, eb + 4ull * k, eb + cnt, u);
         nar_narrow4(u, bf, h01, h23);
+        if constexpr (EF && WR) {
+            if (res) nar_resid4(res, eb + 4ull * k, eb + cnt, u, bf, h01, h23);
+        }
         const uint32_t lo = perm(h23, h01, 0x06040200u), hi = perm(h23, h01, 0x07050301u);
         p0[k] = lo;
         p1[k] = hi;
@@ -252,9 +305,11 @@ __device__ __forceinline__ void nar_step(const uint8_t *s_pl, bool inter, uint32
 }
 
 // The 16-byte groups [g0, g1) of the w = 2 ne narrowed bytes behind the marker, one per lane and store.
-// staged: the planes hold the whole message (ne <= kNarResident); else it is narrowed from the source again.
-__device__ __forceinline__ void nar_uncp_groups(uint8_t *dst, const uint8_t *src, uint64_t ne, bool bf, bool staged, const uint8_t *s_pl,
-                                                uint64_t g0, uint64_t g1) {
+// staged: the planes hold the whole message (ne <= kNarResident); else it is narrowed from the source again
+// (EF: from source + residual, and r' of the groups' elements is stored: the last read of them).
+template <bool EF = false>
+__device__ __forceinline__ void nar_uncp_groups(uint8_t *dst, const uint8_t *src, uint8_t *res, uint64_t ne, bool bf, bool staged,
+                                                const uint8_t *s_pl, uint64_t g0, uint64_t g1) {
     const uint64_t w = 2ull * ne;
     for (uint64_t g = g0 + threadIdx.x; g < g1; g += kNarTeam) {
         const int valid = w - 16ull * g >= 16 ? 16 : (int)(w - 16ull * g);
@@ -266,20 +321,30 @@ __device__ __forceinline__ void nar_uncp_groups(uint8_t *dst, const uint8_t *src
                            perm(hi.y, lo.y, 0x07030602u));
         } else {
             uint32_t u[4];
-            nar_load4(src, 8ull * g, ne, u);
+            nar_value4<EF>(src, res, 8ull * g, ne, u);
             nar_narrow4(u, bf, v.x, v.y);
-            nar_load4(src, 8ull * g + 4, ne, u);
+            if constexpr (EF) {
+                if (res) nar_resid4(res, 8ull * g, ne, u, bf, v.x, v.y);
+            }
+            nar_value4<EF>(src, res, 8ull * g + 4, ne, u);
             nar_narrow4(u, bf, v.z, v.w);
+            if constexpr (EF) {
+                if (res) nar_resid4(res, 8ull * g + 4, ne, u, bf, v.z, v.w);
+            }
         }
         st16_any(dst + 4 + 16ull * g, v, valid);
     }
 }
 // The UNCP form: the marker and every group.
-__device__ __forceinline__ void nar_uncp(uint8_t *dst, const uint8_t *src, uint64_t ne, bool bf, bool staged, const uint8_t *s_pl) {
+template <bool EF = false>
+__device__ __forceinline__ void nar_uncp(uint8_t *dst, const uint8_t *src, uint8_t *res, uint64_t ne, bool bf, bool staged,
+                                         const uint8_t *s_pl) {
     if (threadIdx.x < 4) dst[threadIdx.x] = (uint8_t)(kMagicUNCP >> (8 * threadIdx.x));
-    nar_uncp_groups(dst, src, ne, bf, staged, s_pl, 0, (2ull * ne + 15) / 16);
+    nar_uncp_groups<EF>(dst, src, res, ne, bf, staged, s_pl, 0, (2ull * ne + 15) / 16);
 }
 
+// EF: the instance of tdt_encode_narrow_ef_v (a.resid is set; an entry of 0: that message as without it)
+template <bool EF>
 __global__ __launch_bounds__(kNarTeam) void tdt_encode_narrow_kernel(NarrowArgs a, uint32_t base) {
     __shared__ __attribute__((aligned(16))) uint8_t s_pl[2 * kNarResident];
     __shared__ __attribute__((aligned(16))) uint32_t s_un[kNarHistCopies * 512];  // the histogram copies, then the pair stage
@@ -295,15 +360,17 @@ __global__ __launch_bounds__(kNarTeam) void tdt_encode_narrow_kernel(NarrowArgs 
     const uint64_t srca = a.msgs[msg], size = a.sizes[msg], cap = a.blob_cap[msg];
     const uint8_t *src = reinterpret_cast<const uint8_t *>(srca);
     uint8_t *dst = reinterpret_cast<uint8_t *>(a.blobs[msg]);
+    uint8_t *res = nullptr;
+    if constexpr (EF) res = reinterpret_cast<uint8_t *>(a.resid[msg]);
     auto report = [&](int32_t st, uint64_t len) __attribute__((always_inline)) {
         if (tid == 0) {
             if (a.status) a.status[msg] = st;
             if (a.out_len) a.out_len[msg] = len;
         }
     };
-    // every refusal precedes the first store
+    // every refusal precedes the first store, to the blob and to the residual
     if (code != kNarBF16 && code != kNarF16) return report(ST_ARG, 0);
-    if ((srca & 3u) || (size & 3u)) return report(kNarStElement, 0);
+    if ((srca & 3u) || (size & 3u) || ((uintptr_t)res & 3u)) return report(kNarStElement, 0);
     const bool bf = code == kNarBF16;
     const uint64_t ne = size / 4, w = size / 2;  // elements, wire bytes
     // should_transform :186-201 and compress_tdt's size guard :364-367 on the wire size, at word size 2
@@ -311,7 +378,7 @@ __global__ __launch_bounds__(kNarTeam) void tdt_encode_narrow_kernel(NarrowArgs 
     if (!compress) {
         const bool fits = w + 4 <= cap;
         report(fits ? ST_OK : ST_CAPACITY, fits ? w + 4 : 0);
-        if (fits) nar_uncp(dst, src, ne, bf, false, s_pl);
+        if (fits) nar_uncp<EF>(dst, src, res, ne, bf, false, s_pl);
         return;
     }
     const uint32_t ne32 = (uint32_t)ne, w32 = (uint32_t)w;
@@ -321,7 +388,7 @@ __global__ __launch_bounds__(kNarTeam) void tdt_encode_narrow_kernel(NarrowArgs 
     for (uint32_t i = tid; i < kNarHistCopies * 512u; i += kNarTeam) s_un[i] = 0u;
     __syncthreads();
     for (uint32_t eb = 0; eb < ne32; eb += kNarResident)
-        nar_stage<true>(src, eb, ne32 - eb < kNarResident ? ne32 - eb : kNarResident, bf, s_pl, s_un);
+        nar_stage<true, EF>(src, res, eb, ne32 - eb < kNarResident ? ne32 - eb : kNarResident, bf, s_pl, s_un);
     __syncthreads();
     // ---- M: entropies, then perform_clustering :507-525: entropy > in-order sum / 2
     if (wv < 2u) {
@@ -352,7 +419,7 @@ __global__ __launch_bounds__(kNarTeam) void tdt_encode_narrow_kernel(NarrowArgs 
             const uint32_t cnt = ne32 - eb < kNarResident ? ne32 - eb : kNarResident;
             if (!resident) {
                 __syncthreads();  // (the chunk before is read)
-                nar_stage<false>(src, eb, cnt, bf, s_pl, s_un);
+                nar_stage<false, EF, EMIT>(src, res, eb, cnt, bf, s_pl, s_un);  // (the emit pass: the chunk's last read, r' behind it)
                 __syncthreads();
             }
 #pragma unroll
@@ -394,8 +461,11 @@ __global__ __launch_bounds__(kNarTeam) void tdt_encode_narrow_kernel(NarrowArgs 
     const bool fits = E <= cap;
     report(fits ? ST_OK : ST_CAPACITY, fits ? E : 0);
     if (!fits) return;
+    if constexpr (EF) {
+        if (resident && res) nar_resid_pass(src, res, ne32, bf);  // (neither route below reads the source again)
+    }
     if (raw) {
-        nar_uncp(dst, src, ne, bf, resident, s_pl);
+        nar_uncp<EF>(dst, src, res, ne, bf, resident, s_pl);
         return;
     }
     // ---- E: header (serialize :81-117): magic, original size, streams, word size, mapping; length words
@@ -420,9 +490,13 @@ __device__ __forceinline__ uint32_t nar_claimed(const NarTiledArgs &t, NarCount 
     return (uint32_t)__builtin_amdgcn_readfirstlane((int)(c < cap ? (uint32_t)c : cap));
 }
 __device__ __forceinline__ uint32_t nar_uniform(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }
-// the wire halfword of element e
-__device__ __forceinline__ uint32_t nar_halfword(const uint8_t *src, uint64_t e, bool bf) {
-    const uint32_t u = gload<uint32_t>(src + 4ull * e);
+// the wire halfword of element e (EF and a residual: of source + residual, as nar_value4)
+template <bool EF = false>
+__device__ __forceinline__ uint32_t nar_halfword(const uint8_t *src, const uint8_t *res, uint64_t e, bool bf) {
+    uint32_t u = gload<uint32_t>(src + 4ull * e);
+    if constexpr (EF) {
+        if (res) u = __float_as_uint(__uint_as_float(u) + __uint_as_float(gload<uint32_t>(res + 4ull * e)));
+    }
     return bf ? nar_bf16(u) : nar_f16(u);
 }
 // the bytes of d that are not 0, as a 4-bit mask (the tail of neq_prev_mask4)
@@ -445,13 +519,14 @@ __global__ __launch_bounds__(1024) void tdt_narrow_plan_kernel(NarTiledArgs t) {
     const uint32_t msg = blockIdx.x * 1024u + threadIdx.x, lane = (uint32_t)lane_id();
     bool want = false;
     uint32_t code = 0u;
-    uint64_t srca = 0, size = 0;
+    uint64_t srca = 0, size = 0, resa = 0;
     if (msg < a.n_msgs) {
         code = a.elem_codes ? (uint32_t)a.elem_codes[msg] : a.elem;
         srca = a.msgs[msg];
         size = a.sizes[msg];
+        if (a.resid) resa = a.resid[msg];
         // (everything else is the one-workgroup kernel's: the refusals, a wire size of 2^32 and more)
-        want = (code == kNarBF16 || code == kNarF16) && !((srca | size) & 3u) && size / 2 < (1ull << 32) && size > t.large_min;
+        want = (code == kNarBF16 || code == kNarF16) && !((srca | size | resa) & 3u) && size / 2 < (1ull << 32) && size > t.large_min;
     }
     const uint64_t ne = size / 4, w = size / 2;
     const uint32_t nt = want ? (uint32_t)((ne + kNarTile - 1) / kNarTile) : 0u;
@@ -472,6 +547,7 @@ __global__ __launch_bounds__(1024) void tdt_narrow_plan_kernel(NarTiledArgs t) {
         if (ok) {
             g.src = reinterpret_cast<const uint8_t *>(srca);
             g.dst = reinterpret_cast<uint8_t *>(a.blobs[msg]);
+            g.res = reinterpret_cast<uint8_t *>(resa);
             g.cap = a.blob_cap[msg];
             g.msg = msg;
             g.ne = (uint32_t)ne;
@@ -498,6 +574,7 @@ __global__ __launch_bounds__(1024) void tdt_narrow_plan_kernel(NarTiledArgs t) {
 }
 
 // ---- A: one tile staged once — its bins, and the run records of all three candidate streams
+template <bool EF>
 __global__ __launch_bounds__(kNarTeam) void tdt_narrow_analyse_kernel(NarTiledArgs t) {
     __shared__ __attribute__((aligned(16))) uint8_t s_pl[2 * kNarResident];
     __shared__ __attribute__((aligned(16))) uint32_t s_hist[kNarHistCopies * 512];
@@ -514,14 +591,18 @@ __global__ __launch_bounds__(kNarTeam) void tdt_narrow_analyse_kernel(NarTiledAr
         const uint32_t flags = nar_uniform(g.flags);
         if (flags & kNarUncpRouted) continue;  // (nothing to decide: its tiles copy)
         const uint8_t *src = g.src;
+        uint8_t *res = EF ? g.res : nullptr;
         const bool bf = (flags & kNarIsBf16) != 0u;
         const uint32_t eb = (e - nar_uniform(g.tile0)) * kNarTile, ne = nar_uniform(g.ne);
         const uint32_t cnt = ne - eb < kNarTile ? ne - eb : kNarTile;
         __syncthreads();  // (the tile before is done with the planes and s_first; the copies are zero)
         if (tid < (uint32_t)kNarCand) s_first[tid] = 0u;
-        nar_stage<true>(src, eb, cnt, bf, s_pl, s_hist);
-        // the bytes before the tile: element eb - 1
-        const uint32_t hb = eb ? nar_halfword(src, eb - 1u, bf) : 0u;
+        nar_stage<true, EF>(src, res, eb, cnt, bf, s_pl, s_hist);
+        // the bytes before the tile: element eb - 1 (EF: kept for the emit pass, which must not read it again)
+        const uint32_t hb = eb ? nar_halfword<EF>(src, res, eb - 1u, bf) : 0u;
+        if constexpr (EF) {
+            if (tid == 0) r.prev = hb;
+        }
         const uint32_t pl = hb & 0xffu, ph = hb >> 8;
         __syncthreads();
         // the copies → the tensor's bins (integer adds: any order gives the same counts)
@@ -712,6 +793,7 @@ __global__ __launch_bounds__(kNarTeam) void tdt_narrow_map_kernel(NarTiledArgs t
 }
 
 // ---- E: one tile's pairs of the chosen stream(s), or its share of the UNCP form
+template <bool EF>
 __global__ __launch_bounds__(kNarTeam) void tdt_narrow_emit_kernel(NarTiledArgs t) {
     __shared__ __attribute__((aligned(16))) uint8_t s_pl[2 * kNarResident];
     __shared__ __attribute__((aligned(16))) uint32_t s_stage[(2u * kNarStagePairs + 8u + 3u) / 4u];
@@ -728,12 +810,13 @@ __global__ __launch_bounds__(kNarTeam) void tdt_narrow_emit_kernel(NarTiledArgs 
         if (route == kNarRefused) continue;  // (nothing is written)
         const uint8_t *src = g.src;
         uint8_t *dst = g.dst;
+        uint8_t *res = EF ? g.res : nullptr;
         const bool bf = (nar_uniform(g.flags) & kNarIsBf16) != 0u;
         const uint32_t tt = e - nar_uniform(g.tile0), eb = tt * kNarTile, ne = nar_uniform(g.ne);
         const uint32_t cnt = ne - eb < kNarTile ? ne - eb : kNarTile;
         if (route == kNarRaw) {  // the tile's wire bytes behind the marker (a tile is whole 16-byte groups)
             if (tt == 0u && tid < 4u) dst[tid] = (uint8_t)(kMagicUNCP >> (8 * tid));
-            nar_uncp_groups(dst, src, ne, bf, false, nullptr, eb / 8u, (2ull * (eb + cnt) + 15) / 16);
+            nar_uncp_groups<EF>(dst, src, res, ne, bf, false, nullptr, eb / 8u, (2ull * (eb + cnt) + 15) / 16);
             continue;
         }
         const uint32_t m0 = nar_uniform(g.m0), m1 = nar_uniform(g.m1);
@@ -741,8 +824,11 @@ __global__ __launch_bounds__(kNarTeam) void tdt_narrow_emit_kernel(NarTiledArgs 
         const bool inter = ns == 1u;
         const uint32_t S = inter ? 2u * ne : ne;
         __syncthreads();  // (the tile before is done with the planes)
-        nar_stage<false>(src, eb, cnt, bf, s_pl, nullptr);
-        const uint32_t hb = eb ? nar_halfword(src, eb - 1u, bf) : 0u;  // the bytes before the tile
+        nar_stage<false, EF, true>(src, res, eb, cnt, bf, s_pl, nullptr);  // (EF: the tile's r' behind its last read)
+        // the bytes before the tile (EF: as the analyse pass saw them; that element's residual may be rewritten by now)
+        uint32_t hb;
+        if constexpr (EF) hb = eb ? nar_uniform(r.prev) : 0u;
+        else hb = eb ? nar_halfword(src, nullptr, eb - 1u, bf) : 0u;
         __syncthreads();
         uint8_t *const pairs[2] = {dst + 32, dst + 32 + 2ull * g.pairs[0] + 4};
 #pragma unroll
@@ -786,9 +872,10 @@ int launch_narrow_plan(const NarTiledArgs &t, hipStream_t s) {
 
 int launch_narrow_tiles(const NarTiledArgs &t, hipStream_t s) {
     const dim3 tg(std::max(1u, std::min(t.tcap, t.grid))), lg(std::max(1u, std::min(t.lcap, t.grid)));
-    hipLaunchKernelGGL(tdt_narrow_analyse_kernel, tg, dim3(kNarTeam), 0, s, t);
+    const bool ef = t.a.resid != nullptr;  // tdt_encode_narrow_ef_v
+    hipLaunchKernelGGL(ef ? tdt_narrow_analyse_kernel<true> : tdt_narrow_analyse_kernel<false>, tg, dim3(kNarTeam), 0, s, t);
     hipLaunchKernelGGL(tdt_narrow_map_kernel, lg, dim3(kNarTeam), 0, s, t);
-    hipLaunchKernelGGL(tdt_narrow_emit_kernel, tg, dim3(kNarTeam), 0, s, t);
+    hipLaunchKernelGGL(ef ? tdt_narrow_emit_kernel<true> : tdt_narrow_emit_kernel<false>, tg, dim3(kNarTeam), 0, s, t);
     return (int)hipGetLastError();
 }
 
@@ -801,7 +888,8 @@ int launch_encode_narrow(const NarrowArgs &a, hipStream_t s) {
     // one workgroup per message; a launch holds < 2^32 threads
     const uint32_t maxb = 0xffffffffu / kNarTeam;
     for (uint32_t b = 0; b < a.n_msgs; b += maxb)
-        hipLaunchKernelGGL(tdt_encode_narrow_kernel, dim3(std::min(maxb, a.n_msgs - b)), dim3(kNarTeam), 0, s, a, b);
+        hipLaunchKernelGGL(a.resid ? tdt_encode_narrow_kernel<true> : tdt_encode_narrow_kernel<false>,
+                           dim3(std::min(maxb, a.n_msgs - b)), dim3(kNarTeam), 0, s, a, b);
     return (int)hipGetLastError();
 }
 

@@ -7,7 +7,7 @@
 // one-workgroup kernel, and the tile edges are its chunk edges), one workgroup per tile.  The source
 // is read twice: once to analyse, once to emit.  Passes, all on the caller's stream, in order
 // (DESIGN.md §4); the host reads nothing back:
-//   plan   one lane per tensor.  The rule: a valid code, source and size 4-byte aligned, a wire size
+//   plan   one lane per tensor.  The rule: a valid code, source, size (and residual) 4-byte aligned, a wire size
 //          below 2^32, a source size above large_min (no 1/4096-of-the-batch term: the one-workgroup
 //          path costs three reads however busy the device is).  Such a tensor claims
 //          (workgroup-aggregated atomics) one NarLarge record and ceil(ne / kNarTile) NarTile records;
@@ -34,6 +34,9 @@
 //          the marker too.  Otherwise the tile is restaged (nar_stage<false>) and nar_step<true> runs
 //          over the chosen stream(s) from the record's carry, writing at pairs[s] + 2 base: the run
 //          that crosses into the tile first, and in a stream's last tile the final run behind the rest.
+//          With error feedback (tdt_enc_narrow.h) A reads g + r and leaves the halfword of the element
+//          before its tile in the record; E takes it from there — that element's residual is another
+//          workgroup's to overwrite — and stores r' for its own tile on either route.
 //   snap   the counter block to the pinned snapshot (not under capture) and zero again for the next call.
 // A run that spans many tiles (an all-zero tensor) is written by the one workgroup whose tile holds
 // the start that closes it, or by the last tile: one nar_fill of at most 2 w / 255 bytes.
@@ -61,11 +64,13 @@ struct NarLarge {
     uint32_t route;          // (M) what the emit pass writes
     uint32_t m0, m1;         // (M) the mapping
     uint32_t pairs[2];       // (M) pairs of either stream
+    uint8_t *res;            // the residual of tdt_encode_narrow_ef_v (null: none)
 };
 struct NarTileRec {  // record tile0 + t of its tensor is the tensor's tile t
     uint32_t owner;                                             // (plan) the NarLarge record, or kNarNoOwner
     uint32_t first[kNarCand], last[kNarCand], inner[kNarCand];  // (A) per candidate, tdt_anyws_tiles.h
     uint32_t carry[2], base[2];                                 // (M) per chosen stream
+    uint32_t prev;                                              // (A, with error feedback) the wire halfword of the element before the tile
 };
 constexpr uint32_t kNarNoOwner = 0xffffffffu;
 

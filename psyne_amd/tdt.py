@@ -339,21 +339,35 @@ class TdtCodec:
         return lengths, status
 
     def encode_narrow_v(self, ptrs, sizes, out_ptrs, out_caps, elems=None, elem=_lib.TDT_ELEM_BF16_FROM_F32, lengths=None,
-                        status=None, stream=None):
+                        status=None, stream=None, resid_ptrs=None):
         """encode_v of float32 messages narrowed on the way: message i = sizes[i] bytes of float32 at
         address ptrs[i] is encoded as the width-2 blob of its bfloat16 / float16 narrowing (code
         elems[i], a uint8 tensor on the GPU of TDT_ELEM_BF16_FROM_F32 / TDT_ELEM_F16_FROM_F32 values;
         None: `elem` for every message) into out_caps[i] bytes at out_ptrs[i] — what a codec of
         word_size 2 gives for the sizes[i] / 2 narrowed bytes, raw fallback included, in one launch and
-        without a half-precision copy.  Returns (lengths, status)."""
+        without a half-precision copy.  Returns (lengths, status).
+
+        resid_ptrs (an int64 tensor on the GPU, one address per message; None: no error feedback):
+        message i has a float32 residual r of sizes[i] bytes at resid_ptrs[i] (0: none for it).  Per
+        element v = g + r in float32 is what is narrowed and encoded, and r becomes v - widen(narrow(v)),
+        exactly what the wire lost — bit pattern 0 where the wire value is an infinity or a NaN.  The
+        residual of a message whose status is not 0 is untouched, bit for bit; a residual must not overlap
+        a source, a blob or another residual of the call."""
         import torch
         n = sizes.numel()
         if elems is not None and (elems.dtype != torch.uint8 or elems.numel() < n):
             raise ValueError("elems must be a uint8 tensor of one code per message")
+        if resid_ptrs is not None and (resid_ptrs.dtype != torch.int64 or resid_ptrs.numel() < n):
+            raise ValueError("resid_ptrs must be an int64 tensor of one address per message")
         if lengths is None:
             lengths = torch.empty(max(n, 1), dtype=torch.int64, device=sizes.device)
         if status is None:
             status = torch.empty(max(n, 1), dtype=torch.int32, device=sizes.device)
+        if resid_ptrs is not None:
+            check(self._lib.tdt_encode_narrow_ef_v(self._h, _ptr(ptrs), _ptr(sizes), n, _ptr(resid_ptrs),
+                                                   _ptr(elems) if elems is not None else None, int(elem), _ptr(out_ptrs),
+                                                   _ptr(out_caps), _ptr(lengths), _ptr(status), self._stream(stream)))
+            return lengths, status
         check(self._lib.tdt_encode_narrow_v(self._h, _ptr(ptrs), _ptr(sizes), n, _ptr(elems) if elems is not None else None,
                                             int(elem), _ptr(out_ptrs), _ptr(out_caps), _ptr(lengths), _ptr(status),
                                             self._stream(stream)))
@@ -577,7 +591,7 @@ class TdtCodec:
         return ptrs, sizes
 
     def encode_tensors(self, tensors, out=None, stream=None, word_sizes=None, packed=False, exact=False, mapbits=None,
-                       return_mappings=False, wire_dtype=None):
+                       return_mappings=False, wire_dtype=None, residuals=None):
         """Encode a list of contiguous GPU tensors (message i = the bytes of tensors[i]) without
         packing them: blob i goes to out[slots[i]:slots[i+1]], the slots being the prefix sum of the
         encode bounds.  Returns (out, slots, lengths, status).
@@ -624,11 +638,22 @@ class TdtCodec:
         type (encode_narrow_v: the tensor is read once and no half-precision copy is made); the slots
         are the width-2 bounds of the wire sizes, n + 4 under raw_fallback.  Returns (out, slots,
         lengths, status).  It combines with none of word_sizes, packed, exact, mapbits and
-        return_mappings."""
+        return_mappings.
+
+        residuals (with wire_dtype only): error feedback.  A list with one entry per tensor, each a
+        contiguous float32 GPU tensor of that tensor's shape on its device, or None for a tensor without
+        feedback.  Per element v = g + r in float32 is narrowed and encoded instead of g, and the
+        residual is updated in place, in the same launches, to r = v - widen(narrow(v)): what the wire
+        lost, to be sent with the next step's gradient (bit pattern 0 where the wire value is an
+        infinity or a NaN, so that one bad gradient does not stay).  A tensor whose status is not 0
+        leaves its residual untouched, bit for bit.  A residual may overlap no tensor, `out` or other
+        residual."""
         import torch
+        if residuals is not None and wire_dtype is None:
+            raise ValueError("residuals need wire_dtype: error feedback belongs to the narrowed wire")
         if wire_dtype is not None:
-            return self._encode_tensors_narrow(tensors, out, stream, wire_dtype, word_sizes=word_sizes, packed=packed,
-                                               exact=exact, mapbits=mapbits, return_mappings=return_mappings)
+            return self._encode_tensors_narrow(tensors, out, stream, wire_dtype, residuals, word_sizes=word_sizes,
+                                               packed=packed, exact=exact, mapbits=mapbits, return_mappings=return_mappings)
         ptrs, sizes = self._tensor_table(tensors)
         n = len(tensors)
         if return_mappings and mapbits is not None:
@@ -710,8 +735,8 @@ class TdtCodec:
                                              stream=stream, mapbits=mapbits)
         return out, d[4 * n:5 * n + 1], lengths, status
 
-    def _encode_tensors_narrow(self, tensors, out, stream, wire_dtype, **others):
-        """encode_tensors(wire_dtype=...): the slotted form through encode_narrow_v."""
+    def _encode_tensors_narrow(self, tensors, out, stream, wire_dtype, residuals=None, **others):
+        """encode_tensors(wire_dtype=..., residuals=...): the slotted form through encode_narrow_v."""
         import torch
         for name, value in others.items():
             if value is not None and value is not False:
@@ -723,6 +748,23 @@ class TdtCodec:
                 raise ValueError("encode_tensors(wire_dtype=...) narrows float32 tensors, not %s" % t.dtype)
         ptrs, sizes = self._tensor_table(tensors)
         n = len(tensors)
+        parts = []
+        if residuals is not None:
+            if len(residuals) != n:
+                raise ValueError("%d residuals for %d tensors" % (len(residuals), n))
+            for t, r in zip(tensors, residuals):
+                if r is None:
+                    continue
+                if r.dtype != torch.float32:
+                    raise ValueError("a residual is a float32 tensor, not %s" % r.dtype)
+                if r.shape != t.shape:
+                    raise ValueError("a residual of shape %s for a tensor of shape %s" % (tuple(r.shape), tuple(t.shape)))
+                if r.device != t.device:
+                    raise ValueError("a residual on %s for a tensor on %s" % (r.device, t.device))
+            rptrs, _ = self._tensor_table([r for r in residuals if r is not None])
+            full = np.zeros(n, np.int64)
+            full[[i for i, r in enumerate(residuals) if r is not None]] = rptrs
+            parts = [full]
         dev = tensors[0].device if n else torch.device("cuda", self.device)
         slots = np.zeros(n + 1, np.int64)
         np.cumsum(self._bounds(sizes // 2, 2), out=slots[1:])
@@ -730,10 +772,11 @@ class TdtCodec:
             out = torch.empty(max(int(slots[-1]), 1), dtype=torch.uint8, device=dev)
         elif out.numel() < int(slots[-1]):
             raise ValueError("out holds %d bytes, the slots need %d" % (out.numel(), int(slots[-1])))
-        # one upload: addresses | sizes | blob addresses | capacities | slots
-        d = torch.from_numpy(np.concatenate([ptrs, sizes, out.data_ptr() + slots[:-1], np.diff(slots), slots])).to(dev)
+        # one upload: addresses | sizes | blob addresses | capacities | slots (| residual addresses)
+        d = torch.from_numpy(np.concatenate([ptrs, sizes, out.data_ptr() + slots[:-1], np.diff(slots), slots] + parts)).to(dev)
         code = _lib.TDT_ELEM_BF16_FROM_F32 if wire_dtype == torch.bfloat16 else _lib.TDT_ELEM_F16_FROM_F32
-        lengths, status = self.encode_narrow_v(d[:n], d[n:2 * n], d[2 * n:3 * n], d[3 * n:4 * n], elem=code, stream=stream)
+        lengths, status = self.encode_narrow_v(d[:n], d[n:2 * n], d[2 * n:3 * n], d[3 * n:4 * n], elem=code, stream=stream,
+                                               resid_ptrs=d[5 * n + 1:] if parts else None)
         return out, d[4 * n:5 * n + 1], lengths, status
 
     def _encode_tensors_mapped(self, tensors, ptrs, sizes, out, stream, word_sizes, packed, exact):
